@@ -12,7 +12,7 @@ hot path over the whole image.  At N GPUs the image is row-tiled (rank g renders
 row_range(H, N, g)) and gathered to rank 0 over RCCL at frame end; the timed region includes
 that gather.  Total work is fixed as N grows -> "scaling": "strong".
 
-  python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]   # DIR/frame.npy: the last timed frame
   python bench.py --gpus N [--config cfg3]        # spawns its N ranks itself (one process per GPU, RCCL)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W      # the driver's form: same ranks
@@ -55,6 +55,8 @@ BYTES_PER_PIXEL = 56   # 14 x f32 written per pixel per frame
 # VALU issue peak from MI355X_MICROARCH.md: a wave64 VALU instruction occupies its SIMD-32 for 2 cycles
 # ("v_fma_f32 (wave64): 2 cyc"), 256 CUs x 4 SIMDs, 2.4 GHz -> 1024 x 2.4e9 / 2 wave-instructions per second
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0  # = 1228.8 G wave-instr/s
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+DUMP_SAMPLE_PIXELS = 1 << 19         # pixels of the seeded sample of a frame above that limit (cfg3)
 
 
 def usable_cores():
@@ -116,6 +118,33 @@ def cpu_baseline(oracle, cfg, spheres, basis, rows):
     except Exception as e:  # a missing compiler must not lose the headline
         out["native_build"] = {"error": str(e)[:200]}
     return out
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what the last timed step computed -- the (H, W, 14) float32 frame a caller of the render path receives --
+    as out_dir/frame.npy.  A frame larger than DUMP_LIMIT_BYTES (cfg3: 4096^2 x 14 floats) is written as a fixed, seeded sample
+    of its pixels instead: frame_sample.npy (pixels x 14, float32) and their flat pixel indices, frame_sample_index.npy
+    (float64, exact).  The sample is the same in every run, so two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, c = frame.shape
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float32))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), np.ascontiguousarray(frame.reshape(h * w, c)[idx], dtype=np.float32))
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
+
+
+def save_frame(args, frame):
+    """Rank 0, after the timed steps: the frame of the last timed step to --dump (one .npy) and --dump-outputs (a directory)."""
+    import numpy as np
+
+    if args.dump:
+        np.save(args.dump, frame)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame)
 
 
 def spawn_ranks(args):
@@ -317,7 +346,12 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the side record of the other BASELINE configurations")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline renders (0 = size for ~8 s per build)")
     ap.add_argument("--dump", default=None, help="rank 0 saves the last gathered frame to this .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB: a seeded pixel "
+                         "sample of larger frames)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and args.engine == "dist" and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))  # before anything here touches the GPU
@@ -414,10 +448,8 @@ def main():
         probe = pt.Renderer(WIDTH, HEIGHT, spp, rng_mode=rng_mode, row_begin=rb, row_end=re_, variant=args.variant, persist_rng=False, max_bounces=MAXB)
         ki = probe.kernel_info(len(spheres))
         probe.destroy()
-        if args.dump:
-            import numpy as np
-
-            np.save(args.dump, frame.cpu().numpy().reshape(HEIGHT, WIDTH, 14))
+        if args.dump or args.dump_outputs:
+            save_frame(args, frame.cpu().numpy().reshape(HEIGHT, WIDTH, 14))
         alt = None
         fast = None
         others = None
@@ -470,9 +502,7 @@ def main():
             # ONE frame on its own (N > 1): render, then the gather, nothing overlapped -- the latency a caller of the synchronous
             # Renderer::Render sees ("ms/frame incl. RCCL gather"), next to the pipelined ms_per_step above
             if dump and rank == 0:  # the last TIMED frame (the latency frame below would be one frame further on)
-                import numpy as np
-
-                np.save(dump, fgs[(step_no[0] - 1) % len(fgs)].frame.cpu().numpy().reshape(HEIGHT, WIDTH, 14))
+                save_frame(args, fgs[(step_no[0] - 1) % len(fgs)].frame.cpu().numpy().reshape(HEIGHT, WIDTH, 14))
             lat = 0.0
             if world > 1:
                 sync()
@@ -487,7 +517,7 @@ def main():
             return rend, tmax[0].item(), tmax[1].item()
 
         single_frame = [0.0]
-        renderer, elapsed, kernel_s = measure(rng_mode, fast_math=args.fast, dump=args.dump)
+        renderer, elapsed, kernel_s = measure(rng_mode, fast_math=args.fast, dump=bool(args.dump or args.dump_outputs))
         latency = {"frame_latency_ms": round(single_frame[0] * 1e3, 3),
                    "exchange_exposed_ms": round(max(single_frame[0] - kernel_s, 0.0) * 1e3, 3)} if world > 1 else None
         ki = renderer.kernel_info(len(spheres))

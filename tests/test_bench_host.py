@@ -26,3 +26,30 @@ def test_cpu_baseline_of_a_frame_smaller_than_the_budget(pt, oracle):
     assert "rows 0..63 of the 64x64 frame" in out["sample"] and "rendered" in out["sample"]
     spheres4, label4 = bench.scene_of(pt, bench.CONFIGS["cfg4open"])
     assert len(spheres4) == 1000 and "without walls" in label4
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path):
+    """--dump-outputs: a frame that fits in 64 MB is written whole; a larger one as the same seeded pixel sample in every run."""
+    import os
+
+    import numpy as np
+
+    import bench
+
+    small = np.arange(8 * 8 * 14, dtype=np.float32).reshape(8, 8, 14)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert os.listdir(tmp_path / "small") == ["frame.npy"]
+    got = np.load(tmp_path / "small" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+
+    h, w = 2048, 1024  # 2^21 pixels x 14 floats = 117 MB, over the limit
+    big = np.random.default_rng(5).random((h, w, 14), dtype=np.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+        assert sorted(os.listdir(tmp_path / run)) == ["frame_sample.npy", "frame_sample_index.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= bench.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "a" / "frame_sample_index.npy")
+    val = np.load(tmp_path / "a" / "frame_sample.npy")
+    assert idx.dtype == np.float64 and val.dtype == np.float32 and val.shape == (bench.DUMP_SAMPLE_PIXELS, 14)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_sample_index.npy"))
+    assert np.array_equal(val, big.reshape(h * w, 14)[idx.astype(np.int64)])

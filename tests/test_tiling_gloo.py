@@ -23,6 +23,19 @@ def _free_port():
     return p
 
 
+def _gpu_device_files():
+    """GPU device files (/dev/kfd, /dev/dri/*) this process holds open."""
+    held = []
+    for fd in os.listdir("/proc/self/fd"):
+        try:
+            target = os.readlink(f"/proc/self/fd/{fd}")
+        except OSError:
+            continue
+        if target.startswith(("/dev/kfd", "/dev/dri/")):
+            held.append(target)
+    return held
+
+
 def _worker(rank, world, port, size, spp, rng, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
@@ -40,7 +53,9 @@ def _worker(rank, world, port, size, spp, rng, q):
         tile = oracle.render(size, size, spp, rng_mode=rng, row_begin=b, row_end=e, threads=2)
         fg.tile.copy_(torch.from_numpy(tile.reshape(-1)))
         fg.wait_all(fg.gather())
-        dist.barrier()
+        # gloo's own barrier: dist.barrier() asks torch for an accelerator first, which opens the GPU in every worker
+        dist.monitored_barrier()
+        assert not _gpu_device_files(), "a rank of this CPU test opened the GPU"
         if rank == 0:
             q.put(fg.frame.numpy().reshape(size, size, 14).copy())
     finally:
