@@ -130,6 +130,12 @@ ABI = {
     "pt_camera_basis": (ctypes.c_int, [_fp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, _fp]),
     "pt_camera_basis_up": (ctypes.c_int, [_fp, ctypes.c_float, ctypes.c_float, _fp, ctypes.c_int, ctypes.c_int, _fp]),
     "pt_display_pack": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "pt_denoiser_weights_check": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),
+    "pt_denoiser_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "pt_denoiser_create_from_file": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "pt_denoiser_destroy": (ctypes.c_int, [_vp]),
+    "pt_denoiser_enqueue": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "pt_denoiser_denoise": (ctypes.c_int, [_vp, _vp, _vp, _fp]),
 }
 # include/ptcore_lab.h: only libptcore_lab.so exports these
 LAB_ABI = {
@@ -144,6 +150,13 @@ LAB_ABI = {
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "pt_debug_policy_ms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pt_debug_policy_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "pt_debug_denoiser_layer_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                    ctypes.c_char_p, ctypes.c_size_t]),
+    "pt_debug_denoiser_activation": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t]),
+    "pt_debug_denoiser_set_activation": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t]),
+    "pt_debug_denoiser_conv_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                   ctypes.c_char_p, ctypes.c_size_t]),
+    "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
 }
 
 FN_INV_SQRT_LITERAL, FN_INV_SQRT_FAST, FN_SQRT_LITERAL, FN_SQRT_FAST, FN_SIN, FN_COS, FN_UNIFORM = range(7)
@@ -563,3 +576,109 @@ def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, 
         d_scene.free()
         r.destroy()
     return img, ms
+
+
+def denoiser_weights_bytes(weights):
+    """PTDN bytes from a path, bytes or a reference-keyed state_dict (denoise_weights.py)."""
+    if isinstance(weights, (bytes, bytearray, memoryview)):
+        return bytes(weights)
+    if isinstance(weights, (str, os.PathLike)):
+        with open(weights, "rb") as f:
+            return f.read()
+    from . import denoise_weights
+
+    return denoise_weights.to_bytes(weights)
+
+
+def denoiser_weights_check(weights):
+    """Host-only validation of a weight file / bytes / state_dict (pt_denoiser_weights_check); raises PtError naming the key."""
+    blob = denoiser_weights_bytes(weights)
+    check(lib.pt_denoiser_weights_check(blob, len(blob)))
+
+
+class Denoiser:
+    """ctypes view of pt_denoiser: the reference's DenoiseCNN step (train.py:test, main.cu:146-152) for width x height frames.
+    weights: a PTDN file path, its bytes, or a reference-keyed state_dict."""
+
+    def __init__(self, width, height, weights):
+        blob = denoiser_weights_bytes(weights)
+        h = _vp()
+        check(lib.pt_denoiser_create(width, height, blob, len(blob), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height = width, height
+
+    def enqueue(self, d_frame, d_rgb=None, stream=None):
+        """Asynchronous; d_rgb None = in place on the [H][W][14] frame, else [H][W][3] into d_rgb (frame untouched)."""
+        check(lib.pt_denoiser_enqueue(self.handle, d_frame, d_rgb, stream))
+
+    def denoise(self, d_frame, d_rgb=None):
+        """Synchronous; returns device-event milliseconds."""
+        ms = ctypes.c_float(0)
+        check(lib.pt_denoiser_denoise(self.handle, d_frame, d_rgb, ctypes.byref(ms)))
+        return ms.value
+
+    # lab library only (pt_debug_denoiser_*)
+    def layers(self):
+        """[(name, (rows, cols, channels))] of every activation buffer of the workspace."""
+        n, shape, name = ctypes.c_int(0), (ctypes.c_int * 3)(), ctypes.create_string_buffer(64)
+        check(lib.pt_debug_denoiser_layer_info(self.handle, 0, ctypes.byref(n), shape, name, 64))
+        out = []
+        for i in range(n.value):
+            check(lib.pt_debug_denoiser_layer_info(self.handle, i, None, shape, name, 64))
+            out.append((name.value.decode(), tuple(shape)))
+        return out
+
+    def activation(self, layer):
+        shape = self.layers()[layer][1]
+        out = np.empty(shape, dtype=np.float32)
+        check(lib.pt_debug_denoiser_activation(self.handle, layer, out.ctypes.data, out.size))
+        return out
+
+    def set_activation(self, layer, arr):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        check(lib.pt_debug_denoiser_set_activation(self.handle, layer, arr.ctypes.data, arr.size))
+
+    def convs(self):
+        """[(name, info dict)] of every convolution in execution order (pt_debug_denoiser_conv_info)."""
+        n, info, name = ctypes.c_int(0), (ctypes.c_int * 12)(), ctypes.create_string_buffer(64)
+        check(lib.pt_debug_denoiser_conv_info(self.handle, 0, ctypes.byref(n), info, name, 64))
+        keys = ("in", "out0", "out1", "res", "up", "ks", "stride", "N", "epi", "splits", "bm", "bn")
+        out = []
+        for i in range(n.value):
+            check(lib.pt_debug_denoiser_conv_info(self.handle, i, None, info, name, 64))
+            out.append((name.value.decode(), dict(zip(keys, list(info)))))
+        return out
+
+    def run_conv(self, conv, d_rgb=None):
+        check(lib.pt_debug_denoiser_run_conv(self.handle, conv, d_rgb))
+
+    def destroy(self):
+        if self.handle:
+            check(lib.pt_denoiser_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def denoise_frame(frame, weights, out_of_place=False, denoiser=None):
+    """Convenience for tests: upload a host [H][W][14] frame, denoise it on the GPU, download.  Returns the frame after the
+    in-place step, or (frame untouched, rgb [H][W][3]) with out_of_place=True."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    h, w = frame.shape[:2]
+    dn = denoiser or Denoiser(w, h, weights)
+    d_frame = DeviceBuffer(frame.nbytes).upload(frame)
+    d_rgb = DeviceBuffer(h * w * 12) if out_of_place else None
+    try:
+        dn.denoise(d_frame.ptr, d_rgb.ptr if d_rgb else None)
+        f = d_frame.download(np.float32, frame.shape)
+        return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
+    finally:
+        d_frame.free()
+        if d_rgb:
+            d_rgb.free()
+        if denoiser is None:
+            dn.destroy()

@@ -1,0 +1,810 @@
+// pt_denoise.hip -- the reference's denoising network (DenoiseCNN, denoise_cnn/model.py, run by train.py:test() from the
+// interactive loop, src/main.cu:92-122,146-152) as fp32 MFMA inference behind pt_denoiser_* (include/ptcore.h).
+// Design and numbers: DENOISER.md.  Kernels: the two pre-processing kernels (channel maxima, then the divisions and the
+// channel-padded NHWC copy), ONE implicit-GEMM convolution template (compile-time tile shape, run-time epilogue kind) and the
+// deterministic split-K reduction that applies the same epilogue.  Host side: the PTDN weight loader, the layer table and the
+// workspace, all fixed at create time for the denoiser's width and height.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "pt_internal.h"
+#if PT_BUILD_EXPERIMENTS
+#include "../../include/ptcore_lab.h"
+#endif
+
+#pragma clang fp contract(off)
+
+namespace ptdn {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+enum { EPI_ACT = 0, EPI_LAT = 1, EPI_RGB = 2 };
+constexpr int BK = 16;              // K per staged chunk (every stored Cin is a multiple of 16: one chunk never straddles a tap)
+constexpr int XC = 16;              // channels of the padded input copy (14 + 2 zeros)
+constexpr int PRE_BLOCKS = 256;     // partial maxima of the pre-processing reduction
+constexpr float KEPS = 0.00316f;    // train.py:48-55, model.py forward
+
+struct ConvArgs {
+  const float* in;  // NHWC [in_h][in_w][cin]
+  int in_h, in_w, cin;
+  const float* wt;  // [K][npad], row k = (ky * ks + kx) * cin + c
+  int npad, ks, stride;
+  int out_w, M, N;
+  int nchunks, chunks_per_split;
+  float* partial;  // split-K: [splits][M][npad], else null
+  int epi;
+  const float* bias;  // [npad]
+  const float* scale; // [npad] folded batch-norm (1 / 0 where there is none)
+  const float* shift;
+  float* out0;        // columns [0, nsplit): out0[m * ld0 + n]
+  int ld0, nsplit;
+  float* out1;        // columns [nsplit, N): out1[m * ld1 + n - nsplit]
+  int ld1;
+  const float* res;   // EPI_ACT: residual added after the affine, [M][ld0]
+  const float* up;    // EPI_LAT: the coarser map [up_h][up_w][32], bilinearly upsampled (align_corners) and added
+  int up_h, up_w, out_h;
+  const float* x0;    // EPI_RGB: the pre-processed input (albedo = channels 6-8)
+};
+
+// ReLU that returns +0 for every non-positive input (torch: x <= 0 -> 0)
+__device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
+
+// F.upsample(mode='bilinear') of torch 0.2/0.3: align-corners semantics, source coordinate oy (in - 1) / (out - 1).  The
+// coordinate is formed EXACTLY (integer quotient and remainder; weight = remainder / (out - 1), one rounding) rather than as
+// torch's float32 scale * index, whose rounding moves a sample by up to an ulp of the coordinate (DENOISER.md); the
+// interpolation itself is THNN's: h0 (w0 x00 + w1 x01) + h1 (w0 x10 + w1 x11).
+__device__ __forceinline__ float upsample(const ConvArgs& a, int m, int n) {
+  const int oy = m / a.out_w, ox = m - oy * a.out_w;
+  int h1 = 0, w1 = 0;
+  float h1l = 0.0f, w1l = 0.0f;
+  if (a.out_h > 1) {
+    const int q = oy * (a.up_h - 1);
+    h1 = q / (a.out_h - 1);
+    h1l = (float)(q - h1 * (a.out_h - 1)) / (float)(a.out_h - 1);
+  }
+  if (a.out_w > 1) {
+    const int q = ox * (a.up_w - 1);
+    w1 = q / (a.out_w - 1);
+    w1l = (float)(q - w1 * (a.out_w - 1)) / (float)(a.out_w - 1);
+  }
+  const int hp = h1 < a.up_h - 1 ? 1 : 0, wp = w1 < a.up_w - 1 ? 1 : 0;
+  const float h0l = 1.0f - h1l, w0l = 1.0f - w1l;
+  const float* p = a.up + ((size_t)h1 * a.up_w + w1) * 32 + n;
+  const size_t dy = (size_t)hp * a.up_w * 32, dx = (size_t)wp * 32;
+  return h0l * (w0l * p[0] + w1l * p[dx]) + h1l * (w0l * p[dy] + w1l * p[dy + dx]);
+}
+
+// The fused epilogue of every layer (m < M, n < N).
+__device__ __forceinline__ void epilogue(const ConvArgs& a, int m, int n, float acc) {
+  if (a.epi == EPI_ACT) {  // conv, ReLU, folded BN (ResBlock: model.py:20-30), + residual (conv2)
+    float v = __builtin_fmaf(relu(acc + a.bias[n]), a.scale[n], a.shift[n]);
+    if (n < a.nsplit) {
+      const size_t o = (size_t)m * a.ld0 + n;
+      if (a.res) v = v + a.res[o];
+      a.out0[o] = v;
+    } else {
+      a.out1[(size_t)m * a.ld1 + (n - a.nsplit)] = v;
+    }
+  } else if (a.epi == EPI_LAT) {  // upsample(rep) + ReLU(lat_k(raw_k)), model.py:72-74
+    const float v = relu(acc + a.bias[n]);
+    a.out0[(size_t)m * a.ld0 + n] = upsample(a, m, n) + v;
+  } else {  // rgb head: clamp(rgb_conv(rep) * (0.00316 + albedo), 0, 1), model.py:101-103
+    float v = acc + a.bias[n];
+    v = v * (KEPS + a.x0[(size_t)m * XC + 6 + n]);
+    a.out0[(size_t)m * a.ld0 + n] = fminf(fmaxf(v, 0.0f), 1.0f);
+  }
+}
+
+// Implicit-GEMM convolution: rows = output pixels, columns = output channels, K = taps x Cin.  4 waves; wave (wm, wn) owns
+// TM x TN tiles of 32 x 32 computed with v_mfma_f32_32x32x2_f32.  Inside a 16-wide K chunk, MFMA step kk takes k = kk from lane
+// half 0 and k = 8 + kk from lane half 1, so a lane's A operands for the whole chunk are 8 CONSECUTIVE channels of its pixel --
+// two float4 loads straight from the NHWC activation, no LDS (no other wave reads those rows).  The B chunk (weights) is
+// shared by the 4 waves and double-buffered in LDS.  blockIdx.z = split-K slice (partials to a.partial, summed in order by
+// splitk_reduce_kernel: deterministic, no atomics).
+template <int TM, int TN, int WM, int WN>
+__global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
+  static_assert(WM * WN == 4, "four waves");
+  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, LDB = BN + 4;
+  constexpr int BF4 = BK * BN / 4, BPT = (BF4 + 255) / 256;
+  __shared__ float4 Bs4[2][BK * LDB / 4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave - (wave / WN) * WN;
+  const int h = lane >> 5, r = lane & 31;
+  const int m0 = blockIdx.x * BM + wm * 32 * TM;
+  const int nb = blockIdx.y * BN, nw = wn * 32 * TN;
+  const int split = blockIdx.z;
+  const int c_begin = split * a.chunks_per_split;
+  const int c_end = min(a.nchunks, c_begin + a.chunks_per_split);
+  const int pad = a.ks >> 1;
+
+  int iy0[TM], ix0[TM];
+  bool mv[TM];
+#pragma unroll
+  for (int i = 0; i < TM; i++) {
+    const int m = m0 + i * 32 + r;
+    mv[i] = m < a.M;
+    const int mm = mv[i] ? m : 0;
+    const int oy = mm / a.out_w, ox = mm - oy * a.out_w;
+    iy0[i] = oy * a.stride - pad;
+    ix0[i] = ox * a.stride - pad;
+  }
+  // A chunk c of this lane: 8 consecutive channels of its pixel per 32-row tile (zeros outside the image = padding)
+#define PTDN_LOAD_A(c, ra)                                                                                        \
+  do {                                                                                                            \
+    const int k0_ = (c) * BK;                                                                                     \
+    const int t_ = k0_ / a.cin, ch_ = k0_ - t_ * a.cin + h * 8;                                                   \
+    const int ky_ = t_ / a.ks, kx_ = t_ - ky_ * a.ks;                                                             \
+    _Pragma("unroll") for (int i = 0; i < TM; i++) {                                                              \
+      const int iy = iy0[i] + ky_, ix = ix0[i] + kx_;                                                             \
+      float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;                                                   \
+      if (mv[i] && (unsigned)iy < (unsigned)a.in_h && (unsigned)ix < (unsigned)a.in_w) {                          \
+        const float4* p_ = reinterpret_cast<const float4*>(a.in + ((size_t)iy * a.in_w + ix) * a.cin + ch_);      \
+        v0 = p_[0];                                                                                               \
+        v1 = p_[1];                                                                                               \
+      }                                                                                                           \
+      ra[i][0] = v0.x, ra[i][1] = v0.y, ra[i][2] = v0.z, ra[i][3] = v0.w;                                         \
+      ra[i][4] = v1.x, ra[i][5] = v1.y, ra[i][6] = v1.z, ra[i][7] = v1.w;                                         \
+    }                                                                                                             \
+  } while (0)
+  // B chunk c (BK x BN weights of this block's columns): float4 number tid (and tid + 256) of the chunk per thread
+  static_assert(BPT <= 2, "at most two float4 of B per thread");
+#define PTDN_B_ADDR(c, f) (a.wt + (size_t)((c) * BK + (f) / (BN / 4)) * a.npad + nb + ((f) % (BN / 4)) * 4)
+#define PTDN_LOAD_B(c, rb0, rb1)                                                                                  \
+  do {                                                                                                            \
+    if (tid < BF4) rb0 = *reinterpret_cast<const float4*>(PTDN_B_ADDR(c, tid));                                   \
+    if (BPT > 1 && tid + 256 < BF4) rb1 = *reinterpret_cast<const float4*>(PTDN_B_ADDR(c, tid + 256));            \
+  } while (0)
+#define PTDN_STORE_B(buf, rb0, rb1)                                                                               \
+  do {                                                                                                            \
+    if (tid < BF4) Bs4[buf][(tid / (BN / 4)) * (LDB / 4) + tid % (BN / 4)] = rb0;                                 \
+    if (BPT > 1 && tid + 256 < BF4) Bs4[buf][((tid + 256) / (BN / 4)) * (LDB / 4) + (tid + 256) % (BN / 4)] = rb1; \
+  } while (0)
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[i][j][e] = 0.0f;
+
+  if (c_begin < c_end) {
+    float ra[TM][8];
+    float4 rb0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb1 = rb0;
+    PTDN_LOAD_A(c_begin, ra);
+    PTDN_LOAD_B(c_begin, rb0, rb1);
+    PTDN_STORE_B(0, rb0, rb1);
+    __syncthreads();
+    for (int c = c_begin; c < c_end; c++) {
+      const int buf = (c - c_begin) & 1;
+      const bool more = c + 1 < c_end;
+      float na[TM][8];
+      if (more) {
+        PTDN_LOAD_A(c + 1, na);
+        PTDN_LOAD_B(c + 1, rb0, rb1);
+      }
+      const float* bs = reinterpret_cast<const float*>(Bs4[buf]) + h * 8 * LDB + nw + r;
+#pragma unroll
+      for (int kk = 0; kk < 8; kk++) {
+        float bv[TN];
+#pragma unroll
+        for (int j = 0; j < TN; j++) bv[j] = bs[kk * LDB + j * 32];
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+          for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[i][kk], bv[j], acc[i][j], 0, 0, 0);
+      }
+      if (more) {
+        PTDN_STORE_B(buf ^ 1, rb0, rb1);
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+          for (int e = 0; e < 8; e++) ra[i][e] = na[i][e];
+      }
+      __syncthreads();
+    }
+  }
+#undef PTDN_LOAD_A
+#undef PTDN_LOAD_B
+#undef PTDN_STORE_B
+#undef PTDN_B_ADDR
+
+  // C/D map of the 32x32 f32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++) {
+      const int n = nb + nw + j * 32 + r;
+      if (n >= a.N) continue;
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int m = m0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (m >= a.M) continue;
+        if (a.partial)
+          a.partial[((size_t)split * a.M + m) * a.npad + n] = acc[i][j][e];
+        else
+          epilogue(a, m, n, acc[i][j][e]);
+      }
+    }
+}
+
+// Split-K: the slices' partial sums added in slice order (bit-identical from run to run), then the layer's epilogue.
+__global__ void __launch_bounds__(256) splitk_reduce_kernel(ConvArgs a, int splits) {
+  const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= (uint32_t)a.M * (uint32_t)a.N) return;
+  const int m = (int)(idx / (uint32_t)a.N), n = (int)(idx - (uint32_t)m * (uint32_t)a.N);
+  float s = a.partial[(size_t)m * a.npad + n];
+  for (int z = 1; z < splits; z++) s = s + a.partial[((size_t)z * a.M + m) * a.npad + n];
+  epilogue(a, m, n, s);
+}
+
+// Pre-processing 1/2 (train.py:50-54): per-block maxima of channels 9-13 (a max is exact in any order).
+__global__ void __launch_bounds__(256) pre_max_kernel(const float* __restrict__ frame, uint32_t pixels, float* __restrict__ part) {
+  float mx[5];
+#pragma unroll
+  for (int k = 0; k < 5; k++) mx[k] = -INFINITY;
+  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < pixels; p += gridDim.x * 256u)
+#pragma unroll
+    for (int k = 0; k < 5; k++) mx[k] = fmaxf(mx[k], frame[(size_t)p * 14 + 9 + k]);
+#pragma unroll
+  for (int k = 0; k < 5; k++)
+    for (int s = 1; s < 64; s <<= 1) mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], s));
+  __shared__ float wmx[4][5];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < 5; k++) wmx[wave][k] = mx[k];
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const int k = threadIdx.x;
+    part[blockIdx.x * 5 + k] = fmaxf(fmaxf(wmx[0][k], wmx[1][k]), fmaxf(wmx[2][k], wmx[3][k]));
+  }
+}
+
+// Pre-processing 2/2 (train.py:48-55): colour / (0.00316 + albedo); channel k of 9-13 / (float)(0.00316 + (double)max_k) --
+// the divisor of torch 0.2/0.3, whose torch.max(t) returned a Python float.  Writes the 16-channel NHWC copy the network
+// reads (channels 14, 15 = 0) and, in place, the normalised channels 9-13 back into the frame (channels 3-8 are unchanged,
+// 0-2 are overwritten by the rgb head).
+__global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ frame, uint32_t pixels, const float* __restrict__ part,
+                                                       int nparts, float* __restrict__ x0, int inplace) {
+  __shared__ float div[5];
+  if (threadIdx.x < 5) {
+    float m = -INFINITY;
+    for (int b = 0; b < nparts; b++) m = fmaxf(m, part[b * 5 + threadIdx.x]);
+    div[threadIdx.x] = (float)(0.00316 + (double)m);
+  }
+  __syncthreads();
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= pixels) return;
+  float* c = frame + (size_t)p * 14;
+  float v[XC];
+#pragma unroll
+  for (int k = 0; k < 14; k++) v[k] = c[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) v[k] = v[k] / (KEPS + v[6 + k]);
+#pragma unroll
+  for (int k = 0; k < 5; k++) v[9 + k] = v[9 + k] / div[k];
+  v[14] = v[15] = 0.0f;
+  float4* o = reinterpret_cast<float4*>(x0 + (size_t)p * XC);
+#pragma unroll
+  for (int q = 0; q < 4; q++) o[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  if (inplace)
+#pragma unroll
+    for (int k = 0; k < 5; k++) c[9 + k] = v[9 + k];
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+const int kChannels[7] = {14, 32, 64, 128, 256, 512, 1024};
+
+struct Tensor {
+  std::vector<uint32_t> shape;
+  const unsigned char* data;  // little-endian float32, unaligned
+  size_t count;
+};
+
+// name -> shape of every tensor of the network (denoise_weights.expected_shapes() restates it)
+static std::map<std::string, std::vector<uint32_t>> expected_shapes() {
+  std::map<std::string, std::vector<uint32_t>> out;
+  char name[64];
+  for (int b = 1; b <= 6; b++) {
+    const uint32_t cin = kChannels[b - 1], cout = kChannels[b];
+    const char* convs[3] = {"res_conv", "conv1", "conv2"};
+    for (int c = 0; c < 3; c++) {
+      snprintf(name, sizeof(name), "block%d.%s.weight", b, convs[c]);
+      out[name] = {cout, c == 2 ? cout : cin, 3, 3};
+      snprintf(name, sizeof(name), "block%d.%s.bias", b, convs[c]);
+      out[name] = {cout};
+    }
+    const char* bns[3] = {"res_bn", "bn1", "bn2"};
+    const char* ps[4] = {"weight", "bias", "running_mean", "running_var"};
+    for (int n = 0; n < 3; n++)
+      for (int p = 0; p < 4; p++) {
+        snprintf(name, sizeof(name), "block%d.%s.%s", b, bns[n], ps[p]);
+        out[name] = {cout};
+      }
+  }
+  for (int k = 0; k <= 6; k++) {
+    snprintf(name, sizeof(name), "lat_%d.weight", k);
+    out[name] = {32, (uint32_t)kChannels[k], 1, 1};
+    snprintf(name, sizeof(name), "lat_%d.bias", k);
+    out[name] = {32};
+    if (k < 6) {
+      snprintf(name, sizeof(name), "backwards_%d%d.weight", k + 1, k);
+      out[name] = {32, 32, 3, 3};
+      snprintf(name, sizeof(name), "backwards_%d%d.bias", k + 1, k);
+      out[name] = {32};
+    }
+  }
+  out["rgb_conv.weight"] = {3, 32, 3, 3};
+  out["rgb_conv.bias"] = {3};
+  return out;
+}
+
+static std::string shape_str(const std::vector<uint32_t>& s) {
+  std::string o = "(";
+  for (size_t i = 0; i < s.size(); i++) o += (i ? ", " : "") + std::to_string(s[i]);
+  return o + (s.size() == 1 ? ",)" : ")");
+}
+
+// Parses and checks a PTDN image (layout: include/ptcore.h).  Every expected tensor present once with its shape, nothing
+// else, no trailing bytes; the message names the offending key.
+static int parse_weights(const void* blob, size_t bytes, std::map<std::string, Tensor>* out, const char* who) {
+  if (!blob) return pt_fail(PT_EINVAL, "%s: null weight blob", who);
+  const unsigned char* p = static_cast<const unsigned char*>(blob);
+  size_t off = 0;
+  auto u32 = [&](uint32_t* v) {
+    if (bytes - off < 4) return false;
+    memcpy(v, p + off, 4);  // little-endian hosts only (x86-64)
+    off += 4;
+    return true;
+  };
+  uint32_t version = 0, n = 0;
+  if (bytes < 12 || memcmp(p, "PTDN", 4) != 0) return pt_fail(PT_EINVAL, "%s: not a PTDN weight file (bad magic)", who);
+  off = 4;
+  u32(&version);
+  u32(&n);
+  if (version != 1) return pt_fail(PT_EINVAL, "%s: PTDN version %u is not supported (1 is)", who, version);
+  const auto want = expected_shapes();
+  std::map<std::string, Tensor> got;
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t len = 0, nd = 0;
+    if (!u32(&len) || bytes - off < len) return pt_fail(PT_EINVAL, "%s: truncated file (in the name of tensor %u)", who, i);
+    std::string name(reinterpret_cast<const char*>(p + off), len);
+    off += len;
+    if (!u32(&nd) || nd > 8) return pt_fail(PT_EINVAL, "%s: truncated or corrupt header of tensor '%s'", who, name.c_str());
+    Tensor t;
+    t.count = 1;
+    for (uint32_t d = 0; d < nd; d++) {
+      uint32_t v = 0;
+      if (!u32(&v)) return pt_fail(PT_EINVAL, "%s: truncated shape of tensor '%s'", who, name.c_str());
+      t.shape.push_back(v);
+      t.count *= v;
+    }
+    if (t.count > (bytes - off) / 4) return pt_fail(PT_EINVAL, "%s: truncated data of tensor '%s'", who, name.c_str());
+    t.data = p + off;
+    off += t.count * 4;
+    auto w = want.find(name);
+    if (w == want.end()) return pt_fail(PT_EINVAL, "%s: unexpected tensor '%s'", who, name.c_str());
+    if (got.count(name)) return pt_fail(PT_EINVAL, "%s: tensor '%s' appears twice", who, name.c_str());
+    if (t.shape != w->second)
+      return pt_fail(PT_EINVAL, "%s: tensor '%s' has shape %s, expected %s", who, name.c_str(), shape_str(t.shape).c_str(),
+                     shape_str(w->second).c_str());
+    got[name] = t;
+  }
+  if (off != bytes) return pt_fail(PT_EINVAL, "%s: %zu trailing bytes after the last tensor", who, bytes - off);
+  for (const auto& w : want)
+    if (!got.count(w.first)) return pt_fail(PT_EINVAL, "%s: missing tensor '%s'", who, w.first.c_str());
+  if (out) *out = got;
+  return PT_OK;
+}
+
+static float ld_f32(const Tensor& t, size_t i) {
+  float v;
+  memcpy(&v, t.data + 4 * i, 4);
+  return v;
+}
+
+struct Act {
+  std::string name;
+  int h, w, c;
+  size_t off;  // floats into the workspace
+};
+
+struct Conv {
+  std::string name;
+  int in, out0, out1, res, up;  // activation ids (-1: none); out0 = -1: the frame / rgb buffer (rgb head)
+  int cin, ks, stride, N, nsplit, epi;
+  int in_h, in_w, out_h, out_w, M, K;
+  int cfg, npad, splits, chunks_per_split, nchunks;
+  size_t w_off;  // floats into the weight buffer: wt [K][npad], bias, scale, shift [npad] each
+};
+
+struct TileCfg {
+  int bm, bn;
+};
+// conv_kernel<TM, TN, WM, WN> instances: 256x32, 128x64, 128x128 for large layers, 128x32 and 64x64 for small ones (+ split-K)
+static const TileCfg kCfg[5] = {{256, 32}, {128, 64}, {128, 128}, {128, 32}, {64, 64}};
+
+}  // namespace ptdn
+
+using namespace ptdn;
+
+struct pt_denoiser {
+  int width, height, device;
+  std::vector<Act> acts;
+  std::vector<Conv> convs;
+  float* d_w = nullptr;
+  float* d_ws = nullptr;
+  float* d_partial = nullptr;
+  float* d_premax = nullptr;
+  size_t ws_floats = 0, w_floats = 0, partial_floats = 0;
+  int pre_blocks = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+#define PTDN_HIP(call)                                                                           \
+  do {                                                                                           \
+    hipError_t e_ = (call);                                                                      \
+    if (e_ != hipSuccess)                                                                        \
+      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,   \
+                     hipGetErrorString(e_), __FILE__, __LINE__);                                 \
+  } while (0)
+
+static void choose_tiles(Conv& c) {
+  auto tiles = [&](int cfg) {
+    const int bn = kCfg[cfg].bn;
+    return (int64_t)((c.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((c.N + bn - 1) / bn);
+  };
+  if (c.N <= 32) c.cfg = tiles(0) >= 256 ? 0 : 3;
+  else if (c.N <= 64) c.cfg = tiles(1) >= 128 ? 1 : 4;
+  else c.cfg = tiles(2) >= 256 ? 2 : 4;
+  c.npad = (c.N + kCfg[c.cfg].bn - 1) / kCfg[c.cfg].bn * kCfg[c.cfg].bn;
+  c.nchunks = c.K / BK;
+  // split K until about two workgroups per CU are in flight, keeping at least 8 chunks (128 of K) per slice
+  const int64_t t = tiles(c.cfg);
+  int splits = 1;
+  if (t < 256) {
+    splits = (int)((512 + t - 1) / t);
+    const int most = c.nchunks / 8 > 0 ? c.nchunks / 8 : 1;
+    if (splits > most) splits = most;
+  }
+  c.chunks_per_split = (c.nchunks + splits - 1) / splits;
+  c.splits = (c.nchunks + c.chunks_per_split - 1) / c.chunks_per_split;
+}
+
+// Layer table for a width x height frame (H = rows): activations and convolutions in execution order.
+static void build_layers(pt_denoiser* d) {
+  int sh[7], sw[7];
+  sh[0] = d->height;
+  sw[0] = d->width;
+  for (int b = 1; b <= 6; b++) sh[b] = (sh[b - 1] + 1) / 2, sw[b] = (sw[b - 1] + 1) / 2;
+  auto act = [&](const std::string& n, int h, int w, int c) {
+    d->acts.push_back({n, h, w, c, 0});
+    return (int)d->acts.size() - 1;
+  };
+  int raw[7];
+  raw[0] = act("input", sh[0], sw[0], XC);
+  auto conv = [&](const std::string& n, int in, int ks, int stride, int N, int epi, int out0, int nsplit, int out1, int res, int up) {
+    Conv c{};
+    c.name = n;
+    c.in = in, c.out0 = out0, c.out1 = out1, c.res = res, c.up = up;
+    const Act& a = d->acts[in];
+    c.cin = a.c, c.ks = ks, c.stride = stride, c.N = N, c.nsplit = nsplit, c.epi = epi;
+    c.in_h = a.h, c.in_w = a.w;
+    c.out_h = (a.h - 1) / stride + 1, c.out_w = (a.w - 1) / stride + 1;
+    c.M = c.out_h * c.out_w;
+    c.K = ks * ks * c.cin;
+    choose_tiles(c);
+    d->convs.push_back(c);
+  };
+  char n[64];
+  for (int b = 1; b <= 6; b++) {
+    const int C = kChannels[b];
+    snprintf(n, sizeof(n), "block%d.t1", b);
+    const int t1 = act(n, sh[b], sw[b], C);
+    snprintf(n, sizeof(n), "block%d.res", b);
+    const int rs = act(n, sh[b], sw[b], C);
+    snprintf(n, sizeof(n), "block%d.out", b);
+    raw[b] = act(n, sh[b], sw[b], C);
+    snprintf(n, sizeof(n), "block%d.conv1+res_conv", b);
+    conv(n, raw[b - 1], 3, 2, 2 * C, EPI_ACT, t1, C, rs, -1, -1);
+    snprintf(n, sizeof(n), "block%d.conv2", b);
+    conv(n, t1, 3, 1, C, EPI_ACT, raw[b], C, -1, rs, -1);
+  }
+  int rep = act("lat6", sh[6], sw[6], 32);
+  conv("lat_6", raw[6], 1, 1, 32, EPI_ACT, rep, 32, -1, -1, -1);
+  for (int k = 5; k >= 0; k--) {
+    snprintf(n, sizeof(n), "back%d%d", k + 1, k);
+    const int bk = act(n, (d->acts[rep].h + 1) / 2, (d->acts[rep].w + 1) / 2, 32);
+    snprintf(n, sizeof(n), "backwards_%d%d", k + 1, k);
+    conv(n, rep, 3, 2, 32, EPI_ACT, bk, 32, -1, -1, -1);
+    snprintf(n, sizeof(n), "rep%d", k);
+    const int nr = act(n, sh[k], sw[k], 32);
+    snprintf(n, sizeof(n), "lat_%d", k);
+    conv(n, raw[k], 1, 1, 32, EPI_LAT, nr, 32, -1, -1, bk);
+    rep = nr;
+  }
+  conv("rgb_conv", rep, 3, 1, 3, EPI_RGB, -1, 3, -1, -1, -1);
+  size_t off = 0;
+  for (Act& a : d->acts) {
+    a.off = off;
+    off += ((size_t)a.h * a.w * a.c + 63) / 64 * 64;  // 256-byte aligned
+  }
+  d->ws_floats = off;
+  size_t woff = 0, pmax = 0;
+  for (Conv& c : d->convs) {
+    c.w_off = woff;
+    woff += ((size_t)c.K * c.npad + 3 * (size_t)c.npad + 63) / 64 * 64;
+    if (c.splits > 1 && (size_t)c.splits * c.M * c.npad > pmax) pmax = (size_t)c.splits * c.M * c.npad;
+  }
+  d->w_floats = woff;
+  d->partial_floats = pmax;
+}
+
+// Host image of the device weight buffer: per conv wt [K][npad] (k = (ky ks + kx) Cin_stored + c), bias, scale, shift.
+// BN folded in float64, rounded once: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale.
+static void fill_weights(const pt_denoiser* d, const std::map<std::string, Tensor>& t, std::vector<float>& w) {
+  w.assign(d->w_floats, 0.0f);
+  for (const Conv& c : d->convs) {
+    float* wt = w.data() + c.w_off;
+    float* bias = wt + (size_t)c.K * c.npad;
+    float* scale = bias + c.npad;
+    float* shift = scale + c.npad;
+    // (torch conv name, BN name or "", first column)
+    std::vector<std::pair<std::string, std::string>> parts;
+    std::string base = c.name;
+    if (base.find("conv1+res_conv") != std::string::npos) {
+      const std::string blk = base.substr(0, base.find('.'));
+      parts = {{blk + ".conv1", blk + ".bn1"}, {blk + ".res_conv", blk + ".res_bn"}};
+    } else if (base.find(".conv2") != std::string::npos) {
+      const std::string blk = base.substr(0, base.find('.'));
+      parts = {{blk + ".conv2", blk + ".bn2"}};
+    } else {
+      parts = {{base, ""}};
+    }
+    int col = 0;
+    for (const auto& pr : parts) {
+      const Tensor& W = t.at(pr.first + ".weight");
+      const Tensor& B = t.at(pr.first + ".bias");
+      const int cout = (int)W.shape[0], cin = (int)W.shape[1], ks = (int)W.shape[2];
+      for (int o = 0; o < cout; o++) {
+        for (int ci = 0; ci < cin; ci++)
+          for (int ky = 0; ky < ks; ky++)
+            for (int kx = 0; kx < ks; kx++) {
+              const size_t k = (size_t)(ky * ks + kx) * c.cin + ci;
+              wt[k * c.npad + col + o] = ld_f32(W, ((size_t)(o * cin + ci) * ks + ky) * ks + kx);
+            }
+        bias[col + o] = ld_f32(B, o);
+        if (pr.second.empty()) {
+          scale[col + o] = 1.0f;
+          shift[col + o] = 0.0f;
+        } else {
+          const double g = ld_f32(t.at(pr.second + ".weight"), o), be = ld_f32(t.at(pr.second + ".bias"), o);
+          const double mu = ld_f32(t.at(pr.second + ".running_mean"), o), var = ld_f32(t.at(pr.second + ".running_var"), o);
+          const double s = g / sqrt(var + 1e-5);
+          scale[col + o] = (float)s;
+          shift[col + o] = (float)(be - mu * s);
+        }
+      }
+      col += cout;
+    }
+  }
+}
+
+static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld) {
+  ConvArgs a{};
+  const Act& in = d->acts[c.in];
+  a.in = d->d_ws + in.off;
+  a.in_h = c.in_h, a.in_w = c.in_w, a.cin = c.cin;
+  a.wt = d->d_w + c.w_off;
+  a.npad = c.npad, a.ks = c.ks, a.stride = c.stride;
+  a.out_w = c.out_w, a.out_h = c.out_h, a.M = c.M, a.N = c.N;
+  a.nchunks = c.nchunks, a.chunks_per_split = c.chunks_per_split;
+  a.partial = c.splits > 1 ? d->d_partial : nullptr;
+  a.epi = c.epi;
+  a.bias = a.wt + (size_t)c.K * c.npad;
+  a.scale = a.bias + c.npad;
+  a.shift = a.scale + c.npad;
+  if (c.out0 >= 0) {
+    a.out0 = d->d_ws + d->acts[c.out0].off;
+    a.ld0 = d->acts[c.out0].c;
+  } else {
+    a.out0 = frame_out;
+    a.ld0 = frame_ld;
+  }
+  a.nsplit = c.nsplit;
+  if (c.out1 >= 0) {
+    a.out1 = d->d_ws + d->acts[c.out1].off;
+    a.ld1 = d->acts[c.out1].c;
+  }
+  if (c.res >= 0) a.res = d->d_ws + d->acts[c.res].off;
+  if (c.up >= 0) {
+    a.up = d->d_ws + d->acts[c.up].off;
+    a.up_h = d->acts[c.up].h, a.up_w = d->acts[c.up].w;
+  }
+  a.x0 = d->d_ws + d->acts[0].off;
+  return a;
+}
+
+static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, hipStream_t s) {
+  const ConvArgs a = conv_args(d, c, frame_out, frame_ld);
+  const dim3 grid((c.M + kCfg[c.cfg].bm - 1) / kCfg[c.cfg].bm, c.npad / kCfg[c.cfg].bn, c.splits);
+  switch (c.cfg) {
+    case 0: hipLaunchKernelGGL((conv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((conv_kernel<1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((conv_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((conv_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((conv_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
+  }
+  PTDN_HIP(hipGetLastError());
+  if (c.splits > 1) {
+    const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
+    PTDN_HIP(hipGetLastError());
+  }
+  return PT_OK;
+}
+
+extern "C" {
+
+int pt_denoiser_weights_check(const void* blob, size_t bytes) {
+  return parse_weights(blob, bytes, nullptr, "pt_denoiser_weights_check");
+}
+
+int pt_denoiser_destroy(pt_denoiser* d) {
+  if (!d) return PT_OK;
+  if (d->d_w) (void)hipFree(d->d_w);
+  if (d->d_ws) (void)hipFree(d->d_ws);
+  if (d->d_partial) (void)hipFree(d->d_partial);
+  if (d->d_premax) (void)hipFree(d->d_premax);
+  if (d->ev0) (void)hipEventDestroy(d->ev0);
+  if (d->ev1) (void)hipEventDestroy(d->ev1);
+  delete d;
+  return PT_OK;
+}
+
+int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt_denoiser** out) {
+  if (!out) return pt_fail(PT_EINVAL, "pt_denoiser_create: null output pointer");
+  *out = nullptr;
+  if (width <= 0 || height <= 0 || (int64_t)width * height > 4096 * 4096)
+    return pt_fail(PT_EINVAL, "pt_denoiser_create: frame size %d x %d outside 1 .. 4096 x 4096 pixels", width, height);
+  std::map<std::string, Tensor> t;
+  int rc = parse_weights(blob, bytes, &t, "pt_denoiser_create");
+  if (rc != PT_OK) return rc;
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
+    return pt_fail(PT_ENODEVICE, "pt_denoiser_create: no HIP device visible (there is no CPU fallback)");
+  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_denoiser_create: hipGetDeviceCount: %s (no usable device)", hipGetErrorString(e));
+  pt_denoiser* d = new (std::nothrow) pt_denoiser();
+  if (!d) return pt_fail(PT_ENOMEM, "pt_denoiser_create: out of host memory");
+  d->width = width, d->height = height;
+  build_layers(d);
+  std::vector<float> w;
+  fill_weights(d, t, w);
+  d->pre_blocks = (int)(((uint64_t)width * height + 255) / 256);
+  if (d->pre_blocks > PRE_BLOCKS) d->pre_blocks = PRE_BLOCKS;
+  e = hipGetDevice(&d->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_w, d->w_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d->d_w, w.data(), d->w_floats * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_ws, d->ws_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_floats * sizeof(float));
+  if (e == hipSuccess && d->partial_floats) e = hipMalloc((void**)&d->d_partial, d->partial_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_premax, PRE_BLOCKS * 5 * sizeof(float));
+  if (e == hipSuccess) e = hipEventCreate(&d->ev0);
+  if (e == hipSuccess) e = hipEventCreate(&d->ev1);
+  if (e != hipSuccess) {
+    rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_denoiser_create: %s", hipGetErrorString(e));
+    pt_denoiser_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return PT_OK;
+}
+
+int pt_denoiser_create_from_file(int width, int height, const char* path, pt_denoiser** out) {
+  if (!path) return pt_fail(PT_EINVAL, "pt_denoiser_create_from_file: null path");
+  FILE* f = fopen(path, "rb");
+  if (!f) return pt_fail(PT_EINVAL, "pt_denoiser_create_from_file: cannot open '%s'", path);
+  std::vector<unsigned char> buf;
+  unsigned char tmp[1 << 16];
+  size_t got;
+  while ((got = fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
+  fclose(f);
+  return pt_denoiser_create(width, height, buf.data(), buf.size(), out);
+}
+
+int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_stream) {
+  if (!d || !d_frame) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue: null denoiser or frame");
+  hipStream_t s = (hipStream_t)hip_stream;
+  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
+  hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks), dim3(256), 0, s, d_frame, pixels, d->d_premax);
+  PTDN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256), dim3(256), 0, s, d_frame, pixels, d->d_premax, d->pre_blocks,
+                     d->d_ws + d->acts[0].off, d_rgb ? 0 : 1);
+  PTDN_HIP(hipGetLastError());
+  for (const Conv& c : d->convs) {
+    const int rc = launch_conv(d, c, d_rgb ? d_rgb : d_frame, d_rgb ? 3 : 14, s);
+    if (rc != PT_OK) return rc;
+  }
+  return PT_OK;
+}
+
+int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_denoise: null denoiser");
+  PTDN_HIP(hipEventRecord(d->ev0, nullptr));
+  const int rc = pt_denoiser_enqueue(d, d_frame, d_rgb, nullptr);
+  if (rc != PT_OK) return rc;
+  PTDN_HIP(hipEventRecord(d->ev1, nullptr));
+  PTDN_HIP(hipEventSynchronize(d->ev1));
+  float ms = 0.0f;
+  PTDN_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+  if (ms_out) *ms_out = ms;
+  return PT_OK;
+}
+
+#if PT_BUILD_EXPERIMENTS
+int pt_debug_denoiser_layer_info(pt_denoiser* d, int layer, int* n_layers, int shape[3], char* name, size_t name_len) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_layer_info: null denoiser");
+  if (n_layers) *n_layers = (int)d->acts.size();
+  if (layer < 0 || layer >= (int)d->acts.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_layer_info: no layer %d", layer);
+  const Act& a = d->acts[layer];
+  if (shape) shape[0] = a.h, shape[1] = a.w, shape[2] = a.c;
+  if (name && name_len) snprintf(name, name_len, "%s", a.name.c_str());
+  return PT_OK;
+}
+
+int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats) {
+  if (!d || !h_out || layer < 0 || layer >= (int)d->acts.size())
+    return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: bad arguments");
+  const Act& a = d->acts[layer];
+  const size_t n = (size_t)a.h * a.w * a.c;
+  if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
+  PTDN_HIP(hipDeviceSynchronize());
+  PTDN_HIP(hipMemcpy(h_out, d->d_ws + a.off, n * sizeof(float), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats) {
+  if (!d || !h_in || layer < 0 || layer >= (int)d->acts.size())
+    return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: bad arguments");
+  const Act& a = d->acts[layer];
+  const size_t n = (size_t)a.h * a.w * a.c;
+  if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
+  PTDN_HIP(hipDeviceSynchronize());
+  PTDN_HIP(hipMemcpy(d->d_ws + a.off, h_in, n * sizeof(float), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_info: null denoiser");
+  if (n_convs) *n_convs = (int)d->convs.size();
+  if (conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_info: no conv %d", conv);
+  const Conv& c = d->convs[conv];
+  if (info) {
+    const int v[12] = {c.in, c.out0, c.out1, c.res, c.up, c.ks, c.stride, c.N, c.epi, c.splits, kCfg[c.cfg].bm, kCfg[c.cfg].bn};
+    memcpy(info, v, sizeof(v));
+  }
+  if (name && name_len) snprintf(name, name_len, "%s", c.name.c_str());
+  return PT_OK;
+}
+
+int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
+  if (!d || conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: bad arguments");
+  const Conv& c = d->convs[conv];
+  if (c.out0 < 0 && !d_rgb) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: the rgb head needs an output buffer");
+  const int rc = launch_conv(d, c, d_rgb, 3, nullptr);
+  if (rc != PT_OK) return rc;
+  PTDN_HIP(hipDeviceSynchronize());
+  return PT_OK;
+}
+#endif
+
+}  // extern "C"

@@ -1,8 +1,12 @@
 // pathtrace_main.cpp -- command-line front end equivalent to the single-frame mode of
 // src/main.cu:18-83,179-193, written against the look-alike headers exactly as main.cu is
 // written against the reference's (Scene / Renderer / Camera / OutputBuffer).
-// Same flags, defaults, banner and timing line; -i/-d (OpenGL window, embedded-Python CNN
-// denoiser) are accepted and reported as unsupported: both are out of scope.
+// Same flags, defaults, banner and timing line; -i (OpenGL window) is accepted and reported as
+// unsupported.  -d with --denoise-weights FILE runs the reference's CNN denoiser
+// (DenoiseNet.h, pt_denoiser_*) on the frame in place after every Render() of the headless frame
+// loop, as the interactive loop body does (main.cu:146-152); the saved EXR is the last denoised frame.
+// (In the reference's single-frame mode -d only changes how the buffer is allocated; here the
+// headless loop stands in for the interactive one, so -d denoises.)
 // Additions: --rng, --max-bounces, --spheres N (seeded random scene), --frames N (headless
 // stand-in for the interactive loop main.cu:146-177: N x Render() into the same device buffer),
 // --poses FILE (scripted fly-through: one "x y z yaw pitch" line per frame, the pose-list format of
@@ -15,11 +19,13 @@
 #include <algorithm>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <sstream>
 #include <string>
 #include <vector>
 
 #include "Camera.h"
+#include "DenoiseNet.h"
 #include "Denoiser.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
@@ -34,7 +40,7 @@ static void usage() {
                "  --size arg                    Size of the screen in pixels\n"
                "  -s [ --samples ] arg          Number of samples per pixel\n"
                "  --device arg                  Which device to use for rendering\n"
-               "  -d [ --denoising ]            Use denoising neural network. (unsupported)\n"
+               "  -d [ --denoising ]            Use denoising neural network (needs --denoise-weights)\n"
                "  -i [ --interactive ]          Interactive mode (unsupported; see --frames)\n"
                "  --nobitmap                    Don't output bitmaps for each channel\n"
                "  -o [ --output ] arg           Prefix of output file/path\n"
@@ -51,6 +57,7 @@ static void usage() {
                "  --batch                       with --poses: render the fly-through in batches of 32 frames per launch\n"
                "  --gpus arg                    row-tile the frame over N devices starting at --device (RCCL gather)\n"
                "  --preview arg                 also write the display-packed frame (Denoiser) as a binary PPM\n"
+               "  --denoise-weights arg         with -d: PTDN weight file of the denoising network\n"
             << std::endl;
 }
 
@@ -66,7 +73,7 @@ int main(int argc, const char** argv) {
   std::string outputName = "output/out";
   std::string rng = "xorwow";
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
-  std::string posesFile, previewFile;
+  std::string posesFile, previewFile, denoiseWeights;
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   void* batch_frames = NULL;
 
@@ -102,6 +109,7 @@ int main(int argc, const char** argv) {
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
+    else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
     else {
       std::cerr << "ERROR: unrecognised option '" << a << "'" << std::endl << std::endl;
       usage();
@@ -128,10 +136,29 @@ int main(int argc, const char** argv) {
     std::cout << "Running in interactive mode: " << (denoising ? "denoising is on" : "denoising is off") << std::endl;
   std::cout << "Camera: " << cameraPos[0] << " " << cameraPos[1] << " " << cameraPos[2] << " " << cameraView[0] << " "
             << cameraView[1] << std::endl;
-  if (interactive || denoising) {
-    std::cerr << "ERROR: -i/-d need the OpenGL window / embedded-Python denoiser of the reference, which this build "
-                 "does not include; use --frames N for a headless frame loop" << std::endl;
+  if (interactive) {
+    std::cerr << "ERROR: -i needs the OpenGL window of the reference, which this build does not include; use --frames N "
+                 "for a headless frame loop" << std::endl;
     return 1;
+  }
+  if (denoising && denoiseWeights.empty()) {
+    std::cerr << "ERROR: -d needs the network's weights: --denoise-weights FILE (a PTDN file written by "
+                 "cuda-pathtrace_amd/denoise_weights.py from a state_dict trained with the reference's train.py)" << std::endl;
+    return 1;
+  }
+  if (denoising && batch) {
+    std::cerr << "ERROR: -d cannot be combined with --batch: the denoiser runs after every frame of the loop" << std::endl;
+    return 1;
+  }
+  if (denoising) {  // the weight file is checked before any device is touched (host only)
+    std::ifstream wf(denoiseWeights.c_str(), std::ios::binary);
+    std::vector<char> blob((std::istreambuf_iterator<char>(wf)), std::istreambuf_iterator<char>());
+    if (!wf.good() && !wf.eof()) blob.clear();
+    if (blob.empty() || pt_denoiser_weights_check(blob.data(), blob.size()) != PT_OK) {
+      std::cerr << "ERROR: --denoise-weights " << denoiseWeights << ": "
+                << (blob.empty() ? "cannot read the file" : pt_last_error()) << std::endl;
+      return 1;
+    }
   }
 
   // set device (main.cu:86)
@@ -155,7 +182,14 @@ int main(int argc, const char** argv) {
   } else {
     single = new Renderer(width, height, samplesPerPixel, threadsPerBlock, opts);
   }
-  auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) { return tiled ? tiled->Render(b, s, c) : single->Render(b, s, c); };
+  // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
+  DenoiseNet* net = denoising ? new DenoiseNet(width, height, denoiseWeights) : NULL;
+  float denoiseTime = 0.0f;
+  auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
+    const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
+    if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
+    return ms;
+  };
   Camera camera(glm::vec3(cameraPos[0], cameraPos[1], cameraPos[2]), cameraView[0], cameraView[1]);  // main.cu:128 verbatim
 
   // allocate output buffer (main.cu:131-139)
@@ -216,6 +250,7 @@ int main(int argc, const char** argv) {
     for (int f = 0; f < frames; f++) renderTime = render(d_buffer, scene, camera);
   }
   std::cout << "Render completed in " << renderTime << "ms (" << 1000.0f / renderTime << " fps)" << std::endl;
+  if (net) std::cout << "Denoise completed in " << denoiseTime << "ms" << std::endl;
   if (tiled) {
     std::cout << "Tile kernel times:";
     for (int g = 0; g < gpus; g++) std::cout << " " << tiled->TileKernelMs(g) << "ms";
@@ -252,6 +287,7 @@ int main(int argc, const char** argv) {
   buffer.SaveEXR(outputName + ".exr");
   if (!noBitmap) buffer.SaveBitmaps(outputName);
   buffer.FreeCPU();
+  delete net;
   delete single;
   delete tiled;
   if (batch_frames) (void)pt_free(batch_frames);  // (d_buffer points into it)

@@ -276,6 +276,37 @@ int pt_mgpu_backend(pt_mgpu* m, char* name, size_t name_len);
  * Asynchronous on hip_stream (NULL = default stream). */
 int pt_display_pack(const float* d_buffer, int width, int height, float* d_vertices, void* hip_stream);
 
+/* ---- denoising network ---------------------------------------------------------------- */
+/* The reference's `-d` step (src/main.cu:92-122,146-152): after every Render() the interactive loop runs DenoiseCNN
+ * (denoise_cnn/model.py) on the frame tensor in place through train.py:test() (pre-processing train.py:48-55, eval-mode
+ * forward, modify_tensor main.cu:106 writes the RGB result into channels 0-2).  Here: fp32 MFMA inference in HIP for a
+ * fixed width x height (DENOISER.md).  Result in place: channels 0-2 = clamp(net, 0, 1), 3-8 as rendered, 9-13 normalised
+ * (divided by 0.00316 + the channel's max, that sum formed in double as torch 0.2/0.3's Python-float max did).
+ *
+ * Weights: the reference ships none; a state_dict trained by its train.py (its parameter names, e.g. block1.res_conv.weight,
+ * block1.res_bn.running_var, lat_0.bias, backwards_10.weight, rgb_conv.weight; num_batches_tracked dropped) is written as a
+ * PTDN image by cuda-pathtrace_amd/denoise_weights.py.  Layout, little-endian, no padding or alignment:
+ *   char magic[4] = "PTDN"; uint32 version = 1; uint32 n_tensors;
+ *   n_tensors x { uint32 name_len; char name[name_len] (UTF-8, no NUL); uint32 ndim; uint32 dims[ndim];
+ *                 float32 data[prod(dims)] (row-major, torch's order) }
+ * A file with a missing, unexpected, repeated or wrongly shaped tensor, a truncation or trailing bytes is rejected with
+ * PT_EINVAL and a message naming the key.  Host only; needs no device. */
+typedef struct pt_denoiser pt_denoiser; /* opaque: the network's weights + the activation workspace of one frame size */
+int pt_denoiser_weights_check(const void* blob, size_t bytes);
+/* DenoiseCNN() + load_pretrained (the model train.py loads for main.cu:92-102) for width x height frames (H = rows):
+ * uploads the weights (re-laid out for the GEMMs, batch norm folded) and allocates the workspace on the current device. */
+int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt_denoiser** out);
+int pt_denoiser_create_from_file(int width, int height, const char* path, pt_denoiser** out);
+int pt_denoiser_destroy(pt_denoiser* d);
+/* train.py:test(model, boost_tensor) + modify_tensor (main.cu:106,150-152) on the device frame d_frame ([height][width][14]),
+ * asynchronous on hip_stream (NULL = default stream).  d_rgb == NULL: the reference's in-place semantics.  d_rgb != NULL:
+ * the result goes to d_rgb ([height][width][3]) and d_frame is left byte for byte untouched.  One denoiser's enqueues share
+ * its workspace: do not run two of them concurrently on different streams. */
+int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around the
+ * network, like Renderer::Render (Renderer.h:63-75). */
+int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out);
+
 /* ---- host-side inputs of the path ------------------------------------------------------ */
 /* The 9 spheres Scene() hard-codes, include/Scene.h:26-34 (host array). */
 int pt_scene_cornell(pt_sphere out[9]);

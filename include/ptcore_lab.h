@@ -60,6 +60,20 @@ int pt_debug_policy_ms(int rng_mode, int variant, double waves_per_simd, int spp
 /* the variant the library's own cost-model policy picks (6, 8 or 9) for a tile of `waves_per_simd` one-lane waves per SIMD */
 int pt_debug_policy_choice(int rng_mode, double waves_per_simd, int spp, int bounces, int with9, int chunked, int* variant);
 
+/* Denoiser diagnostics (csrc/pt_denoise.hip).  Layers = the activation buffers of the workspace, in execution order:
+ * 0 "input" (the pre-processed frame, NHWC, 16 channels of which 14-15 are zero), "block<b>.t1" / ".res" / ".out", "lat6",
+ * "back<k+1><k>", "rep<k>".  shape = {rows, cols, channels}; *n_layers = their number (also for an invalid `layer`). */
+int pt_debug_denoiser_layer_info(pt_denoiser* d, int layer, int* n_layers, int shape[3], char* name, size_t name_len);
+/* Synchronises the device and copies layer `layer` ([rows][cols][channels] floats, n_floats of them) to / from the host. */
+int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats);
+int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats);
+/* Convolution `conv` of the forward pass (execution order): info = {input layer, output layer (-1: the frame / rgb
+ * buffer), second output layer, residual layer, upsampled layer, kernel size, stride, columns N, epilogue kind (0 affine,
+ * 1 lateral upsample-add, 2 rgb head), split-K slices, tile rows, tile columns}. */
+int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len);
+/* Runs convolution `conv` alone on the workspace as it stands (synchronous); the rgb head writes [rows][cols][3] to d_rgb. */
+int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,189 @@
+#!/usr/bin/env python3
+"""Times pt_denoiser_enqueue (the reference's DenoiseCNN step, csrc/pt_denoise.hip) with device events around each run on a
+rendered Cornell frame with random weights: warm-up, then the median of --runs runs per size.  In the same process it times
+torch's own fp32 forward of the restated network (tests/denoise_restatement.py; torch/MIOpen, a comparison point only) and
+lists every layer's shape and FLOPs (2 M N K, counted from the shapes; K with the 14 real input channels).
+
+  python3 tools/denoise_time.py [--sizes 512 1024] [--runs 200] [--no-torch] [--out DIR]
+  python3 tools/denoise_time.py --trace DIR/..._kernel_trace.csv --sizes 512 --out DIR
+      per-layer kernel times from a rocprofv3 --kernel-trace run of this tool (dispatches mapped to layers in launch order)
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as ge  # noqa: E402
+
+FLOOR_TFS = 157.3  # fp32 MFMA peak (MI355X_MICROARCH.md): 256 CUs x 4 SIMDs x 64 FLOP/clk x 2.4 GHz
+
+
+def layer_table(lab, w, h, sd):
+    """[(name, M, N, K, flops, splits, tile)] in launch order, from the lab library's conv table."""
+    dn = lab.Denoiser(w, h, sd)
+    try:
+        layers = dn.layers()
+        rows = []
+        for name, inf in dn.convs():
+            ih, iw, cin = layers[inf["in"]][1]
+            cin_real = 14 if inf["in"] == 0 else cin
+            oh, ow = (ih - 1) // inf["stride"] + 1, (iw - 1) // inf["stride"] + 1
+            M, N, K = oh * ow, inf["N"], inf["ks"] ** 2 * cin_real
+            rows.append(dict(name=name, M=M, N=N, K=K, flops=2.0 * M * N * K, splits=inf["splits"],
+                             tile=f'{inf["bm"]}x{inf["bn"]}'))
+        return rows
+    finally:
+        dn.destroy()
+
+
+def time_hip(pt, w, h, sd, runs, warmup):
+    import torch
+
+    frame = pt.render_frame(w, h, 4)[0]
+    d_src = torch.from_numpy(frame).cuda()
+    d_frame = d_src.clone()
+    dn = pt.Denoiser(w, h, sd)
+    s = torch.cuda.current_stream()
+    times = []
+    try:
+        for i in range(warmup + runs):
+            d_frame.copy_(d_src)  # in place is the reference's mode: every run starts from the rendered frame
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            dn.enqueue(d_frame.data_ptr(), None, s.cuda_stream)
+            e1.record(s)
+            e1.synchronize()
+            if i >= warmup:
+                times.append(e0.elapsed_time(e1))
+    finally:
+        torch.cuda.synchronize()
+        dn.destroy()
+    return np.array(times)
+
+
+def time_torch(w, h, sd, runs, warmup):
+    import torch
+
+    import denoise_restatement as R
+
+    pt = ge.load_package()
+    frame = pt.render_frame(w, h, 4)[0]
+    x = R.to_nchw(R.preprocess(frame), torch.float32).cuda()
+    sdt = {k: torch.from_numpy(v).cuda() for k, v in sd.items()}
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    times = []
+    with torch.no_grad():
+        for i in range(warmup + runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            R.forward(x, sdt)
+            e1.record()
+            e1.synchronize()
+            if i >= warmup:
+                times.append(e0.elapsed_time(e1))
+    return np.array(times)
+
+
+def from_trace(path, rows):
+    """Median kernel time of each layer from a rocprofv3 kernel trace: per frame the two pre-processing kernels, then per
+    layer its conv kernel (+ the split-K reduction)."""
+    with open(path) as f:
+        recs = list(csv.DictReader(f))
+    key_name = next(k for k in recs[0] if k.lower() in ("kernel_name", "kernelname"))
+    key_s = next(k for k in recs[0] if k.lower() in ("start_timestamp", "begin_ns", "start"))
+    key_e = next(k for k in recs[0] if k.lower() in ("end_timestamp", "end_ns", "end"))
+    recs = [r for r in recs if "ptdn" in r[key_name]]
+    recs.sort(key=lambda r: int(r[key_s]))
+    per_frame = 2 + sum(1 + (r["splits"] > 1) for r in rows)
+    frames = len(recs) // per_frame
+    out = {"pre_max + pre_apply": []}
+    for r in rows:
+        out[r["name"]] = []
+    for f in range(frames):
+        seq = recs[f * per_frame:(f + 1) * per_frame]
+        assert "pre_max" in seq[0][key_name], seq[0][key_name]
+        dur = lambda q: (int(q[key_e]) - int(q[key_s])) * 1e-6  # ns -> ms
+        out["pre_max + pre_apply"].append(dur(seq[0]) + dur(seq[1]))
+        i = 2
+        for r in rows:
+            t = dur(seq[i])
+            i += 1
+            if r["splits"] > 1:
+                assert "splitk" in seq[i][key_name]
+                t += dur(seq[i])
+                i += 1
+            out[r["name"]].append(t)
+    return frames, {k: float(np.median(v)) for k, v in out.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
+    ap.add_argument("--runs", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--trace", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not a.trace:
+        import torch
+
+        torch.cuda.set_device(0)  # torch's HIP context first (as bench.py does), then the library's
+    pt, lab = ge.load_package(), ge.load_lab()
+    from cuda_pathtrace_amd import denoise_weights as dw
+
+    sd = dw.random_state_dict(seed=1)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+    if a.trace:
+        path = a.trace if os.path.isfile(a.trace) else sorted(glob.glob(os.path.join(a.trace, "**", "*kernel_trace.csv"), recursive=True))[-1]
+        size = a.sizes[0]
+        rows = layer_table(lab, size, size, sd)
+        frames, ms = from_trace(path, rows)
+        lines = [f"per-layer kernel times at {size}x{size}, median over {frames} frames of {os.path.basename(path)}",
+                 f"{'layer':28s} {'M':>7s} {'N':>5s} {'K':>5s} {'GFLOP':>7s} {'tile':>8s} {'split':>5s} {'ms':>8s} {'TF/s':>7s}"]
+        lines.append(f"{'pre_max + pre_apply':28s} {'':>7s} {'':>5s} {'':>5s} {'':>7s} {'':>8s} {'':>5s} {ms['pre_max + pre_apply']:8.4f}")
+        tot_ms, tot_fl = ms["pre_max + pre_apply"], 0.0
+        for r in rows:
+            t = ms[r["name"]]
+            tot_ms, tot_fl = tot_ms + t, tot_fl + r["flops"]
+            lines.append(f"{r['name']:28s} {r['M']:7d} {r['N']:5d} {r['K']:5d} {r['flops'] / 1e9:7.3f} {r['tile']:>8s} {r['splits']:5d} "
+                         f"{t:8.4f} {r['flops'] / t / 1e9:7.2f}")
+        lines.append(f"{'sum of kernels':28s} {'':>7s} {'':>5s} {'':>5s} {tot_fl / 1e9:7.3f} {'':>8s} {'':>5s} {tot_ms:8.4f} "
+                     f"{tot_fl / tot_ms / 1e9:7.2f}")
+        text = "\n".join(lines)
+        print(text)
+        if a.out:
+            open(os.path.join(a.out, f"layers_{size}.txt"), "w").write(text + "\n")
+        return
+    pt.set_device(0)
+    res = {"device": pt.device_info()["name"], "fingerprint": pt.build_fingerprint(), "runs": a.runs, "warmup": a.warmup,
+           "weights": "denoise_weights.random_state_dict(seed=1)", "frame": "Cornell box, 4 spp, default camera", "sizes": {}}
+    for s in a.sizes:
+        rows = layer_table(lab, s, s, sd)
+        flops = sum(r["flops"] for r in rows)
+        t = time_hip(pt, s, s, sd, a.runs, a.warmup)
+        entry = {"gflop": flops / 1e9, "hip_ms": {"median": float(np.median(t)), "min": float(t.min()), "max": float(t.max())},
+                 "hip_tflops": flops / np.median(t) / 1e9, "floor_ms_at_fp32_mfma_peak": flops / (FLOOR_TFS * 1e9)}
+        if not a.no_torch:
+            tt = time_torch(s, s, sd, max(a.runs // 4, 20), 5)
+            entry["torch_fp32_ms"] = {"median": float(np.median(tt)), "min": float(tt.min())}
+        res["sizes"][str(s)] = entry
+        print(f"{s}x{s}: {flops / 1e9:.2f} GFLOP, HIP median {entry['hip_ms']['median']:.4f} ms ({entry['hip_tflops']:.1f} TF/s), "
+              f"floor {entry['floor_ms_at_fp32_mfma_peak']:.4f} ms"
+              + (f", torch fp32 {entry['torch_fp32_ms']['median']:.4f} ms" if "torch_fp32_ms" in entry else ""), flush=True)
+    if a.out:
+        with open(os.path.join(a.out, "denoise_time.json"), "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
