@@ -275,6 +275,61 @@ __device__ __forceinline__ uint32_t screen_sphere_oc(F3 off, float c, int i, F3 
   return key;
 }
 
+// Secondary rays of a nine-sphere scene with a wall block (stage_walls, pt_walls.h): rank the three objects and, per axis, the
+// wall the ray faces (the sign of d[axis] picks it per lane: one per-lane LDS read, index and address by v_bitop3_b32), and
+// CERTIFY the wall behind it instead of screening it.  A certified wall's reference root lies beyond the best of the six keys by
+// more than the ranking's tie margin, so it can neither win nor tie (EXACTNESS.md A.18): with h = dot(d, off) and c of the
+// reference's own floats,
+//   2h + K < 0,  K = T1 (1 + 2^-10)     the far root -b/(2a) ... lies beyond the six keys' winner, and
+//   c + 2^-24 r*r (1 + 2^-8) < 0        the origin is inside the sphere by more than the rounding of b*b: the near root is <= 0,
+// each tested as "finite, negative and non-zero" (v_cmp_class_f32), so NaN and infinities fail.  If any lane of the wave fails
+// (a ray nearly parallel to a wall; an origin outside a wall; a scene without the structure, whose block makes K infinite), the
+// wave screens the three behind walls into the same ranking -- the two smallest of nine distinct keys do not depend on the order
+// they are ranked in, so that is today's ranking.  Everything after the ranking is unchanged.
+__device__ __forceinline__ bool neg_finite(float x) { return __builtin_amdgcn_classf(x, 0x18); }  // -normal or -subnormal
+__device__ __forceinline__ void screen_walled(ScreenState& st, const uint4* W, F3 o, F3 d, const RayConst& rc, uint32_t imask,
+                                              uint32_t lim_hi_bits) {
+  auto umin = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
+  auto umax = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
+  const float4* Wg = reinterpret_cast<const float4*>(W);
+  const uint4 oi = W[3];
+  // per axis: all ones where d[axis] is negative; such a ray faces the wall centred on the plus side (W[4 + k].y, .w), any
+  // other the one on the minus side (.x, .z)
+  auto sel = [](uint32_t dbits) { return (uint32_t)((int32_t)dbits >> 31); };
+  auto faced = [&](int k, uint32_t m) {
+    const uint4 t = W[4 + k];
+    return screen_sphere(lds_read_f4(bitop3<0xE4>(t.y, t.x, m)), (int)bitop3<0xE4>(t.w, t.z, m), o, d, rc, imask, st);
+  };
+  const uint32_t mx = sel(__float_as_uint(d.x)), my = sel(__float_as_uint(d.y)), mz = sel(__float_as_uint(d.z));
+  const uint32_t a0 = screen_sphere(Wg[0], (int)oi.x, o, d, rc, imask, st), a1 = screen_sphere(Wg[1], (int)oi.y, o, d, rc, imask, st),
+                 a2 = screen_sphere(Wg[2], (int)oi.z, o, d, rc, imask, st);
+  const uint32_t l0 = umin(umin(a0, a1), a2), n0 = umed3(a0, a1, a2);
+  const uint32_t b0 = faced(0, mx), b1 = faced(1, my), b2 = faced(2, mz);
+  const uint32_t l1 = umin(umin(b0, b1), b2), n1 = umed3(b0, b1, b2);
+  st.k1 = umin(l0, l1);
+  st.k2 = umin(umin(umax(l0, l1), n0), n1);
+  // the certificates of the three behind walls
+  const float K = __uint_as_float(st.k1 & ~imask) * __uint_as_float(oi.w);
+  auto certified = [&](int k, uint32_t m) {
+    const uint4 t = W[4 + k];
+    const float4 g = lds_read_f4(bitop3<0xE4>(t.x, t.y, m));
+    const F3 off = mk3(o.x - g.x, o.y - g.y, o.z - g.z);  // :73
+    const float h = dot(d, off);                          // b / 2 (:75)
+    const float c = dot(off, off) - g.w;                  // :76
+    return neg_finite(fmaf(2.0f, h, K)) & neg_finite(fmaf(g.w, 5.9837103e-08f, c));
+  };
+  const bool cert = (st.k1 < lim_hi_bits) & certified(0, mx) & certified(1, my) & certified(2, mz);
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!cert) != 0, 0)) {
+    auto behind = [&](int k, uint32_t m) {
+      const uint4 t = W[4 + k];
+      screen_insert(st, screen_sphere(lds_read_f4(bitop3<0xE4>(t.x, t.y, m)), (int)bitop3<0xE4>(t.z, t.w, m), o, d, rc, imask, st));
+    };
+    behind(0, mx);
+    behind(1, my);
+    behind(2, mz);
+  }
+}
+
 // PRIMARY: the ray starts at the eye the scene image was staged for -- off and c come from SceneLds::eyeg
 #ifdef PT_SCREEN_STATS
 __device__ unsigned long long g_screen_stats[8];
@@ -320,6 +375,12 @@ __device__ __forceinline__ bool intersect_scene_screened_keys(const SceneLds& sc
     }
   }
 #if PT_UNROLL_NINE
+  if constexpr (!PRIMARY) {
+    if (sc.walls && n == 9) {  // builds with a wall block (stage_walls): rank six spheres, certify three
+      screen_walled(st, sc.walls, o, d, rc, imask, lim_hi_bits);
+      i = 9;
+    }
+  }
   if (i == 0 && n == 9) {  // the reference's scene size (Scene.h:23): constant LDS offsets and indices, no loop state
     screen_nine(st, [&](int u) { return key_of(sc.geom[u], u); });
     i = 9;

@@ -149,6 +149,9 @@ pixel_kernel(typename KernelArgsOf<FRAMES>::type args) {  // (an XORWOW batch ha
   // variants with a lean build run their LDS build only on scenes up to PT_SCREEN_MAX_SPHERES (launcher): the
   // many-sphere path is not even compiled into it, which keeps the hot loop's code small
   sc.small_only = !LEAN && (VAR == 6 || VAR == 8 || VAR == 10);
+  // the 5-bounce reference-configuration builds of variant 6 screen secondary rays against the faced wall of each axis only
+  // (pt_walls.h; the 8-bounce interactive build keeps the nine-sphere screen: DESIGN.md section 8)
+  if constexpr (VAR == 6 && REFB == 5 && !LEAN) stage_walls(sc, a.spheres, a.n_spheres);
   constexpr bool kRegen = (VAR == 10 || VAR == 11 || VAR == 13);
   GridLds grid;
   if constexpr (VAR == 11 || VAR == 12 || VAR == 13) {  // the frame's grid, built by build_grid_kernel just before this launch
@@ -958,7 +961,7 @@ static inline bool lds_lean(int n, int variant) {
 static inline bool is_split(int variant) { return variant == 8 || variant == 9; }
 static inline size_t scene_lds_f4(int n, int variant) {
   if (lds_lean(n, variant)) return pt::kTablesF4;  // the lean builds read the caller's array directly: only the small tables
-  return (size_t)n * 4 + pt::kTablesF4 + (variant == 3 ? (size_t)((n + 1) / 2) * 2 : 0);  // geometry, two material slots, the eye image, the unit-length table
+  return (size_t)n * 4 + pt::kTablesF4 + (variant == 3 ? (size_t)((n + 1) / 2) * 2 : variant == 6 ? (size_t)pt::kWallF4 : 0);  // geometry, two material slots, the eye image, the unit-length table, the wall block (variant 6)
 }
 // what follows the scene image: one 64 x 14 float transpose slice per wave for the epilogue, or the
 // split kernels' exchange records

@@ -2,6 +2,7 @@
 #pragma once
 #include "pt_device.h"
 #include "pt_kernel.h"
+#include "pt_walls.h"
 
 #pragma clang fp contract(off)
 
@@ -43,6 +44,7 @@ struct SceneLds {
   void* pool;           // variant 13: the workgroup's pool area (pt_grid.h: per wave a test ring and the owners' result slots)
   uint32_t prim_mask;   // wave-uniform: the spheres the bounce-0 screen of this wave has to rank (pt_footprint.h); all ones = every sphere
   uint32_t absmask;     // 0x7FFFFFFF in a VGPR (vgpr_const, pt_device.h): operand of the hot paths' v_bitop3_b32 sign transfers
+  const uint4* walls = nullptr;  // the wall block (stage_walls) of the kernel builds that have one, else null: a compile-time property
 
   // geometry of sphere i, i wave-uniform
   __device__ __forceinline__ float4 geom_uniform(int i) const {
@@ -121,6 +123,38 @@ __device__ __forceinline__ SceneLds stage_scene(const pt_sphere* __restrict__ sp
   }
   __syncthreads();
   return s;
+}
+
+// 32-bit LDS byte address of an LDS object, and a read through one that differs per lane
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
+}
+__device__ __forceinline__ float4 lds_read_f4(uint32_t addr) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v v = *(const __attribute__((address_space(3))) f4v*)(uintptr_t)addr;
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// The wall block of the secondary-bounce screen (pt_walls.h, intersect_scene_screened_keys), kWallF4 float4 slots after the
+// small tables (where variant 3 keeps its pair image):
+//   W[0..2]  geometry {cx, cy, cz, r*r} of the three spheres that are always screened (copies: constant LDS offsets)
+//   W[3]     {their indices, the bits of the certificate's scale: 1 + 2^-10, or +inf when the scene has no walls to certify}
+//   W[4 + k] per axis k: {LDS address of geom[minus wall], of geom[plus wall], minus wall's index, plus wall's index}
+// Classified once per workgroup by one thread from the caller's array; the rest of the workgroup waits at the barrier.
+constexpr int kWallF4 = 7;
+__device__ __forceinline__ void stage_walls(SceneLds& s, const pt_sphere* __restrict__ spheres, int n) {
+  uint4* W = reinterpret_cast<uint4*>(s.pair);
+  if (threadIdx.x == 0) {
+    const WallLayout w = classify_walls(spheres, n);
+    for (int k = 0; k < 3; k++) {
+      const float4 g = s.geom[w.obj[k]];
+      W[k] = make_uint4(__float_as_uint(g.x), __float_as_uint(g.y), __float_as_uint(g.z), __float_as_uint(g.w));
+      W[4 + k] = make_uint4(lds_addr(s.geom + w.minus[k]), lds_addr(s.geom + w.plus[k]), (uint32_t)w.minus[k], (uint32_t)w.plus[k]);
+    }
+    W[3] = make_uint4((uint32_t)w.obj[0], (uint32_t)w.obj[1], (uint32_t)w.obj[2], w.ok ? 0x3F802000u : 0x7F800000u);
+  }
+  __syncthreads();
+  s.walls = W;
 }
 
 // emission and colour of sphere idx (Scene.h:10-11) from whichever copy the layout keeps
