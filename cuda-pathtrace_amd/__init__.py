@@ -136,6 +136,13 @@ ABI = {
     "pt_denoiser_destroy": (ctypes.c_int, [_vp]),
     "pt_denoiser_enqueue": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "pt_denoiser_denoise": (ctypes.c_int, [_vp, _vp, _vp, _fp]),
+    "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "pt_progressive_reset": (ctypes.c_int, [_vp]),
+    "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
+    "pt_progressive_render": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _fp]),
+    "pt_progressive_samples": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "pt_progressive_variant": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "pt_progressive_destroy": (ctypes.c_int, [_vp]),
 }
 # include/ptcore_lab.h: only libptcore_lab.so exports these
 LAB_ABI = {
@@ -157,6 +164,7 @@ LAB_ABI = {
     "pt_debug_denoiser_conv_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                    ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
 }
 
 FN_INV_SQRT_LITERAL, FN_INV_SQRT_FAST, FN_SQRT_LITERAL, FN_SQRT_FAST, FN_SIN, FN_COS, FN_UNIFORM = range(7)
@@ -484,6 +492,59 @@ class Renderer:
     def destroy(self):
         if self.handle:
             check(lib.pt_renderer_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Progressive:
+    """ctypes view of pt_progressive: one still frame of `renderer` refined pass by pass (include/ptcore.h).  After a pass that
+    leaves the session at n >= 2 samples the frame equals the first Render() of a fresh renderer at n spp, bit for bit."""
+
+    def __init__(self, renderer):
+        h = _vp()
+        check(lib.pt_progressive_create(renderer.handle, ctypes.byref(h)))
+        self.handle = h.value
+        self.renderer = renderer  # (the session uses the renderer's scratch: keep it alive)
+
+    def enqueue(self, spp, d_out, d_spheres, n_spheres, basis, eye=DEFAULT_EYE, stream=None):
+        """Asynchronous pass of spp samples; d_out receives the frame of all samples so far."""
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        check(lib.pt_progressive_enqueue(self.handle, spp, d_out, d_spheres, n_spheres, b, e, stream))
+
+    def render(self, spp, d_out, d_spheres, n_spheres, basis, eye=DEFAULT_EYE):
+        """Synchronous pass; returns device-event milliseconds."""
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        ms = ctypes.c_float(0)
+        check(lib.pt_progressive_render(self.handle, spp, d_out, d_spheres, n_spheres, b, e, ctypes.byref(ms)))
+        return ms.value
+
+    def samples(self):
+        n = ctypes.c_int64(0)
+        check(lib.pt_progressive_samples(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def reset(self):
+        check(lib.pt_progressive_reset(self.handle))
+
+    def variant(self, n_spheres):
+        """The kernel variant the next pass on a scene of n_spheres runs (6, 10, 13 or 14)."""
+        v = ctypes.c_int(0)
+        check(lib.pt_progressive_variant(self.handle, n_spheres, ctypes.byref(v)))
+        return v.value
+
+    def set_samples(self, n):  # lab library only (pt_debug_progressive_set_samples)
+        check(lib.pt_debug_progressive_set_samples(self.handle, n))
+
+    def destroy(self):
+        if self.handle:
+            check(lib.pt_progressive_destroy(self.handle))
             self.handle = None
 
     def __del__(self):

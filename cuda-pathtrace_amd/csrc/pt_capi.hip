@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -715,6 +716,192 @@ int pt_renderer_check(pt_renderer* r, int wait, uint32_t* repaired_frames) {
   if (repaired_frames) *repaired_frames = r->repaired;
   return check_device_error(r, wait != 0);
 }
+
+// ---- progressive sessions (include/ptcore.h: the contract; pt_kernel.hip, pixel_kernel RESUME: the passes) ------------------
+// The reference's interactive loop renders a resting camera's frame again and again from fresh samples (main.cu:146-177,
+// pathtrace.cu:212-256); a session adds samples to one frame instead.  Its record holds each pixel's whole state between passes.
+struct pt_progressive {
+  pt_renderer* r;
+  uint32_t* d_rec;            // PT_CHUNK_WORDS words per tile pixel, [word][pixel] (pixel_kernel RESUME), or null for an empty tile
+  int64_t samples;            // samples per pixel so far
+  float cam[15];              // the first pass's basis and eye ...
+  const pt_sphere* spheres;   // ... and scene: later passes must bring the same
+  int n_spheres;
+  hipEvent_t ev_start, ev_stop;
+};
+
+// the automatic policy's choice restricted to the kernels with a resume build: where it would pick 8 or 9, variant 6
+static int session_variant(pt_renderer* r, int n_spheres) {
+  const int v = effective_variant(r, n_spheres);
+  return (v == 8 || v == 9) ? 6 : v;
+}
+
+int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
+  if (!out) return pt_fail(PT_EINVAL, "pt_progressive_create: out is NULL");
+  *out = nullptr;
+  if (!r) return pt_fail(PT_EINVAL, "pt_progressive_create: renderer is NULL");
+  if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants 6, 10, 13, 14)");
+  if (!r->auto_variant && !pt_kernel_has_resume(r->opts.variant))
+    return pt_fail(PT_EINVAL, "pt_progressive_create: kernel variant %d has no progressive passes (resume builds: variants 6, 10, 13, 14)", r->opts.variant);
+  pt_progressive* p = new (std::nothrow) pt_progressive();
+  if (!p) return pt_fail(PT_ENOMEM, "pt_progressive_create: out of host memory");
+  p->r = r;
+  p->d_rec = nullptr;
+  p->samples = 0;
+  memset(p->cam, 0, sizeof(p->cam));
+  p->spheres = nullptr;
+  p->n_spheres = 0;
+  p->ev_start = p->ev_stop = nullptr;
+  hipError_t e = hipSuccess;
+  if (r->tile_pixels) e = hipMalloc((void**)&p->d_rec, (size_t)PT_CHUNK_WORDS * r->tile_pixels * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipEventCreate(&p->ev_start);
+  if (e == hipSuccess) e = hipEventCreate(&p->ev_stop);
+  if (e != hipSuccess) {
+    const int rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_progressive_create: %s", hipGetErrorString(e));
+    pt_progressive_destroy(p);
+    return rc;
+  }
+  *out = p;
+  return PT_OK;
+}
+
+int pt_progressive_destroy(pt_progressive* p) {
+  if (!p) return PT_OK;
+  if (p->d_rec) (void)hipFree(p->d_rec);
+  if (p->ev_start) (void)hipEventDestroy(p->ev_start);
+  if (p->ev_stop) (void)hipEventDestroy(p->ev_stop);
+  delete p;
+  return PT_OK;
+}
+
+int pt_progressive_reset(pt_progressive* p) {
+  if (!p) return pt_fail(PT_EINVAL, "pt_progressive_reset: session is NULL");
+  p->samples = 0;
+  return PT_OK;
+}
+
+int pt_progressive_samples(const pt_progressive* p, int64_t* samples) {
+  if (!p || !samples) return pt_fail(PT_EINVAL, "pt_progressive_samples: NULL argument");
+  *samples = p->samples;
+  return PT_OK;
+}
+
+int pt_progressive_variant(const pt_progressive* p, int n_spheres, int* variant) {
+  if (!p || !variant) return pt_fail(PT_EINVAL, "pt_progressive_variant: NULL argument");
+  *variant = session_variant(p->r, n_spheres);
+  return PT_OK;
+}
+
+// Checks a pass and fills its arguments; *empty = the tile has no pixels (the pass only counts)
+static int progressive_args(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres, const float basis[12],
+                            const float eye[3], ResumeKernelArgs* ra, int* variant) {
+  if (!p) return pt_fail(PT_EINVAL, "pt_progressive: session is NULL");
+  pt_renderer* r = p->r;
+  if (spp < 1) return pt_fail(PT_EINVAL, "pt_progressive: spp %d (a pass adds at least one sample)", spp);
+  if (!d_out && r->tile_pixels) return pt_fail(PT_EINVAL, "pt_progressive: d_out is NULL");
+  if (n_spheres < 0 || (n_spheres > 0 && !d_spheres)) return pt_fail(PT_EINVAL, "pt_progressive: bad scene (%d spheres)", n_spheres);
+  if (!basis || !eye) return pt_fail(PT_EINVAL, "pt_progressive: basis/eye is NULL");
+  if ((int64_t)spp > (int64_t)INT_MAX - p->samples)
+    return pt_fail(PT_EINVAL, "pt_progressive: %lld + %d samples exceed INT_MAX (the reference's counts are int)", (long long)p->samples, spp);
+  if (p->samples > 0 && (memcmp(p->cam, basis, 12 * sizeof(float)) != 0 || memcmp(p->cam + 12, eye, 3 * sizeof(float)) != 0 ||
+                         p->spheres != d_spheres || p->n_spheres != n_spheres))
+    return pt_fail(PT_EINVAL, "pt_progressive: camera or scene differs from the session's first pass: reset the session");
+  const int v = session_variant(r, n_spheres);
+  if (!pt_kernel_has_resume(v)) return pt_fail(PT_EINVAL, "pt_progressive: kernel variant %d has no progressive passes", v);
+  if (n_spheres > pt_kernel_max_spheres(v))
+    return pt_fail(PT_ELIMIT, "pt_progressive: %d spheres exceed the LDS staging limit of %d", n_spheres, pt_kernel_max_spheres(v));
+  *variant = v;
+  PixelKernelArgs& a = ra->base;
+  memset(&a, 0, sizeof(a));
+  a.out = d_out;
+  a.spheres = d_spheres;
+  a.rng_state = nullptr;  // the session's own generator: seeded at sample 0, the record's afterwards
+  memcpy(a.basis, basis, sizeof(a.basis));
+  memcpy(a.eye, eye, sizeof(a.eye));
+  a.n_spheres = n_spheres;
+  a.width = r->width;
+  a.height = r->height;
+  a.row_begin = r->opts.row_begin;
+  a.tile_pixels = r->tile_pixels;
+  a.spp = (int32_t)(p->samples + spp);  // the frame this pass completes
+  a.max_bounces = r->opts.max_bounces;
+  a.frame = 0u;
+  a.planar = r->opts.layout == PT_LAYOUT_PLANAR ? 1u : 0u;
+  a.fail_count = nullptr;
+  a.accel = r->d_accel;
+  a.seed = r->opts.seed;
+  a.err_word = r->d_err;
+  a.chunk_wait_ticks = r->chunk_wait_ticks;
+  a.debug = r->debug;
+  a.vertices = nullptr;  // (display vertices: pt_display_pack on the frame)
+  a.prio = (spp >= 4 && (uint64_t)r->tile_pixels <= 2u * r->resident_pixels) ? 1u : 0u;  // as fill_args, on the pass's own count
+  ra->sample_begin = (int32_t)p->samples;
+  ra->session = p->d_rec;
+  return PT_OK;
+}
+
+// the pass went out: the session now holds its samples (and, after its first pass, its camera and scene)
+static void progressive_advance(pt_progressive* p, int spp, const pt_sphere* d_spheres, int n_spheres, const float basis[12], const float eye[3]) {
+  if (p->samples == 0) {
+    memcpy(p->cam, basis, 12 * sizeof(float));
+    memcpy(p->cam + 12, eye, 3 * sizeof(float));
+    p->spheres = d_spheres;
+    p->n_spheres = n_spheres;
+  }
+  p->samples += spp;
+}
+
+int pt_progressive_enqueue(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres, const float basis[12],
+                           const float eye[3], void* hip_stream) {
+  ResumeKernelArgs ra;
+  int variant = 0;
+  int rc = progressive_args(p, spp, d_out, d_spheres, n_spheres, basis, eye, &ra, &variant);
+  if (rc != PT_OK) return rc;
+  pt_renderer* r = p->r;
+  if (r->tile_pixels) {
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    rc = order_after_last(r, stream);  // (the grid buffer is the renderer's)
+    if (rc != PT_OK) return rc;
+    PT_HIP(pt_launch_resume_kernel(ra, r->opts.rng_mode, variant, stream));
+    rc = mark_last(r, stream);
+    if (rc != PT_OK) return rc;
+  }
+  progressive_advance(p, spp, d_spheres, n_spheres, basis, eye);
+  return PT_OK;
+}
+
+int pt_progressive_render(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres, const float basis[12],
+                          const float eye[3], float* ms_out) {
+  ResumeKernelArgs ra;
+  int variant = 0;
+  if (ms_out) *ms_out = 0.0f;
+  int rc = progressive_args(p, spp, d_out, d_spheres, n_spheres, basis, eye, &ra, &variant);
+  if (rc != PT_OK) return rc;
+  pt_renderer* r = p->r;
+  if (r->tile_pixels) {
+    rc = order_after_last(r, nullptr);
+    if (rc != PT_OK) return rc;
+    PT_HIP(hipEventRecord(p->ev_start, nullptr));
+    PT_HIP(pt_launch_resume_kernel(ra, r->opts.rng_mode, variant, nullptr));
+    PT_HIP(hipEventRecord(p->ev_stop, nullptr));
+    PT_HIP(hipEventSynchronize(p->ev_stop));
+    r->have_last = false;  // the pass has completed: nothing left to order against
+    float ms = 0.0f;
+    PT_HIP(hipEventElapsedTime(&ms, p->ev_start, p->ev_stop));
+    if (ms_out) *ms_out = ms;
+  }
+  progressive_advance(p, spp, d_spheres, n_spheres, basis, eye);
+  return PT_OK;
+}
+
+#if PT_BUILD_EXPERIMENTS
+// lab library: a session's sample count without the samples (the INT_MAX limit's test, include/ptcore_lab.h)
+int pt_debug_progressive_set_samples(pt_progressive* p, int64_t samples) {
+  if (!p || samples < 0) return pt_fail(PT_EINVAL, "pt_debug_progressive_set_samples: bad arguments");
+  p->samples = samples;
+  return PT_OK;
+}
+#endif
 
 #if PT_BUILD_EXPERIMENTS
 // lab library: the variant the C++ policy itself picks for a tile of the reference's scene (tests/test_policy_model.py compares

@@ -159,6 +159,15 @@ struct FramesKernelArgs {
   uint64_t vtx_stride;         // ... of the display vertices (fused display pack)
   float cams[PT_FRAMES_MAX][15];
 };
+// One pass of a progressive session (pt_progressive_*, pt_capi.hip): the single-frame arguments with base.spp = n_end, the
+// session's sample count after the pass, plus where the pass starts and the session's record.  The pass renders samples
+// [sample_begin, n_end) of an n_end-spp frame, writes that frame (fs = n_end) to base.out and the pixel's state to `session`.
+// base.rng_state is null, base.frame 0 and base.chunks 0: a session's generator is its own (seeded), and passes are unchunked.
+struct ResumeKernelArgs {
+  PixelKernelArgs base;
+  int32_t sample_begin;        // samples the session holds before this pass: 0 = start from zero and the seeded generator
+  uint32_t* session;           // PT_CHUNK_WORDS words per tile pixel, [word][pixel] like chunk_state (philox: the first 20)
+};
 // words handed from one chunk of a pixel block to the next: 10 sums, 2 counts (colour; the three first-hit accumulators share
 // one), 4 x {mean, M2}, and the 6 generator words (xorwow only; philox needs none)
 #define PT_CHUNK_WORDS 26
@@ -205,6 +214,10 @@ hipError_t pt_launch_pixel_kernel(const PixelKernelArgs& a, int rng_mode, int va
 // frame batches: is there a kernel for these launch parameters (reference scene, variant 6, interleaved layout), and the launch
 bool pt_kernel_has_frames(int variant, int n_spheres, int max_bounces, bool planar);
 hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, hipStream_t stream);
+// progressive passes: the resume builds of variants 6 (reference configurations included), 10, 13 and 14
+bool pt_kernel_has_resume(int variant);
+const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar);
+hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream);
 hipError_t pt_launch_build_grid(const pt_sphere* spheres, int n, uint32_t* accel, const float* eye /* camera hint or NULL */,
                                 bool pooled /* for variant 13's LDS image (fewer cells at large n) */, hipStream_t stream,
                                 int threads = PT_GRID_BLOCK_THREADS /* workgroup size of the kernel that will stage the grid */);

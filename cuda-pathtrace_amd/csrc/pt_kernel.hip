@@ -96,18 +96,25 @@ __device__ __forceinline__ void chunk_publish(const PixelKernelArgs& a, uint32_t
 //  * the counter-based generator is re-keyed per frame, so its frames are independent: one workgroup per (frame, pixel block),
 //    frame-major -- the next frame's workgroups fill the slots the current one's leave (and the fifth slot per CU a single
 //    1024-workgroup frame cannot use).
-template <bool FRAMES> struct KernelArgsOf { typedef PixelKernelArgs type; };
-template <> struct KernelArgsOf<true> { typedef FramesKernelArgs type; };  // (the cameras travel as kernel arguments too)
-template <bool FRAMES> __device__ __forceinline__ PixelKernelArgs& base_args(typename KernelArgsOf<FRAMES>::type& args) {
-  if constexpr (FRAMES) return args.base; else return args;
+//
+// RESUME (progressive passes, pt_capi.hip): the launch renders samples [sample_begin, spp) of an spp-sample frame.  It starts
+// from the session's record -- the state a chunk hands to the next one, same words, same [word][pixel] layout -- unless
+// sample_begin is 0, and ends by writing BOTH the frame of all spp samples and the record.  Per pixel, a session performs the
+// operations of one spp-sample launch in their order (EXACTNESS.md A.19); the one difference is that a session always jitters.
+template <bool FRAMES, bool RESUME = false> struct KernelArgsOf { typedef PixelKernelArgs type; };
+template <> struct KernelArgsOf<true, false> { typedef FramesKernelArgs type; };  // (the cameras travel as kernel arguments too)
+template <> struct KernelArgsOf<false, true> { typedef ResumeKernelArgs type; };
+template <bool FRAMES, bool RESUME> __device__ __forceinline__ PixelKernelArgs& base_args(typename KernelArgsOf<FRAMES, RESUME>::type& args) {
+  if constexpr (FRAMES || RESUME) return args.base; else return args;
 }
 
 // WIDE (variant 13 only; the launcher's "variant 14"): 1024-thread workgroups, one per CU -- pt_grid.h, grid_max_entries
-template <int RNG, int VAR, bool LEAN = false, int REFB = 0, bool FRAMES = false, bool WIDE = false>
-__global__ void __launch_bounds__((kBlockThreads<VAR, WIDE>), ((FRAMES && RNG == PT_RNG_XORWOW) ? PT_MIN_WAVES : kMinWavesR<VAR, REFB, RNG>)) PT_KERNEL_ATTR
-pixel_kernel(typename KernelArgsOf<FRAMES>::type args) {  // (an XORWOW batch has one workgroup per pixel block for all its frames: the
+// (the 8-bounce XORWOW resume build: at five waves it spills two words its twin does not -- four waves, like the batch build)
+template <int RNG, int VAR, bool LEAN = false, int REFB = 0, bool FRAMES = false, bool WIDE = false, bool RESUME = false>
+__global__ void __launch_bounds__((kBlockThreads<VAR, WIDE>), (((FRAMES || (RESUME && REFB == 8)) && RNG == PT_RNG_XORWOW) ? PT_MIN_WAVES : kMinWavesR<VAR, REFB, RNG>)) PT_KERNEL_ATTR
+pixel_kernel(typename KernelArgsOf<FRAMES, RESUME>::type args) {  // (an XORWOW batch has one workgroup per pixel block for all its frames: the
                                                            // interactive shape fills four of a CU's five slots, so that build takes 128 registers)
-  PixelKernelArgs& a = base_args<FRAMES>(args);
+  PixelKernelArgs& a = base_args<FRAMES, RESUME>(args);
   // a batch of frames, two shapes (head of this section): the counter-based generator's frames are independent -- one workgroup
   // per (frame, pixel block), frame-major; XORWOW's are a chain per pixel -- one workgroup per pixel block, looping over the frames
   constexpr bool FRAME_GRID = FRAMES && RNG == PT_RNG_PHILOX, FRAME_LOOP = FRAMES && !FRAME_GRID;
@@ -133,8 +140,12 @@ pixel_kernel(typename KernelArgsOf<FRAMES>::type args) {  // (an XORWOW batch ha
     load_camera(fr);  // before the scene image is staged for this frame's eye
   }
   constexpr bool REF = REFB != 0;
-  constexpr bool CHUNKS = kChunkable<VAR, REFB> && !FRAMES;
+  constexpr bool CHUNKS = kChunkable<VAR, REFB> && !FRAMES && !RESUME;
   static_assert(!FRAMES || (VAR == 6 && REFB != 0), "frame batches: reference-configuration builds of variant 6");
+  static_assert(!RESUME || (!FRAMES && (VAR == 6 || VAR == 10 || VAR == 13)), "progressive passes: variants 6, 10, 13 (14 = WIDE)");
+  int sample_begin = 0;  // (a pass: the samples the session already holds; a.spp is the session's count after the pass)
+  if constexpr (RESUME) sample_begin = args.sample_begin;
+  const int pass_spp = a.spp - sample_begin;  // the cost heuristics below look at what this launch renders
   if constexpr (REF) {
     a.n_spheres = 9;
     a.max_bounces = REFB;
@@ -223,7 +234,22 @@ frame_top:
 
   Welford var[4] = {{0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}};
   TraceOutput L{mk3(0, 0, 0), mk3(0, 0, 0), mk3(0, 0, 0), 0.0f};
-  int i_begin = 0, i_end = a.spp;
+  int i_begin = sample_begin, i_end = a.spp;
+  if constexpr (RESUME) {
+    if (sample_begin > 0 && active) {  // the session's record (written by the pass before: no other launch touches it)
+      const uint32_t* rec = args.session;
+      auto ld = [&](int w) { return rec[(size_t)w * a.tile_pixels + tp]; };
+      auto ldf = [&](int w) { return __uint_as_float(ld(w)); };
+      L.color = mk3(ldf(0), ldf(1), ldf(2));
+      L.normal = mk3(ldf(3), ldf(4), ldf(5));
+      L.albedo = mk3(ldf(6), ldf(7), ldf(8));
+      L.depth = ldf(9);
+      const int n0 = (int)ld(10), n1 = (int)ld(11);
+#pragma unroll
+      for (int k = 0; k < 4; k++) var[k] = Welford{k == 0 ? n0 : n1, ldf(12 + 2 * k), ldf(13 + 2 * k)};
+      if constexpr (RNG == PT_RNG_XORWOW) rng.st = Xorwow{ld(20), ld(21), ld(22), ld(23), ld(24), ld(25)};
+    }
+  }
   if constexpr (CHUNKS) {
     if (n_chunks > 1u) {
       const int per = (a.spp + (int)n_chunks - 1) / (int)n_chunks;
@@ -249,7 +275,7 @@ frame_top:
 
   auto primary_ray = [&](Rng<RNG>& g, F3& dir) {  // :221-229
     float sx = (float)row, sy = (float)col;
-    if (a.spp != 1) {
+    if (RESUME || a.spp != 1) {  // (a session cannot know its final count: it always jitters)
       float jx, jy;
       g.jitter(jx, jy);
       sx += jx * 1.0f - 0.5f;
@@ -279,7 +305,7 @@ frame_top:
   if constexpr (REF && VAR == 6) {
 #ifndef PT_NO_FOOTPRINT
     // once per pixel: the spheres this pixel's primary rays can return; the wave ranks the union at bounce 0
-    if (a.spp >= PT_FOOTPRINT_MIN_SPP) {
+    if (pass_spp >= PT_FOOTPRINT_MIN_SPP) {
       const uint32_t mine = active ? primary_candidates(sc, a.n_spheres, (float)row, (float)col, dir_at) : 0u;
       uint32_t wave_mask = 0u;
 #pragma unroll
@@ -293,7 +319,7 @@ frame_top:
   bool prim_ok = false;  // variant 13: this pixel's primary rays take their spheres from the pixel's list instead of walking the grid
   if constexpr (VAR == 13 && PT_PRIMLIST) {
     // once per pixel and workgroup: the grid spheres the pixel's primary rays can return (pt_primlist.h)
-    if (grid.valid && a.spp >= PT_PRIMLIST_MIN_SPP && a.max_bounces >= 1) {
+    if (grid.valid && pass_spp >= PT_PRIMLIST_MIN_SPP && a.max_bounces >= 1) {
       int k = 0;
       const uint32_t slot = grid.h.prim_base + (uint32_t)kPrimEntriesPerLane * threadIdx.x;
       prim_ok = build_primary_list(grid, a.spheres, a.n_spheres, eye, (float)row, (float)col, active, dir_at, pool_of_wave(sc.pool).ring,
@@ -302,7 +328,7 @@ frame_top:
       if (prim_ok & (k == 0) & ((grid.h.n_big & 0xFFFFu) == 0u)) {
         for (; i < i_end; i++) {
           if constexpr (RNG == PT_RNG_XORWOW) {  // (philox: begin_sample only positions the counter)
-            if (a.spp != 1) {
+            if (RESUME || a.spp != 1) {
               float jx, jy;
               rng.jitter(jx, jy);  // :223-224
             }
@@ -568,6 +594,27 @@ frame_top:
   if constexpr (FRAME_LOOP) {
     __builtin_amdgcn_wave_barrier();  // (the wave's transpose slice is reused by its next frame)
     if (++fr < fr_count) goto frame_top;
+  }
+  if constexpr (RESUME) {  // the pixel's state after spp samples, for the next pass (the frame above is output only)
+    if (active) {
+      uint32_t* rec = args.session;
+      auto st = [&](int w, uint32_t v) { rec[(size_t)w * a.tile_pixels + tp] = v; };
+      auto stf = [&](int w, float v) { st(w, __float_as_uint(v)); };
+      stf(0, L.color.x); stf(1, L.color.y); stf(2, L.color.z);
+      stf(3, L.normal.x); stf(4, L.normal.y); stf(5, L.normal.z);
+      stf(6, L.albedo.x); stf(7, L.albedo.y); stf(8, L.albedo.z);
+      stf(9, L.depth);
+      st(10, (uint32_t)var[0].n);
+      st(11, (uint32_t)var[1].n);
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        stf(12 + 2 * k, var[k].mean);
+        stf(13 + 2 * k, var[k].M2);
+      }
+      if constexpr (RNG == PT_RNG_XORWOW) {
+        st(20, rng.st.d); st(21, rng.st.v0); st(22, rng.st.v1); st(23, rng.st.v2); st(24, rng.st.v3); st(25, rng.st.v4);
+      }
+    }
   }
 
   if constexpr (RNG == PT_RNG_XORWOW) {
@@ -1182,5 +1229,70 @@ hipError_t pt_launch_setup_random(uint32_t* state, int width, int row_begin, uin
   const unsigned grid = (tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS;
   hipLaunchKernelGGL(pt::setup_random_kernel, dim3(grid), dim3(PT_BLOCK_THREADS), 0, stream, state, width, row_begin,
                      tile_pixels, seed);
+  return hipGetLastError();
+}
+
+// ---- progressive passes (pixel_kernel, RESUME) ------------------------------------------------
+// The resume builds: variant 6 (the two reference configurations, the generic and the lean layout), 10 (both layouts), 13 and
+// its 1024-thread form 14.  Nothing else has one (pt_progressive_create refuses the rest).
+typedef void (*resume_kernel_fn)(ResumeKernelArgs);
+
+static resume_kernel_fn select_resume_kernel(int rng_mode, int variant, bool lean, int ref) {
+  const bool philox = rng_mode == PT_RNG_PHILOX;
+  if (variant == 6 && ref == 5 && !lean)
+    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5, false, false, true>;
+  if (variant == 6 && ref == 8 && !lean)
+    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8, false, false, true>;
+  if (lean) {
+    switch (variant) {
+      case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, true, 0, false, false, true>;
+      case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, true, 0, false, false, true>;
+      case 13: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, false, true>;
+      case 14: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, true, true>;
+      default: return nullptr;
+    }
+  }
+  switch (variant) {
+    case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 0, false, false, true>;
+    case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, false, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, false, 0, false, false, true>;
+    default: return nullptr;
+  }
+}
+
+bool pt_kernel_has_resume(int variant) { return variant == 6 || variant == 10 || variant == 13 || variant == 14; }
+
+const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  return (const void*)select_resume_kernel(rng_mode, variant, lds_lean(n_spheres, variant), ref_config(n_spheres, max_bounces, variant, planar));
+}
+
+// One pass: pt_launch_pixel_kernel without sample chunking (ra.base.chunks and repair are ignored) and with the issue priority
+// decided by the pass's own sample count
+hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream) {
+  const PixelKernelArgs& a = ra.base;
+  if (!pt_kernel_has_resume(variant) || !ra.session || ra.sample_begin < 0 || ra.sample_begin >= a.spp || a.rng_state) return hipErrorInvalidValue;
+  resume_kernel_fn fn = select_resume_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u));
+  if (!fn) return hipErrorInvalidValue;
+  ResumeKernelArgs b = ra;
+  b.base.scene_lds_f4 = (uint32_t)scene_lds_f4(a.n_spheres, variant);
+  b.base.prio = (a.spp - ra.sample_begin >= PT_PRIO_MIN_SPP || a.prio != 0u) ? 1u : 0u;
+  b.base.chunks = 0u;
+  b.base.chunk_state = nullptr;
+  b.base.chunk_flag = nullptr;
+  b.base.repair = 0u;
+  const size_t lds = scene_lds_bytes(a.n_spheres, variant);
+  const size_t lds_budget = variant == 14 ? (size_t)PT_LDS_WIDE_BUDGET_BYTES : (size_t)PT_LDS_BUDGET_BYTES;
+  if (lds > lds_budget) return hipErrorInvalidValue;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget);
+    if (e != hipSuccess) return e;
+  }
+  if (variant == 13 || variant == 14) {  // the grid of this pass's scene and eye (the renderer's scratch)
+    if (!a.accel) return hipErrorInvalidValue;
+    hipError_t e = pt_launch_build_grid(a.spheres, a.n_spheres, const_cast<uint32_t*>(a.accel), a.eye, true, stream, pt_kernel_block_threads(variant));
+    if (e != hipSuccess) return e;
+  }
+  const unsigned block = (unsigned)pt_kernel_block_threads(variant);
+  const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + block - 1) / block);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds, stream, b);
   return hipGetLastError();
 }

@@ -35,6 +35,7 @@ class Renderer {
   Renderer& operator=(const Renderer&) = delete;
 
   ~Renderer() { (void)pt_renderer_destroy(impl); }  // Renderer.h:48-53
+  pt_renderer* Handle() const { return impl; }  // extension: the C ABI object (ProgressiveRenderer.h)
 
   // Renderer.h:55-76: synchronous, returns kernel-only milliseconds.
   float Render(OutputBuffer d_buffer, const Scene& d_scene, const Camera& camera) {

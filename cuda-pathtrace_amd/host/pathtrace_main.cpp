@@ -12,7 +12,10 @@
 // --poses FILE (scripted fly-through: one "x y z yaw pitch" line per frame, the pose-list format of
 // collect_data.py:20-31; generator state carries over from frame to frame like the reference's
 // interactive mode, per-frame times are summarised), --gpus N (the frame row-tiled over devices
-// --device .. --device+N-1 by one process: MultiRenderer / pt_mgpu_*, RCCL gather to the first device).
+// --device .. --device+N-1 by one process: MultiRenderer / pt_mgpu_*, RCCL gather to the first device), --progressive N
+// (the still frame refined in N passes of -s samples each into one buffer: ProgressiveRenderer / pt_progressive_*; the
+// saved frame is bit for bit the one -s N*S writes, the one-pass variant of the interactive loop with the camera at rest).
+#include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,6 +32,7 @@
 #include "Denoiser.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
+#include "ProgressiveRenderer.h"
 #include "Renderer.h"
 #include "Scene.h"
 
@@ -58,6 +62,7 @@ static void usage() {
                "  --gpus arg                    row-tile the frame over N devices starting at --device (RCCL gather)\n"
                "  --preview arg                 also write the display-packed frame (Denoiser) as a binary PPM\n"
                "  --denoise-weights arg         with -d: PTDN weight file of the denoising network\n"
+               "  --progressive arg             refine the still frame in N passes of -s samples each (one buffer)\n"
             << std::endl;
 }
 
@@ -75,6 +80,8 @@ int main(int argc, const char** argv) {
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
   std::string posesFile, previewFile, denoiseWeights;
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
+  int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
+  bool progressiveGiven = false, framesGiven = false, gpusGiven = false;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -104,8 +111,9 @@ int main(int argc, const char** argv) {
     else if (a == "--rng") rng = value("--rng");
     else if (a == "--max-bounces") maxBounces = atoi(value("--max-bounces"));
     else if (a == "--spheres") nSpheres = atoi(value("--spheres"));
-    else if (a == "--frames") frames = atoi(value("--frames"));
-    else if (a == "--gpus") gpus = atoi(value("--gpus"));
+    else if (a == "--frames") { frames = atoi(value("--frames")); framesGiven = true; }
+    else if (a == "--gpus") { gpus = atoi(value("--gpus")); gpusGiven = true; }
+    else if (a == "--progressive") { progressive = atoi(value("--progressive")); progressiveGiven = true; }
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -149,6 +157,25 @@ int main(int argc, const char** argv) {
   if (denoising && batch) {
     std::cerr << "ERROR: -d cannot be combined with --batch: the denoiser runs after every frame of the loop" << std::endl;
     return 1;
+  }
+  if (progressiveGiven) {  // (before any device is touched, like the weight check below)
+    const char* other = framesGiven ? "--frames" : !posesFile.empty() ? "--poses" : batch ? "--batch" : gpusGiven ? "--gpus" : NULL;
+    if (other) {
+      std::cerr << "ERROR: --progressive cannot be combined with " << other << ": a progressive session refines one still frame on one device"
+                << std::endl;
+      return 1;
+    }
+    if (progressive < 1) {
+      std::cerr << "ERROR: --progressive needs at least one pass (got " << progressive << ")" << std::endl;
+      return 1;
+    }
+    const long long total = (long long)progressive * samplesPerPixel;
+    if (samplesPerPixel < 1 || total < 2 || total > INT_MAX) {
+      std::cerr << "ERROR: --progressive " << progressive << " with -s " << samplesPerPixel << " makes " << total
+                << " samples per pixel; a session needs 2 .. " << INT_MAX << " (one sample is the reference's unjittered frame: use -s 1)"
+                << std::endl;
+      return 1;
+    }
   }
   if (denoising) {  // the weight file is checked before any device is touched (host only)
     std::ifstream wf(denoiseWeights.c_str(), std::ios::binary);
@@ -246,6 +273,23 @@ int main(int argc, const char** argv) {
     std::cout << "Fly-through: " << times.size() << " frames, mean " << sum / times.size() << "ms, median "
               << sorted[sorted.size() / 2] << "ms, min " << sorted.front() << "ms, max " << sorted.back() << "ms ("
               << 1000.0 * times.size() / sum << " fps)" << std::endl;
+  } else if (progressiveGiven) {
+    // the interactive loop with the camera at rest, refining instead of re-rendering: pass k adds samplesPerPixel samples and
+    // leaves the frame of all k * samplesPerPixel in the buffer (-d: the network runs on it after every pass)
+    ProgressiveRenderer session(*single, width, height);
+    std::vector<float> times;
+    for (int k = 0; k < progressive; k++) {
+      times.push_back(session.Refine(d_buffer, scene, camera, samplesPerPixel));
+      if (net) denoiseTime = net->Denoise(d_buffer);
+    }
+    std::vector<float> sorted(times);
+    std::sort(sorted.begin(), sorted.end());
+    double sum = 0;
+    for (float t : times) sum += t;
+    std::cout << "Progressive: " << times.size() << " passes of " << samplesPerPixel << " spp (" << session.Samples()
+              << " spp), pass mean " << sum / times.size() << "ms, median " << sorted[sorted.size() / 2] << "ms, min "
+              << sorted.front() << "ms, max " << sorted.back() << "ms" << std::endl;
+    renderTime = (float)sum;
   } else {
     for (int f = 0; f < frames; f++) renderTime = render(d_buffer, scene, camera);
   }

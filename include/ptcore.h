@@ -307,6 +307,42 @@ int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_
  * network, like Renderer::Render (Renderer.h:63-75). */
 int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out);
 
+/* ---- progressive rendering ------------------------------------------------------------ */
+/* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
+ * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.
+ * A session belongs to one renderer and holds one still frame: one camera (basis + eye) and one scene.
+ *  - pt_progressive_enqueue(p, spp, ...) adds spp >= 1 samples per pixel and writes the frame of ALL samples so far into d_out,
+ *    in the renderer's layout and tile.  After a pass that leaves the session at n >= 2 samples, d_out is bit for bit the frame
+ *    the first Render() of a fresh renderer with the same options produces at n spp, however n was split into passes.
+ *  - Jitter: the reference jitters only when spp != 1 (pathtrace.cu:219-225).  A session cannot know its final count, so a
+ *    session ALWAYS jitters.  Hence the one exception: the frame after a first pass of exactly one sample is the first sample
+ *    of the jittered stream, not the reference's unjittered 1-spp frame.
+ *  - Generator: a session starts from the seed, not from the renderer's persisted state (XORWOW xorwow_init(id + seed),
+ *    philox key (seed, frame 0)).  Passes never touch the renderer's generator state or frame counter, and Render() calls
+ *    between passes do not disturb the session.  pt_progressive_reset returns it to 0 samples.
+ *  - d_out is output only: the state lives in the session's own record (PT_CHUNK_WORDS = 26 words per tile pixel, 104 B).
+ *    The caller may denoise the frame in place, overwrite it, or pass a different buffer on every pass.
+ *  - A pass whose camera (15 floats, compared bitwise), d_spheres or n_spheres differs from the session's first pass returns
+ *    PT_EINVAL ("reset the session").  The CONTENT of the scene cannot be checked: it must not change during a session.  A
+ *    total above INT_MAX samples (the reference's counts are int) and spp < 1 are PT_EINVAL too.
+ *  - Kernels: the resume builds of variants 6, 10, 13 and 14; an automatic renderer gets the automatic policy's choice with
+ *    8 and 9 replaced by 6.  pt_progressive_create refuses a renderer with an explicit other variant or fast_math.  Passes run
+ *    unchunked.
+ *  - A session shares its renderer's scratch (grid buffer, error word): do not run a session and its renderer concurrently on
+ *    two streams (the same rule as for one denoiser's enqueues).  Passes are ordered after the renderer's last launch. */
+typedef struct pt_progressive pt_progressive; /* opaque */
+int pt_progressive_create(pt_renderer* r, pt_progressive** out);
+int pt_progressive_reset(pt_progressive* p);
+/* One pass of spp samples, asynchronous on hip_stream (NULL = default stream). */
+int pt_progressive_enqueue(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres,
+                           const float basis[12], const float eye[3], void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around the pass. */
+int pt_progressive_render(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres,
+                          const float basis[12], const float eye[3], float* ms_out);
+int pt_progressive_samples(const pt_progressive* p, int64_t* samples);  /* samples per pixel so far */
+int pt_progressive_variant(const pt_progressive* p, int n_spheres, int* variant);  /* the variant the next pass runs */
+int pt_progressive_destroy(pt_progressive* p);
+
 /* ---- host-side inputs of the path ------------------------------------------------------ */
 /* The 9 spheres Scene() hard-codes, include/Scene.h:26-34 (host array). */
 int pt_scene_cornell(pt_sphere out[9]);

@@ -74,6 +74,10 @@ int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info
 /* Runs convolution `conv` alone on the workspace as it stands (synchronous); the rgb head writes [rows][cols][3] to d_rgb. */
 int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
 
+/* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
+ * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */
+int pt_debug_progressive_set_samples(pt_progressive* p, int64_t samples);
+
 #ifdef __cplusplus
 }
 #endif
