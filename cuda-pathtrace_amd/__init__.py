@@ -64,6 +64,19 @@ LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER_COPY = 0, 1, 2
 
 
+class AdaptiveOpts(ctypes.Structure):  # pt_adaptive_opts
+    _fields_ = [
+        ("tolerance", ctypes.c_float),
+        ("floor", ctypes.c_float),
+        ("min_samples", ctypes.c_int32),
+        ("radius", ctypes.c_int32),
+    ]
+
+
+# Progressive.set_adaptive's defaults (profiles/adaptive/README.md: how they were chosen)
+ADAPTIVE_FLOOR, ADAPTIVE_MIN_SAMPLES, ADAPTIVE_RADIUS = 0.05, 16, 1
+
+
 class MgpuOpts(ctypes.Structure):
     _fields_ = [
         ("gather", ctypes.c_int32),
@@ -143,6 +156,9 @@ ABI = {
     "pt_progressive_samples": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "pt_progressive_variant": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_progressive_destroy": (ctypes.c_int, [_vp]),
+    "pt_progressive_set_adaptive": (ctypes.c_int, [_vp, _vp]),
+    "pt_progressive_active": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "pt_progressive_counts": (ctypes.c_int, [_vp, _vp, _vp]),
 }
 # include/ptcore_lab.h: only libptcore_lab.so exports these
 LAB_ABI = {
@@ -165,6 +181,8 @@ LAB_ABI = {
                                                    ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
+    "pt_debug_progressive_record": (ctypes.c_int, [_vp, _vp]),
+    "pt_debug_progressive_set_active": (ctypes.c_int, [_vp, _vp]),
 }
 
 FN_INV_SQRT_LITERAL, FN_INV_SQRT_FAST, FN_SQRT_LITERAL, FN_SQRT_FAST, FN_SIN, FN_COS, FN_UNIFORM = range(7)
@@ -541,6 +559,54 @@ class Progressive:
 
     def set_samples(self, n):  # lab library only (pt_debug_progressive_set_samples)
         check(lib.pt_debug_progressive_set_samples(self.handle, n))
+
+    def set_adaptive(self, tolerance, floor=ADAPTIVE_FLOOR, min_samples=ADAPTIVE_MIN_SAMPLES, radius=ADAPTIVE_RADIUS):
+        """Adaptive sampling from the next first pass on (only at 0 samples): pixels whose mean luminance has a relative
+        standard error <= tolerance stop (include/ptcore.h has the rule).  tolerance=None turns it off."""
+        if tolerance is None:
+            check(lib.pt_progressive_set_adaptive(self.handle, None))
+            return
+        o = AdaptiveOpts(float(tolerance), float(floor), int(min_samples), int(radius))
+        check(lib.pt_progressive_set_adaptive(self.handle, ctypes.byref(o)))
+
+    def active(self):
+        """How many pixels the next pass renders (synchronous)."""
+        n = ctypes.c_int64(0)
+        check(lib.pt_progressive_active(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def counts(self):
+        """Every tile pixel's sample count, an int32 torch tensor on the current device (tile order)."""
+        import torch
+
+        n = self.renderer.rows * self.renderer.width
+        t = torch.empty(n, dtype=torch.int32, device="cuda")
+        if n:
+            torch.cuda.synchronize()
+            check(lib.pt_progressive_counts(self.handle, t.data_ptr(), None))
+            torch.cuda.synchronize()
+        return t
+
+    def refine(self, max_samples, pass_spp, d_out, d_spheres, n_spheres, basis, eye=DEFAULT_EYE, on_pass=None):
+        """Synchronous passes of pass_spp samples until no pixel is active or the next pass would take the session past
+        max_samples per pixel.  on_pass(session, pass_index, ms) is called after every pass.  Returns the number of passes."""
+        passes = 0
+        while not (passes > 0 and self.active() == 0) and self.samples() + pass_spp <= max_samples:
+            ms = self.render(pass_spp, d_out, d_spheres, n_spheres, basis, eye)
+            if on_pass is not None:
+                on_pass(self, passes, ms)
+            passes += 1
+        return passes
+
+    def record(self):  # lab library only (pt_debug_progressive_record): [26][tile pixels] uint32
+        n = self.renderer.rows * self.renderer.width
+        a = np.zeros((26, n), dtype=np.uint32)
+        check(lib.pt_debug_progressive_record(self.handle, a.ctypes.data))
+        return a
+
+    def set_active(self, mask):  # lab library only (pt_debug_progressive_set_active)
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        check(lib.pt_debug_progressive_set_active(self.handle, m.ctypes.data))
 
     def destroy(self):
         if self.handle:

@@ -728,6 +728,12 @@ struct pt_progressive {
   const pt_sphere* spheres;   // ... and scene: later passes must bring the same
   int n_spheres;
   hipEvent_t ev_start, ev_stop;
+  // adaptive sampling (pt_progressive_set_adaptive, pt_adaptive.hip): off unless d_adaptive is set
+  void* d_adaptive;           // one allocation: counts, list, mask, block sums, words (AdaptiveState)
+  AdaptiveState ast;
+  AdaptiveRule rule;
+  pt_adaptive_opts opts;
+  bool forced;                // the next pass takes mask bit 0 as it is (lab library: pt_debug_progressive_set_active)
 };
 
 // the automatic policy's choice restricted to the kernels with a resume build: where it would pick 8 or 9, variant 6
@@ -752,6 +758,11 @@ int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
   p->spheres = nullptr;
   p->n_spheres = 0;
   p->ev_start = p->ev_stop = nullptr;
+  p->d_adaptive = nullptr;
+  memset(&p->ast, 0, sizeof(p->ast));
+  memset(&p->rule, 0, sizeof(p->rule));
+  memset(&p->opts, 0, sizeof(p->opts));
+  p->forced = false;
   hipError_t e = hipSuccess;
   if (r->tile_pixels) e = hipMalloc((void**)&p->d_rec, (size_t)PT_CHUNK_WORDS * r->tile_pixels * sizeof(uint32_t));
   if (e == hipSuccess) e = hipEventCreate(&p->ev_start);
@@ -768,6 +779,7 @@ int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
 int pt_progressive_destroy(pt_progressive* p) {
   if (!p) return PT_OK;
   if (p->d_rec) (void)hipFree(p->d_rec);
+  if (p->d_adaptive) (void)hipFree(p->d_adaptive);
   if (p->ev_start) (void)hipEventDestroy(p->ev_start);
   if (p->ev_stop) (void)hipEventDestroy(p->ev_stop);
   delete p;
@@ -777,12 +789,26 @@ int pt_progressive_destroy(pt_progressive* p) {
 int pt_progressive_reset(pt_progressive* p) {
   if (!p) return pt_fail(PT_EINVAL, "pt_progressive_reset: session is NULL");
   p->samples = 0;
+  p->forced = false;  // (an adaptive session's next pass is a first pass again: every pixel active, the options kept)
+  return PT_OK;
+}
+
+// waits for the session's last pass (and whatever its renderer launched before it)
+static int session_sync(const pt_progressive* p) {
+  if (p->r->have_last) PT_HIP(hipEventSynchronize(p->r->ev_last));
   return PT_OK;
 }
 
 int pt_progressive_samples(const pt_progressive* p, int64_t* samples) {
   if (!p || !samples) return pt_fail(PT_EINVAL, "pt_progressive_samples: NULL argument");
   *samples = p->samples;
+  if (p->d_adaptive && p->samples > 0 && p->r->tile_pixels) {  // the maximum per-pixel count: the total, unless the set emptied
+    int rc = session_sync(p);
+    if (rc != PT_OK) return rc;
+    uint32_t w = 0u;
+    PT_HIP(hipMemcpy(&w, p->ast.words + 1, sizeof(w), hipMemcpyDeviceToHost));
+    *samples = (int64_t)w;
+  }
   return PT_OK;
 }
 
@@ -851,6 +877,25 @@ static void progressive_advance(pt_progressive* p, int spp, const pt_sphere* d_s
   p->samples += spp;
 }
 
+// The pass's launches: a plain session's one resume launch; an adaptive session's selection, the pass over its list and the frame
+static int launch_progressive_pass(pt_progressive* p, const ResumeKernelArgs& ra, int variant, hipStream_t stream) {
+  pt_renderer* r = p->r;
+  if (!p->d_adaptive) {
+    PT_HIP(pt_launch_resume_kernel(ra, r->opts.rng_mode, variant, stream));
+    return PT_OK;
+  }
+  const int mode = p->forced ? 1 : (p->samples == 0 ? 2 : 0);
+  PT_HIP(pt_launch_adaptive_select(p->ast, p->rule, p->d_rec, r->tile_pixels, r->width, (int)p->samples, ra.base.spp, mode, false, stream));
+  AdaptiveKernelArgs aa;
+  static_cast<ResumeKernelArgs&>(aa) = ra;
+  aa.list = p->ast.list;
+  aa.list_len = p->ast.words;
+  PT_HIP(pt_launch_adaptive_kernel(aa, r->opts.rng_mode, variant, stream));
+  PT_HIP(pt_launch_adaptive_finalize(p->d_rec, p->ast.counts, ra.base.out, r->tile_pixels, r->opts.layout == PT_LAYOUT_PLANAR, stream));
+  p->forced = false;
+  return PT_OK;
+}
+
 int pt_progressive_enqueue(pt_progressive* p, int spp, float* d_out, const pt_sphere* d_spheres, int n_spheres, const float basis[12],
                            const float eye[3], void* hip_stream) {
   ResumeKernelArgs ra;
@@ -862,7 +907,8 @@ int pt_progressive_enqueue(pt_progressive* p, int spp, float* d_out, const pt_sp
     const hipStream_t stream = (hipStream_t)hip_stream;
     rc = order_after_last(r, stream);  // (the grid buffer is the renderer's)
     if (rc != PT_OK) return rc;
-    PT_HIP(pt_launch_resume_kernel(ra, r->opts.rng_mode, variant, stream));
+    rc = launch_progressive_pass(p, ra, variant, stream);
+    if (rc != PT_OK) return rc;
     rc = mark_last(r, stream);
     if (rc != PT_OK) return rc;
   }
@@ -882,7 +928,8 @@ int pt_progressive_render(pt_progressive* p, int spp, float* d_out, const pt_sph
     rc = order_after_last(r, nullptr);
     if (rc != PT_OK) return rc;
     PT_HIP(hipEventRecord(p->ev_start, nullptr));
-    PT_HIP(pt_launch_resume_kernel(ra, r->opts.rng_mode, variant, nullptr));
+    rc = launch_progressive_pass(p, ra, variant, nullptr);
+    if (rc != PT_OK) return rc;
     PT_HIP(hipEventRecord(p->ev_stop, nullptr));
     PT_HIP(hipEventSynchronize(p->ev_stop));
     r->have_last = false;  // the pass has completed: nothing left to order against
@@ -893,6 +940,120 @@ int pt_progressive_render(pt_progressive* p, int spp, float* d_out, const pt_sph
   progressive_advance(p, spp, d_spheres, n_spheres, basis, eye);
   return PT_OK;
 }
+
+int pt_progressive_set_adaptive(pt_progressive* p, const pt_adaptive_opts* opts) {
+  if (!p) return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: session is NULL");
+  if (p->samples != 0) return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: the session holds %lld samples: only at 0 samples (reset it)", (long long)p->samples);
+  if (opts) {
+    if (!(opts->tolerance >= 0.0f)) return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: tolerance %g (>= 0)", (double)opts->tolerance);
+    if (!(opts->floor > 0.0f)) return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: floor %g (> 0)", (double)opts->floor);
+    if (opts->min_samples < 2) return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: min_samples %d (>= 2)", opts->min_samples);
+    if (opts->radius < 0 || opts->radius > PT_ADAPTIVE_MAX_RADIUS)
+      return pt_fail(PT_EINVAL, "pt_progressive_set_adaptive: radius %d (0..%d)", opts->radius, PT_ADAPTIVE_MAX_RADIUS);
+  }
+  if (!opts) {  // off: a plain session again
+    if (p->d_adaptive) (void)hipFree(p->d_adaptive);
+    p->d_adaptive = nullptr;
+    memset(&p->ast, 0, sizeof(p->ast));
+    p->forced = false;
+    return PT_OK;
+  }
+  const uint32_t tp = p->r->tile_pixels;
+  if (!p->d_adaptive && tp) {
+    const size_t n_blocks = (tp + PT_ADAPTIVE_BLOCK - 1) / PT_ADAPTIVE_BLOCK;
+    const size_t words = 2 * (size_t)tp + n_blocks + 4;  // counts, list, block sums, words; then the mask bytes
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, words * sizeof(uint32_t) + tp);
+    if (e != hipSuccess) return pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_progressive_set_adaptive: %s", hipGetErrorString(e));
+    uint32_t* w = (uint32_t*)d;
+    p->d_adaptive = d;
+    p->ast.counts = w;
+    p->ast.list = w + tp;
+    p->ast.block_sums = w + 2 * (size_t)tp;
+    p->ast.words = w + 2 * (size_t)tp + n_blocks;
+    p->ast.mask = (uint8_t*)(w + words);
+    PT_HIP(hipMemset(p->ast.words, 0, 4 * sizeof(uint32_t)));
+  }
+  p->opts = *opts;
+  p->rule.tolerance = (double)opts->tolerance;
+  p->rule.floor = (double)opts->floor;
+  p->rule.min_samples = opts->min_samples;
+  p->rule.radius = opts->radius;
+  p->forced = false;
+  return PT_OK;
+}
+
+int pt_progressive_active(pt_progressive* p, int64_t* active) {
+  if (!p || !active) return pt_fail(PT_EINVAL, "pt_progressive_active: NULL argument");
+  pt_renderer* r = p->r;
+  *active = (int64_t)r->tile_pixels;
+  if (!p->d_adaptive || p->samples == 0 || !r->tile_pixels) return PT_OK;  // (a first pass renders every pixel)
+  int rc = order_after_last(r, nullptr);
+  if (rc != PT_OK) return rc;
+  // the next pass's decision without its list: the selection's first three steps (they only rewrite the scratch bits)
+  PT_HIP(pt_launch_adaptive_select(p->ast, p->rule, p->d_rec, r->tile_pixels, r->width, (int)p->samples, (int)p->samples + 1,
+                                   p->forced ? 1 : 0, true, nullptr));
+  uint32_t n = 0u;
+  PT_HIP(hipMemcpy(&n, p->ast.words, sizeof(n), hipMemcpyDeviceToHost));
+  r->have_last = false;  // (the copy waited for everything before it on the default stream)
+  *active = (int64_t)n;
+  return PT_OK;
+}
+
+int pt_progressive_counts(pt_progressive* p, uint32_t* d_counts, void* hip_stream) {
+  if (!p) return pt_fail(PT_EINVAL, "pt_progressive_counts: session is NULL");
+  pt_renderer* r = p->r;
+  if (!r->tile_pixels) return PT_OK;
+  if (!d_counts) return pt_fail(PT_EINVAL, "pt_progressive_counts: d_counts is NULL");
+  if (p->samples > (int64_t)UINT32_MAX) return pt_fail(PT_EINVAL, "pt_progressive_counts: count beyond 32 bits");
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  int rc = order_after_last(r, stream);
+  if (rc != PT_OK) return rc;
+  if (p->d_adaptive && p->samples > 0)
+    PT_HIP(hipMemcpyAsync(d_counts, p->ast.counts, (size_t)r->tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+  else
+    PT_HIP(hipMemsetD32Async((hipDeviceptr_t)d_counts, (int)p->samples, r->tile_pixels, stream));
+  return mark_last(r, stream);  // (a later pass rewrites the counts: it waits for the copy)
+}
+
+#if PT_BUILD_EXPERIMENTS
+// lab library: a copy of the session's record, PT_CHUNK_WORDS words per tile pixel, [word][pixel] (include/ptcore_lab.h)
+int pt_debug_progressive_record(pt_progressive* p, uint32_t* host) {
+  if (!p || !host) return pt_fail(PT_EINVAL, "pt_debug_progressive_record: NULL argument");
+  if (!p->r->tile_pixels) return PT_OK;
+  int rc = session_sync(p);
+  if (rc != PT_OK) return rc;
+  PT_HIP(hipMemcpy(host, p->d_rec, (size_t)PT_CHUNK_WORDS * p->r->tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// lab library: the next pass renders exactly the pixels of host_mask (one byte per tile pixel, non-zero = active); the set may only
+// shrink (a pixel the last pass did not render cannot come back)
+int pt_debug_progressive_set_active(pt_progressive* p, const uint8_t* host_mask) {
+  if (!p || !host_mask) return pt_fail(PT_EINVAL, "pt_debug_progressive_set_active: NULL argument");
+  if (!p->d_adaptive) return pt_fail(PT_EINVAL, "pt_debug_progressive_set_active: not an adaptive session");
+  if (p->samples == 0) return pt_fail(PT_EINVAL, "pt_debug_progressive_set_active: a first pass renders every pixel");
+  const uint32_t tp = p->r->tile_pixels;
+  if (!tp) return PT_OK;
+  int rc = session_sync(p);
+  if (rc != PT_OK) return rc;
+  uint8_t* m = (uint8_t*)malloc(tp);
+  if (!m) return pt_fail(PT_ENOMEM, "pt_debug_progressive_set_active: out of host memory");
+  hipError_t e = hipMemcpy(m, p->ast.mask, tp, hipMemcpyDeviceToHost);
+  bool grows = false;
+  for (uint32_t i = 0; e == hipSuccess && i < tp; i++) {
+    const uint8_t want = host_mask[i] ? 1u : 0u;
+    if (want && !(m[i] & 1u)) grows = true;
+    m[i] = want;
+  }
+  if (e == hipSuccess && !grows) e = hipMemcpy(p->ast.mask, m, tp, hipMemcpyHostToDevice);
+  free(m);
+  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_debug_progressive_set_active: %s", hipGetErrorString(e));
+  if (grows) return pt_fail(PT_EINVAL, "pt_debug_progressive_set_active: the set may only shrink");
+  p->forced = true;
+  return PT_OK;
+}
+#endif
 
 #if PT_BUILD_EXPERIMENTS
 // lab library: a session's sample count without the samples (the INT_MAX limit's test, include/ptcore_lab.h)

@@ -168,6 +168,12 @@ struct ResumeKernelArgs {
   int32_t sample_begin;        // samples the session holds before this pass: 0 = start from zero and the seeded generator
   uint32_t* session;           // PT_CHUNK_WORDS words per tile pixel, [word][pixel] like chunk_state (philox: the first 20)
 };
+// One pass of an adaptive session (pt_adaptive.hip): a resume pass over the pixels of the session's active list only.  Every
+// listed pixel holds sample_begin samples (the active set only shrinks: EXACTNESS.md A.20).  base.out is not written.
+struct AdaptiveKernelArgs : ResumeKernelArgs {
+  const uint32_t* list;        // tile pixel indices in raster order ...
+  const uint32_t* list_len;    // ... and how many (one device word): both written by pt_launch_adaptive_select
+};
 // words handed from one chunk of a pixel block to the next: 10 sums, 2 counts (colour; the three first-hit accumulators share
 // one), 4 x {mean, M2}, and the 6 generator words (xorwow only; philox needs none)
 #define PT_CHUNK_WORDS 26
@@ -218,6 +224,35 @@ hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, hip
 bool pt_kernel_has_resume(int variant);
 const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar);
 hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream);
+// adaptive passes: the same builds over a device-side list of pixels (pt_adaptive.hip selects, the pass renders, finalize writes)
+const void* pt_adaptive_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar);
+hipError_t pt_launch_adaptive_kernel(const AdaptiveKernelArgs& aa, int rng_mode, int variant, hipStream_t stream);
+// The session's adaptive state on the device (pt_adaptive.hip): per tile pixel a count, a list slot and a mask byte, plus one
+// word per 256-pixel block and three words (list length, maximum count, spare).
+struct AdaptiveState {
+  uint32_t* counts;            // samples each pixel holds
+  uint32_t* list;              // active pixels, raster order
+  uint8_t* mask;               // bit 0: active in the last pass (or forced for the next one); bits 1, 2: scratch of the selection
+  uint32_t* block_sums;        // per 256-pixel block: active pixels, then their exclusive prefix
+  uint32_t* words;             // [0] list length, [1] maximum count
+};
+struct AdaptiveRule {
+  double tolerance;            // target relative standard error of the mean luminance
+  double floor;                // luminance floor
+  int32_t min_samples;         // the rule is evaluated from this count on
+  int32_t radius;              // dilation window (2 radius + 1)^2, clipped to the tile
+};
+#define PT_ADAPTIVE_BLOCK 256
+#define PT_ADAPTIVE_MAX_RADIUS 4
+// Decide the pass's active set and list.  n = samples every active pixel holds now, n_end = after the pass.  mode: 0 = evaluate
+// the rule (when n >= min_samples) on the pixels of mask bit 0, 1 = take mask bit 0 as it is (a forced set), 2 = every pixel
+// (a session's first pass).  Active pixels' counts become n_end.  peek: only the decision and its size (words[0]); the list,
+// the counts, mask bit 0 and the maximum count stay as they are.
+hipError_t pt_launch_adaptive_select(const AdaptiveState& s, const AdaptiveRule& rule, const uint32_t* rec, uint32_t tile_pixels,
+                                     int width, int n, int n_end, int mode, bool peek, hipStream_t stream);
+// The frame of every tile pixel at its own count from the record, in the renderer's layout (frame_values, pt_scene_lds.h)
+hipError_t pt_launch_adaptive_finalize(const uint32_t* rec, const uint32_t* counts, float* out, uint32_t tile_pixels, bool planar,
+                                       hipStream_t stream);
 hipError_t pt_launch_build_grid(const pt_sphere* spheres, int n, uint32_t* accel, const float* eye /* camera hint or NULL */,
                                 bool pooled /* for variant 13's LDS image (fewer cells at large n) */, hipStream_t stream,
                                 int threads = PT_GRID_BLOCK_THREADS /* workgroup size of the kernel that will stage the grid */);

@@ -101,20 +101,32 @@ __device__ __forceinline__ void chunk_publish(const PixelKernelArgs& a, uint32_t
 // from the session's record -- the state a chunk hands to the next one, same words, same [word][pixel] layout -- unless
 // sample_begin is 0, and ends by writing BOTH the frame of all spp samples and the record.  Per pixel, a session performs the
 // operations of one spp-sample launch in their order (EXACTNESS.md A.19); the one difference is that a session always jitters.
-template <bool FRAMES, bool RESUME = false> struct KernelArgsOf { typedef PixelKernelArgs type; };
-template <> struct KernelArgsOf<true, false> { typedef FramesKernelArgs type; };  // (the cameras travel as kernel arguments too)
-template <> struct KernelArgsOf<false, true> { typedef ResumeKernelArgs type; };
-template <bool FRAMES, bool RESUME> __device__ __forceinline__ PixelKernelArgs& base_args(typename KernelArgsOf<FRAMES, RESUME>::type& args) {
+//
+// ADAPTIVE (RESUME builds only; adaptive progressive passes, pt_adaptive.hip): lane slot -> pixel list[slot] of the session's
+// active list (raster order, *list_len entries, written on the device by the selection just before).  Slots past the length
+// are inactive lanes; a workgroup whose first slot lies past it leaves before staging anything.  The pass writes only the
+// record: the frame is formed afterwards for every pixel at its own count (pt_launch_adaptive_finalize).
+template <bool FRAMES, bool RESUME = false, bool ADAPTIVE = false> struct KernelArgsOf { typedef PixelKernelArgs type; };
+template <> struct KernelArgsOf<true, false, false> { typedef FramesKernelArgs type; };  // (the cameras travel as kernel arguments too)
+template <> struct KernelArgsOf<false, true, false> { typedef ResumeKernelArgs type; };
+template <> struct KernelArgsOf<false, true, true> { typedef AdaptiveKernelArgs type; };
+template <bool FRAMES, bool RESUME, bool ADAPTIVE> __device__ __forceinline__ PixelKernelArgs& base_args(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type& args) {
   if constexpr (FRAMES || RESUME) return args.base; else return args;
 }
 
 // WIDE (variant 13 only; the launcher's "variant 14"): 1024-thread workgroups, one per CU -- pt_grid.h, grid_max_entries
 // (the 8-bounce XORWOW resume build: at five waves it spills two words its twin does not -- four waves, like the batch build)
-template <int RNG, int VAR, bool LEAN = false, int REFB = 0, bool FRAMES = false, bool WIDE = false, bool RESUME = false>
+template <int RNG, int VAR, bool LEAN = false, int REFB = 0, bool FRAMES = false, bool WIDE = false, bool RESUME = false, bool ADAPTIVE = false>
 __global__ void __launch_bounds__((kBlockThreads<VAR, WIDE>), (((FRAMES || (RESUME && REFB == 8)) && RNG == PT_RNG_XORWOW) ? PT_MIN_WAVES : kMinWavesR<VAR, REFB, RNG>)) PT_KERNEL_ATTR
-pixel_kernel(typename KernelArgsOf<FRAMES, RESUME>::type args) {  // (an XORWOW batch has one workgroup per pixel block for all its frames: the
+pixel_kernel(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type args) {  // (an XORWOW batch has one workgroup per pixel block for all its frames: the
                                                            // interactive shape fills four of a CU's five slots, so that build takes 128 registers)
-  PixelKernelArgs& a = base_args<FRAMES, RESUME>(args);
+  PixelKernelArgs& a = base_args<FRAMES, RESUME, ADAPTIVE>(args);
+  static_assert(!ADAPTIVE || RESUME, "adaptive passes are resume builds");
+  uint32_t n_active = 0u;  // (adaptive: the length of the active list; workgroup-uniform)
+  if constexpr (ADAPTIVE) {
+    n_active = __builtin_amdgcn_readfirstlane(*args.list_len);
+    if (blockIdx.x * (uint32_t)kBlockThreads<VAR, WIDE> >= n_active) return;  // no active slot in this workgroup
+  }
   // a batch of frames, two shapes (head of this section): the counter-based generator's frames are independent -- one workgroup
   // per (frame, pixel block), frame-major; XORWOW's are a chain per pixel -- one workgroup per pixel block, looping over the frames
   constexpr bool FRAME_GRID = FRAMES && RNG == PT_RNG_PHILOX, FRAME_LOOP = FRAMES && !FRAME_GRID;
@@ -189,8 +201,11 @@ pixel_kernel(typename KernelArgsOf<FRAMES, RESUME>::type args) {  // (an XORWOW 
       block_id = blockIdx.x - chunk * n_blocks;
     }
   }
-  const uint32_t tp = block_id * kBlockThreads<VAR, WIDE> + threadIdx.x;  // pixel index inside the tile
-  const bool active = tp < a.tile_pixels;  // lanes past the tile stay for the cooperative epilogue
+  const uint32_t slot = block_id * kBlockThreads<VAR, WIDE> + threadIdx.x;
+  const bool active = ADAPTIVE ? slot < n_active : slot < a.tile_pixels;  // lanes past the tile (the list) stay for the cooperative parts
+  const uint32_t tp = [&]() -> uint32_t {  // pixel index inside the tile
+    if constexpr (ADAPTIVE) return active ? args.list[slot] : 0u; else return slot;
+  }();
   const int row = a.row_begin + (int)(tp / (uint32_t)a.width);
   const int col = (int)(tp % (uint32_t)a.width);
   const uint32_t id = (uint32_t)row * (uint32_t)a.width + (uint32_t)col;  // :206
@@ -549,21 +564,21 @@ frame_top:
   }
 
   const float fs = (float)a.spp;  // :234-237
-  const float px[14] = {L.color.x / fs,  L.color.y / fs,  L.color.z / fs,  L.normal.x / fs, L.normal.y / fs,
-                        L.normal.z / fs, L.albedo.x / fs, L.albedo.y / fs, L.albedo.z / fs, L.depth / fs,
-                        welford_variance(var[0]), welford_variance(var[1]), welford_variance(var[2]),
-                        welford_variance(var[3])};  // :240-254
+  float px[14];
+  frame_values(L, var, fs, px);  // :240-254
   float* out_f = a.out;  // this frame's buffers
   float* vtx_f = a.vertices;
   if constexpr (FRAMES) {
     out_f += (size_t)fr * args.out_stride;
     if (vtx_f) vtx_f += (size_t)fr * args.vtx_stride;
   }
-  if (vtx_f && active) store_display_vertex(vtx_f + (size_t)tp * 3, a.width, row, col, px[0], px[1], px[2]);
+  if (!ADAPTIVE && vtx_f && active) store_display_vertex(vtx_f + (size_t)tp * 3, a.width, row, col, px[0], px[1], px[2]);
   // The 64 pixels of a wave are 64 consecutive columns, so their 64 x 14 floats are ONE contiguous
   // 3584-byte span of the [row][col][14] buffer: transpose through the wave's own LDS slice and write
   // it as 224 coalesced 16-byte stores (3.5 per lane) instead of 14 strided dword stores per lane.
-  if (!REF && a.planar) {  // channel-first: consecutive lanes are consecutive columns of one plane, stores coalesce as they are
+  if (ADAPTIVE) {
+    // (an adaptive pass writes only the record: its lanes are scattered pixels; pt_adaptive.hip forms the frame)
+  } else if (!REF && a.planar) {  // channel-first: consecutive lanes are consecutive columns of one plane, stores coalesce as they are
     // (the reference-configuration builds are interleaved-only: the launcher sends planar frames to the generic build)
     if (active) {
 #pragma unroll
@@ -1259,6 +1274,30 @@ static resume_kernel_fn select_resume_kernel(int rng_mode, int variant, bool lea
   }
 }
 
+typedef void (*adaptive_kernel_fn)(AdaptiveKernelArgs);
+
+static adaptive_kernel_fn select_adaptive_kernel(int rng_mode, int variant, bool lean, int ref) {
+  const bool philox = rng_mode == PT_RNG_PHILOX;
+  if (variant == 6 && ref == 5 && !lean)
+    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5, false, false, true, true>;
+  if (variant == 6 && ref == 8 && !lean)
+    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8, false, false, true, true>;
+  if (lean) {
+    switch (variant) {
+      case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, true, 0, false, false, true, true>;
+      case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, true, 0, false, false, true, true>;
+      case 13: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, false, true, true>;
+      case 14: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, true, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, true, true, true>;
+      default: return nullptr;
+    }
+  }
+  switch (variant) {
+    case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 0, false, false, true, true>;
+    case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, false, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, false, 0, false, false, true, true>;
+    default: return nullptr;
+  }
+}
+
 bool pt_kernel_has_resume(int variant) { return variant == 6 || variant == 10 || variant == 13 || variant == 14; }
 
 const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
@@ -1266,13 +1305,13 @@ const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, in
 }
 
 // One pass: pt_launch_pixel_kernel without sample chunking (ra.base.chunks and repair are ignored) and with the issue priority
-// decided by the pass's own sample count
-hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream) {
+// decided by the pass's own sample count.  An adaptive pass launches the tile's full block count: the workgroups past the
+// device-side list length leave at once (pixel_kernel, ADAPTIVE), so nothing is read back.
+template <class Args>
+static hipError_t launch_pass(void (*fn)(Args), const Args& ra, int variant, hipStream_t stream) {
   const PixelKernelArgs& a = ra.base;
-  if (!pt_kernel_has_resume(variant) || !ra.session || ra.sample_begin < 0 || ra.sample_begin >= a.spp || a.rng_state) return hipErrorInvalidValue;
-  resume_kernel_fn fn = select_resume_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u));
   if (!fn) return hipErrorInvalidValue;
-  ResumeKernelArgs b = ra;
+  Args b = ra;
   b.base.scene_lds_f4 = (uint32_t)scene_lds_f4(a.n_spheres, variant);
   b.base.prio = (a.spp - ra.sample_begin >= PT_PRIO_MIN_SPP || a.prio != 0u) ? 1u : 0u;
   b.base.chunks = 0u;
@@ -1295,4 +1334,24 @@ hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int
   const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + block - 1) / block);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds, stream, b);
   return hipGetLastError();
+}
+
+hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream) {
+  const PixelKernelArgs& a = ra.base;
+  if (!pt_kernel_has_resume(variant) || !ra.session || ra.sample_begin < 0 || ra.sample_begin >= a.spp || a.rng_state) return hipErrorInvalidValue;
+  return launch_pass(select_resume_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u)),
+                     ra, variant, stream);
+}
+
+const void* pt_adaptive_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  return (const void*)select_adaptive_kernel(rng_mode, variant, lds_lean(n_spheres, variant), ref_config(n_spheres, max_bounces, variant, planar));
+}
+
+hipError_t pt_launch_adaptive_kernel(const AdaptiveKernelArgs& aa, int rng_mode, int variant, hipStream_t stream) {
+  const PixelKernelArgs& a = aa.base;
+  if (!pt_kernel_has_resume(variant) || !aa.session || !aa.list || !aa.list_len || aa.sample_begin < 0 || aa.sample_begin >= a.spp ||
+      a.rng_state)
+    return hipErrorInvalidValue;
+  return launch_pass(select_adaptive_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u)),
+                     aa, variant, stream);
 }

@@ -184,6 +184,25 @@ struct TraceOutput {  // src/pathtrace.cu:24-36
   float depth;
 };
 
+// The 14 channels of a pixel after fs samples (:234-254): the sums over fs and the four variances.  ONE definition for the
+// frame pixel_kernel writes and the one pt_adaptive.hip's finalize forms from a session's record (EXACTNESS.md A.20).
+__device__ __forceinline__ void frame_values(const TraceOutput& L, const Welford var[4], float fs, float px[14]) {
+  px[0] = L.color.x / fs;
+  px[1] = L.color.y / fs;
+  px[2] = L.color.z / fs;
+  px[3] = L.normal.x / fs;
+  px[4] = L.normal.y / fs;
+  px[5] = L.normal.z / fs;
+  px[6] = L.albedo.x / fs;
+  px[7] = L.albedo.y / fs;
+  px[8] = L.albedo.z / fs;
+  px[9] = L.depth / fs;
+  px[10] = welford_variance(var[0]);
+  px[11] = welford_variance(var[1]);
+  px[12] = welford_variance(var[2]);
+  px[13] = welford_variance(var[3]);
+}
+
 template <int RNG>
 struct Rng;
 

@@ -47,5 +47,27 @@ class ProgressiveRenderer {
     return (long long)n;
   }
   void Reset() { gpuErrchk(pt_progressive_reset(session)); }
+
+  // Adaptive sampling (include/ptcore.h, pt_progressive_set_adaptive): only at 0 samples; later passes render only the pixels
+  // whose mean luminance is not yet within `tolerance` (relative standard error).  Samples() is then the maximum count.
+  void SetAdaptive(float tolerance, float floor, int minSamples, int radius) {
+    pt_adaptive_opts o;
+    o.tolerance = tolerance;
+    o.floor = floor;
+    o.min_samples = minSamples;
+    o.radius = radius;
+    gpuErrchk(pt_progressive_set_adaptive(session, &o));
+  }
+  // how many pixels the next Refine() renders (synchronous)
+  long long Active() {
+    int64_t n = 0;
+    gpuErrchk(pt_progressive_active(session, &n));
+    return (long long)n;
+  }
+  // every pixel's sample count into d_counts (width * height uint32 in device memory, row-major); synchronous
+  void Counts(unsigned int* d_counts) {
+    gpuErrchk(pt_progressive_counts(session, d_counts, NULL));
+    gpuErrchk(pt_device_synchronize());
+  }
 };
 #endif

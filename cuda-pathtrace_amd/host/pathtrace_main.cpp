@@ -63,6 +63,10 @@ static void usage() {
                "  --preview arg                 also write the display-packed frame (Denoiser) as a binary PPM\n"
                "  --denoise-weights arg         with -d: PTDN weight file of the denoising network\n"
                "  --progressive arg             refine the still frame in N passes of -s samples each (one buffer)\n"
+               "  --adaptive arg                with --progressive: stop pixels whose mean luminance has a relative\n"
+               "                                standard error <= arg; ends early when no pixel is active\n"
+               "  --adaptive-min arg            with --adaptive: no pixel stops before this many samples (default 16)\n"
+               "  --adaptive-radius arg         with --adaptive: dilation radius 0..4 (default 1)\n"
             << std::endl;
 }
 
@@ -82,6 +86,12 @@ int main(int argc, const char** argv) {
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
   bool progressiveGiven = false, framesGiven = false, gpusGiven = false;
+  // --adaptive TOL (with --progressive): adaptive sampling, pt_progressive_set_adaptive (floor: the library's Python default)
+  bool adaptiveGiven = false;
+  double adaptiveTol = 0.0;
+  int adaptiveMin = 16, adaptiveRadius = 1;
+  const float adaptiveFloor = 0.05f;
+  bool adaptiveMinGiven = false, adaptiveRadiusGiven = false;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -114,6 +124,9 @@ int main(int argc, const char** argv) {
     else if (a == "--frames") { frames = atoi(value("--frames")); framesGiven = true; }
     else if (a == "--gpus") { gpus = atoi(value("--gpus")); gpusGiven = true; }
     else if (a == "--progressive") { progressive = atoi(value("--progressive")); progressiveGiven = true; }
+    else if (a == "--adaptive") { adaptiveTol = atof(value("--adaptive")); adaptiveGiven = true; }
+    else if (a == "--adaptive-min") { adaptiveMin = atoi(value("--adaptive-min")); adaptiveMinGiven = true; }
+    else if (a == "--adaptive-radius") { adaptiveRadius = atoi(value("--adaptive-radius")); adaptiveRadiusGiven = true; }
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -157,6 +170,29 @@ int main(int argc, const char** argv) {
   if (denoising && batch) {
     std::cerr << "ERROR: -d cannot be combined with --batch: the denoiser runs after every frame of the loop" << std::endl;
     return 1;
+  }
+  if ((adaptiveGiven || adaptiveMinGiven || adaptiveRadiusGiven) && !progressiveGiven) {  // (before any device is touched)
+    std::cerr << "ERROR: " << (adaptiveGiven ? "--adaptive" : adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius")
+              << " needs --progressive: adaptive sampling refines a progressive session" << std::endl;
+    return 1;
+  }
+  if ((adaptiveMinGiven || adaptiveRadiusGiven) && !adaptiveGiven) {
+    std::cerr << "ERROR: " << (adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius") << " needs --adaptive" << std::endl;
+    return 1;
+  }
+  if (adaptiveGiven) {
+    if (!(adaptiveTol >= 0.0) || !(adaptiveTol <= 3.4e38)) {
+      std::cerr << "ERROR: --adaptive " << adaptiveTol << ": the tolerance must be a finite number >= 0" << std::endl;
+      return 1;
+    }
+    if (adaptiveMin < 2) {
+      std::cerr << "ERROR: --adaptive-min " << adaptiveMin << ": at least 2 samples (the variance needs two)" << std::endl;
+      return 1;
+    }
+    if (adaptiveRadius < 0 || adaptiveRadius > 4) {
+      std::cerr << "ERROR: --adaptive-radius " << adaptiveRadius << ": 0 .. 4" << std::endl;
+      return 1;
+    }
   }
   if (progressiveGiven) {  // (before any device is touched, like the weight check below)
     const char* other = framesGiven ? "--frames" : !posesFile.empty() ? "--poses" : batch ? "--batch" : gpusGiven ? "--gpus" : NULL;
@@ -276,12 +312,31 @@ int main(int argc, const char** argv) {
   } else if (progressiveGiven) {
     // the interactive loop with the camera at rest, refining instead of re-rendering: pass k adds samplesPerPixel samples and
     // leaves the frame of all k * samplesPerPixel in the buffer (-d: the network runs on it after every pass)
+    // (--adaptive: only the pixels that have not converged; the loop ends early when none is left)
     ProgressiveRenderer session(*single, width, height);
+    if (adaptiveGiven) session.SetAdaptive((float)adaptiveTol, adaptiveFloor, adaptiveMin, adaptiveRadius);
     std::vector<float> times;
+    unsigned int* d_counts = NULL;
+    if (adaptiveGiven) gpuErrchk(pt_malloc((void**)&d_counts, (size_t)width * height * sizeof(unsigned int)));
+    std::vector<unsigned int> counts(adaptiveGiven ? (size_t)width * height : 0);
     for (int k = 0; k < progressive; k++) {
+      long long active = (long long)width * height;
+      if (adaptiveGiven && k > 0) {
+        active = session.Active();
+        if (active == 0) break;
+      }
       times.push_back(session.Refine(d_buffer, scene, camera, samplesPerPixel));
       if (net) denoiseTime = net->Denoise(d_buffer);
+      if (adaptiveGiven) {
+        session.Counts(d_counts);
+        gpuErrchk(pt_memcpy_d2h(counts.data(), d_counts, counts.size() * sizeof(unsigned int)));
+        double spp = 0;
+        for (unsigned int c : counts) spp += c;
+        std::cout << "Pass " << k + 1 << ": active " << 100.0 * active / ((double)width * height) << "%, mean "
+                  << spp / counts.size() << " spp, " << times.back() << "ms" << std::endl;
+      }
     }
+    if (d_counts) gpuErrchk(pt_free(d_counts));
     std::vector<float> sorted(times);
     std::sort(sorted.begin(), sorted.end());
     double sum = 0;

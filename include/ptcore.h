@@ -343,6 +343,46 @@ int pt_progressive_samples(const pt_progressive* p, int64_t* samples);  /* sampl
 int pt_progressive_variant(const pt_progressive* p, int n_spheres, int* variant);  /* the variant the next pass runs */
 int pt_progressive_destroy(pt_progressive* p);
 
+/* ---- adaptive sampling of a progressive session ------------------------------------------- */
+/* Opt-in per session: pt_progressive_set_adaptive at 0 samples (after create or reset; later it is PT_EINVAL).  NULL turns it
+ * off.  A session without the call behaves exactly as above.
+ *  - Options: tolerance >= 0, the target relative standard error of a pixel's mean luminance; floor > 0, the luminance floor
+ *    (dark pixels do not need infinitely many samples); min_samples >= 2, no pixel stops before this count; radius 0..4, the
+ *    dilation window.  Any other value (NaN included) is PT_EINVAL.
+ *  - Monotone active set.  The first pass renders every pixel.  Each later pass first decides which pixels stay active, then
+ *    adds spp samples to exactly those.  A stopped pixel never resumes, so all active pixels hold the same count: the
+ *    session's total (the sample index of a pass stays uniform across its launch).
+ *  - Rule, for each pixel active in the last pass once the session holds n >= min_samples: with the pixel's frame values at n
+ *    as the frame forms them (c0..c2 = sum / (float)n, c10 = the colour's Welford variance, lum = the reference's luminance of
+ *    c0..c2), the pixel is CONVERGED when (a) no sample hit anything (depth 0), or (b) every one of its n samples scored
+ *    (the colour variance skips escaped paths, pathtrace.cu:157-161) and
+ *        (double)c10 <= ((double)tol * (double)tol * (double)n) * (m * m),  m = max((double)lum, (double)floor),
+ *    evaluated left to right in double.  Because of the "every sample scored" condition, a pixel where some path escapes
+ *    keeps sampling: adaptivity mostly helps closed scenes.
+ *  - Dilation: a pixel stays active if it was active and an active, unconverged pixel lies in the (2 radius + 1)^2 window
+ *    around it, clipped to the renderer's tile.
+ *  - Every pass writes the WHOLE frame into d_out (pixels that stopped earlier included; d_out stays output only).  A pass
+ *    with no active pixel adds nothing and only writes the frame.
+ *  - Contract: after any pass, every pixel p with count n_p >= 2 is bit for bit pixel p of a fresh renderer's first Render()
+ *    at n_p spp (the one-sample jitter exception above stays as it is).
+ *  - pt_progressive_samples returns the maximum per-pixel count (synchronous for an adaptive session); the INT_MAX limit
+ *    applies to the session's total, which is that maximum while any pixel is active.  pt_progressive_reset returns to 0
+ *    samples with every pixel active and keeps the options.
+ *  - Device memory: 9 bytes per tile pixel (count, list slot, mask) on top of the session's record, allocated by the first
+ *    pt_progressive_set_adaptive call with options. */
+typedef struct pt_adaptive_opts {
+  float tolerance;      /* target relative standard error of the mean luminance, >= 0 */
+  float floor;          /* luminance floor, > 0 */
+  int32_t min_samples;  /* >= 2 */
+  int32_t radius;       /* 0..4 */
+} pt_adaptive_opts;
+int pt_progressive_set_adaptive(pt_progressive* p, const pt_adaptive_opts* opts);
+/* Synchronous: how many pixels the next pass renders (the whole tile for a plain session and before a first pass). */
+int pt_progressive_active(pt_progressive* p, int64_t* active);
+/* Every tile pixel's sample count (uint32, tile order) into device memory, device to device on hip_stream; a plain session's
+ * counts are all its total. */
+int pt_progressive_counts(pt_progressive* p, uint32_t* d_counts, void* hip_stream);
+
 /* ---- host-side inputs of the path ------------------------------------------------------ */
 /* The 9 spheres Scene() hard-codes, include/Scene.h:26-34 (host array). */
 int pt_scene_cornell(pt_sphere out[9]);

@@ -77,6 +77,11 @@ int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
 /* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
  * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */
 int pt_debug_progressive_set_samples(pt_progressive* p, int64_t samples);
+/* A copy of the session's record: PT_CHUNK_WORDS (26) words per tile pixel, [word][pixel] (synchronous). */
+int pt_debug_progressive_record(pt_progressive* p, uint32_t* host);
+/* Adaptive sessions after their first pass: the next pass renders exactly the pixels whose byte in host_mask (one per tile
+ * pixel) is non-zero, without the rule.  The set may only shrink: a pixel the last pass did not render is PT_EINVAL. */
+int pt_debug_progressive_set_active(pt_progressive* p, const uint8_t* host_mask);
 
 #ifdef __cplusplus
 }
