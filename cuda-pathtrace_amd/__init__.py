@@ -149,6 +149,9 @@ ABI = {
     "pt_denoiser_destroy": (ctypes.c_int, [_vp]),
     "pt_denoiser_enqueue": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "pt_denoiser_denoise": (ctypes.c_int, [_vp, _vp, _vp, _fp]),
+    "pt_denoiser_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_denoiser_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pt_denoiser_denoise_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _fp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -180,6 +183,8 @@ LAB_ABI = {
     "pt_debug_denoiser_conv_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                    ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_debug_denoiser_last_enqueue": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "pt_debug_denoiser_conv_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "pt_debug_progressive_record": (ctypes.c_int, [_vp, _vp]),
     "pt_debug_progressive_set_active": (ctypes.c_int, [_vp, _vp]),
@@ -725,14 +730,45 @@ def denoiser_weights_check(weights):
 
 class Denoiser:
     """ctypes view of pt_denoiser: the reference's DenoiseCNN step (train.py:test, main.cu:146-152) for width x height frames.
-    weights: a PTDN file path, its bytes, or a reference-keyed state_dict."""
+    weights: a PTDN file path, its bytes, or a reference-keyed state_dict.  max_frames > 1 reserves the workspace for batches
+    of that many frames per group (pt_denoiser_reserve_frames)."""
 
-    def __init__(self, width, height, weights):
+    def __init__(self, width, height, weights, max_frames=1):
         blob = denoiser_weights_bytes(weights)
         h = _vp()
         check(lib.pt_denoiser_create(width, height, blob, len(blob), ctypes.byref(h)))
         self.handle = h.value
         self.width, self.height = width, height
+        self.max_frames = 1
+        if max_frames > 1:
+            try:
+                self.reserve_frames(max_frames)
+            except PtError:
+                self.destroy()
+                raise
+
+    def reserve_frames(self, n):
+        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
+        check(lib.pt_denoiser_reserve_frames(self.handle, n))
+        self.max_frames = max(self.max_frames, n)
+
+    def _strides(self, frame_stride_floats, rgb_stride_floats):
+        px = self.width * self.height
+        return (px * CHANNELS if frame_stride_floats is None else frame_stride_floats,
+                px * 3 if rgb_stride_floats is None else rgb_stride_floats)
+
+    def enqueue_frames(self, d_frames, n, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None, stream=None):
+        """Asynchronous; n frames at d_frames + f * frame_stride_floats (default: packed [n][H][W][14]), in place or, with d_rgb,
+        [H][W][3] at d_rgb + f * rgb_stride_floats (default packed): bit for bit n single enqueues."""
+        fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
+        check(lib.pt_denoiser_enqueue_frames(self.handle, n, d_frames, fs, d_rgb, rs, stream))
+
+    def denoise_frames(self, d_frames, n, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None):
+        """Synchronous enqueue_frames; returns device-event milliseconds."""
+        fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
+        ms = ctypes.c_float(0)
+        check(lib.pt_denoiser_denoise_frames(self.handle, n, d_frames, fs, d_rgb, rs, ctypes.byref(ms)))
+        return ms.value
 
     def enqueue(self, d_frame, d_rgb=None, stream=None):
         """Asynchronous; d_rgb None = in place on the [H][W][14] frame, else [H][W][3] into d_rgb (frame untouched)."""
@@ -779,6 +815,22 @@ class Denoiser:
     def run_conv(self, conv, d_rgb=None):
         check(lib.pt_debug_denoiser_run_conv(self.handle, conv, d_rgb))
 
+    def last_enqueue(self):
+        """(groups, kernel launches) of the last enqueue (pt_debug_denoiser_last_enqueue)."""
+        g, n = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib.pt_debug_denoiser_last_enqueue(self.handle, ctypes.byref(g), ctypes.byref(n)))
+        return g.value, n.value
+
+    def conv_plan(self, n_frames):
+        """[info dict] of every convolution in the plan of a group of n_frames frames (pt_debug_denoiser_conv_plan)."""
+        info = (ctypes.c_int * 6)()
+        keys = ("M", "bm", "bn", "splits", "chunks_per_split", "workgroups")
+        out = []
+        for i in range(len(self.convs())):
+            check(lib.pt_debug_denoiser_conv_plan(self.handle, n_frames, i, info))
+            out.append(dict(zip(keys, list(info))))
+        return out
+
     def destroy(self):
         if self.handle:
             check(lib.pt_denoiser_destroy(self.handle))
@@ -805,6 +857,27 @@ def denoise_frame(frame, weights, out_of_place=False, denoiser=None):
         return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
     finally:
         d_frame.free()
+        if d_rgb:
+            d_rgb.free()
+        if denoiser is None:
+            dn.destroy()
+
+
+def denoise_frames(frames, weights, out_of_place=False, denoiser=None):
+    """The batched twin of denoise_frame: host frames [N][H][W][14] through ONE pt_denoiser_denoise_frames call (a denoiser
+    reserved for all N frames unless one is given).  Returns the frames after the in-place step, or (frames untouched,
+    rgb [N][H][W][3]) with out_of_place=True."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    n, h, w = frames.shape[:3]
+    dn = denoiser or Denoiser(w, h, weights, max_frames=n)
+    d_frames = DeviceBuffer(frames.nbytes).upload(frames)
+    d_rgb = DeviceBuffer(n * h * w * 12) if out_of_place else None
+    try:
+        dn.denoise_frames(d_frames.ptr, n, d_rgb=d_rgb.ptr if d_rgb else None)
+        f = d_frames.download(np.float32, frames.shape)
+        return (f, d_rgb.download(np.float32, (n, h, w, 3))) if out_of_place else f
+    finally:
+        d_frames.free()
         if d_rgb:
             d_rgb.free()
         if denoiser is None:

@@ -3,7 +3,8 @@
 // Design and numbers: DENOISER.md.  Kernels: the two pre-processing kernels (channel maxima, then the divisions and the
 // channel-padded NHWC copy), ONE implicit-GEMM convolution template (compile-time tile shape, run-time epilogue kind) and the
 // deterministic split-K reduction that applies the same epilogue.  Host side: the PTDN weight loader, the layer table and the
-// workspace, all fixed at create time for the denoiser's width and height.
+// workspace, fixed at create time for the denoiser's width and height and grown by pt_denoiser_reserve_frames for batches:
+// a batch of n frames runs through the same launches as one frame, its rows m = (frame, pixel) (DENOISER.md, "Batches").
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -30,9 +31,12 @@ constexpr int BK = 16;              // K per staged chunk (every stored Cin is a
 constexpr int XC = 16;              // channels of the padded input copy (14 + 2 zeros)
 constexpr int PRE_BLOCKS = 256;     // partial maxima of the pre-processing reduction
 constexpr float KEPS = 0.00316f;    // train.py:48-55, model.py forward
+constexpr int64_t MAX_BATCH_PIXELS = (int64_t)1 << 26;  // max_frames x width x height: every row index m stays inside int32
+constexpr int MAX_FRAMES = 65535;                        // frames of one group: gridDim.y of the pre-processing kernels
 
+// Rows m = f * out_h * out_w + pixel over the `frames` frames of a group; every activation is [frames][h][w][c], contiguous.
 struct ConvArgs {
-  const float* in;  // NHWC [in_h][in_w][cin]
+  const float* in;  // NHWC [frames][in_h][in_w][cin]
   int in_h, in_w, cin;
   const float* wt;  // [K][npad], row k = (ky * ks + kx) * cin + c
   int npad, ks, stride;
@@ -51,7 +55,12 @@ struct ConvArgs {
   const float* up;    // EPI_LAT: the coarser map [up_h][up_w][32], bilinearly upsampled (align_corners) and added
   int up_h, up_w, out_h;
   const float* x0;    // EPI_RGB: the pre-processed input (albedo = channels 6-8)
+  int frames, out_hw; // frames of the group (M = frames * out_hw)
+  size_t frame_stride; // EPI_RGB: floats from one frame's output to the next (out0 + f * frame_stride + pixel * ld0)
 };
+
+// The frame of row m and the row's pixel inside it (one frame: no division).
+__device__ __forceinline__ int frame_of(const ConvArgs& a, int m) { return a.frames > 1 ? m / a.out_hw : 0; }
 
 // ReLU that returns +0 for every non-positive input (torch: x <= 0 -> 0)
 __device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
@@ -60,8 +69,8 @@ __device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
 // coordinate is formed EXACTLY (integer quotient and remainder; weight = remainder / (out - 1), one rounding) rather than as
 // torch's float32 scale * index, whose rounding moves a sample by up to an ulp of the coordinate (DENOISER.md); the
 // interpolation itself is THNN's: h0 (w0 x00 + w1 x01) + h1 (w0 x10 + w1 x11).
-__device__ __forceinline__ float upsample(const ConvArgs& a, int m, int n) {
-  const int oy = m / a.out_w, ox = m - oy * a.out_w;
+__device__ __forceinline__ float upsample(const ConvArgs& a, int f, int pix, int n) {
+  const int oy = pix / a.out_w, ox = pix - oy * a.out_w;
   int h1 = 0, w1 = 0;
   float h1l = 0.0f, w1l = 0.0f;
   if (a.out_h > 1) {
@@ -76,29 +85,36 @@ __device__ __forceinline__ float upsample(const ConvArgs& a, int m, int n) {
   }
   const int hp = h1 < a.up_h - 1 ? 1 : 0, wp = w1 < a.up_w - 1 ? 1 : 0;
   const float h0l = 1.0f - h1l, w0l = 1.0f - w1l;
-  const float* p = a.up + ((size_t)h1 * a.up_w + w1) * 32 + n;
+  const float* p = a.up + ((size_t)(f * a.up_h + h1) * a.up_w + w1) * 32 + n;
   const size_t dy = (size_t)hp * a.up_w * 32, dx = (size_t)wp * 32;
   return h0l * (w0l * p[0] + w1l * p[dx]) + h1l * (w0l * p[dy] + w1l * p[dy + dx]);
 }
 
+// conv, ReLU, folded BN (ResBlock: model.py:20-30), + residual (conv2)
+__device__ __forceinline__ void epilogue_act(const ConvArgs& a, int m, int n, float acc) {
+  float v = __builtin_fmaf(relu(acc + a.bias[n]), a.scale[n], a.shift[n]);
+  if (n < a.nsplit) {
+    const size_t o = (size_t)m * a.ld0 + n;
+    if (a.res) v = v + a.res[o];
+    a.out0[o] = v;
+  } else {
+    a.out1[(size_t)m * a.ld1 + (n - a.nsplit)] = v;
+  }
+}
+
 // The fused epilogue of every layer (m < M, n < N).
 __device__ __forceinline__ void epilogue(const ConvArgs& a, int m, int n, float acc) {
-  if (a.epi == EPI_ACT) {  // conv, ReLU, folded BN (ResBlock: model.py:20-30), + residual (conv2)
-    float v = __builtin_fmaf(relu(acc + a.bias[n]), a.scale[n], a.shift[n]);
-    if (n < a.nsplit) {
-      const size_t o = (size_t)m * a.ld0 + n;
-      if (a.res) v = v + a.res[o];
-      a.out0[o] = v;
-    } else {
-      a.out1[(size_t)m * a.ld1 + (n - a.nsplit)] = v;
-    }
+  if (a.epi == EPI_ACT) {
+    epilogue_act(a, m, n, acc);
   } else if (a.epi == EPI_LAT) {  // upsample(rep) + ReLU(lat_k(raw_k)), model.py:72-74
     const float v = relu(acc + a.bias[n]);
-    a.out0[(size_t)m * a.ld0 + n] = upsample(a, m, n) + v;
+    const int f = frame_of(a, m);
+    a.out0[(size_t)m * a.ld0 + n] = upsample(a, f, m - f * a.out_hw, n) + v;
   } else {  // rgb head: clamp(rgb_conv(rep) * (0.00316 + albedo), 0, 1), model.py:101-103
     float v = acc + a.bias[n];
     v = v * (KEPS + a.x0[(size_t)m * XC + 6 + n]);
-    a.out0[(size_t)m * a.ld0 + n] = fminf(fmaxf(v, 0.0f), 1.0f);
+    const int f = frame_of(a, m);
+    a.out0[(size_t)f * a.frame_stride + (size_t)(m - f * a.out_hw) * a.ld0 + n] = fminf(fmaxf(v, 0.0f), 1.0f);
   }
 }
 
@@ -107,7 +123,8 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, int m, int n, float 
 // half 0 and k = 8 + kk from lane half 1, so a lane's A operands for the whole chunk are 8 CONSECUTIVE channels of its pixel --
 // two float4 loads straight from the NHWC activation, no LDS (no other wave reads those rows).  The B chunk (weights) is
 // shared by the 4 waves and double-buffered in LDS.  blockIdx.z = split-K slice (partials to a.partial, summed in order by
-// splitk_reduce_kernel: deterministic, no atomics).
+// splitk_reduce_kernel: deterministic, no atomics).  Rows run over the group's frames: a window is zero-padded at its own
+// frame's borders (iy is checked against in_h before the frame's first input row iyb is added).
 template <int TM, int TN, int WM, int WN>
 __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
   static_assert(WM * WN == 4, "four waves");
@@ -124,14 +141,16 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
   const int c_end = min(a.nchunks, c_begin + a.chunks_per_split);
   const int pad = a.ks >> 1;
 
-  int iy0[TM], ix0[TM];
+  int iy0[TM], ix0[TM], iyb[TM];
   bool mv[TM];
 #pragma unroll
   for (int i = 0; i < TM; i++) {
     const int m = m0 + i * 32 + r;
     mv[i] = m < a.M;
     const int mm = mv[i] ? m : 0;
-    const int oy = mm / a.out_w, ox = mm - oy * a.out_w;
+    const int f = frame_of(a, mm), pix = mm - f * a.out_hw;
+    const int oy = pix / a.out_w, ox = pix - oy * a.out_w;
+    iyb[i] = f * a.in_h;
     iy0[i] = oy * a.stride - pad;
     ix0[i] = ox * a.stride - pad;
   }
@@ -145,7 +164,7 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
       const int iy = iy0[i] + ky_, ix = ix0[i] + kx_;                                                             \
       float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;                                                   \
       if (mv[i] && (unsigned)iy < (unsigned)a.in_h && (unsigned)ix < (unsigned)a.in_w) {                          \
-        const float4* p_ = reinterpret_cast<const float4*>(a.in + ((size_t)iy * a.in_w + ix) * a.cin + ch_);      \
+        const float4* p_ = reinterpret_cast<const float4*>(a.in + ((size_t)(iyb[i] + iy) * a.in_w + ix) * a.cin + ch_); \
         v0 = p_[0];                                                                                               \
         v1 = p_[1];                                                                                               \
       }                                                                                                           \
@@ -229,6 +248,8 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
         if (m >= a.M) continue;
         if (a.partial)
           a.partial[((size_t)split * a.M + m) * a.npad + n] = acc[i][j][e];
+        else if (BN > 32)  // wide tiles only serve affine layers (N > 32; launch_conv checks)
+          epilogue_act(a, m, n, acc[i][j][e]);
         else
           epilogue(a, m, n, acc[i][j][e]);
       }
@@ -245,8 +266,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(ConvArgs a, int spli
   epilogue(a, m, n, s);
 }
 
-// Pre-processing 1/2 (train.py:50-54): per-block maxima of channels 9-13 (a max is exact in any order).
-__global__ void __launch_bounds__(256) pre_max_kernel(const float* __restrict__ frame, uint32_t pixels, float* __restrict__ part) {
+// Pre-processing 1/2 (train.py:50-54): per-block maxima of channels 9-13 (a max is exact in any order).  blockIdx.y = frame
+// of the group (frames frame_stride floats apart), part[frame][block][5]: every frame gets its own maxima.
+__global__ void __launch_bounds__(256) pre_max_kernel(const float* __restrict__ frames, size_t frame_stride, uint32_t pixels,
+                                                     float* __restrict__ part) {
+  const float* frame = frames + blockIdx.y * frame_stride;
   float mx[5];
 #pragma unroll
   for (int k = 0; k < 5; k++) mx[k] = -INFINITY;
@@ -264,26 +288,27 @@ __global__ void __launch_bounds__(256) pre_max_kernel(const float* __restrict__ 
   __syncthreads();
   if (threadIdx.x < 5) {
     const int k = threadIdx.x;
-    part[blockIdx.x * 5 + k] = fmaxf(fmaxf(wmx[0][k], wmx[1][k]), fmaxf(wmx[2][k], wmx[3][k]));
+    part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 5 + k] = fmaxf(fmaxf(wmx[0][k], wmx[1][k]), fmaxf(wmx[2][k], wmx[3][k]));
   }
 }
 
 // Pre-processing 2/2 (train.py:48-55): colour / (0.00316 + albedo); channel k of 9-13 / (float)(0.00316 + (double)max_k) --
 // the divisor of torch 0.2/0.3, whose torch.max(t) returned a Python float.  Writes the 16-channel NHWC copy the network
 // reads (channels 14, 15 = 0) and, in place, the normalised channels 9-13 back into the frame (channels 3-8 are unchanged,
-// 0-2 are overwritten by the rgb head).
-__global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ frame, uint32_t pixels, const float* __restrict__ part,
-                                                       int nparts, float* __restrict__ x0, int inplace) {
+// 0-2 are overwritten by the rgb head).  blockIdx.y = frame of the group, divided by its own maxima; x0 is [frame][pixel][16].
+__global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ frames, size_t frame_stride, uint32_t pixels,
+                                                       const float* __restrict__ part, int nparts, float* __restrict__ x0, int inplace) {
   __shared__ float div[5];
   if (threadIdx.x < 5) {
     float m = -INFINITY;
-    for (int b = 0; b < nparts; b++) m = fmaxf(m, part[b * 5 + threadIdx.x]);
+    const float* fp = part + (size_t)blockIdx.y * nparts * 5;
+    for (int b = 0; b < nparts; b++) m = fmaxf(m, fp[b * 5 + threadIdx.x]);
     div[threadIdx.x] = (float)(0.00316 + (double)m);
   }
   __syncthreads();
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p >= pixels) return;
-  float* c = frame + (size_t)p * 14;
+  float* c = frames + blockIdx.y * frame_stride + (size_t)p * 14;
   float v[XC];
 #pragma unroll
   for (int k = 0; k < 14; k++) v[k] = c[k];
@@ -292,7 +317,7 @@ __global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ fram
 #pragma unroll
   for (int k = 0; k < 5; k++) v[9 + k] = v[9 + k] / div[k];
   v[14] = v[15] = 0.0f;
-  float4* o = reinterpret_cast<float4*>(x0 + (size_t)p * XC);
+  float4* o = reinterpret_cast<float4*>(x0 + ((size_t)blockIdx.y * pixels + p) * XC);
 #pragma unroll
   for (int q = 0; q < 4; q++) o[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
   if (inplace)
@@ -414,7 +439,7 @@ static float ld_f32(const Tensor& t, size_t i) {
 struct Act {
   std::string name;
   int h, w, c;
-  size_t off;  // floats into the workspace
+  size_t off;  // floats into the workspace: [max_frames][h][w][c], frame 0 first
 };
 
 struct Conv {
@@ -446,8 +471,12 @@ struct pt_denoiser {
   float* d_premax = nullptr;
   size_t ws_floats = 0, w_floats = 0, partial_floats = 0;
   int pre_blocks = 0;
+  int max_frames = 1;                         // frames per group (pt_denoiser_reserve_frames)
+  std::map<int, std::vector<Conv>> plans;     // batch_plan of each group size used so far
+  int last_groups = 0, last_launches = 0;     // of the last enqueue (lab getter)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
+
 
 #define PTDN_HIP(call)                                                                           \
   do {                                                                                           \
@@ -457,18 +486,23 @@ struct pt_denoiser {
                      hipGetErrorString(e_), __FILE__, __LINE__);                                 \
   } while (0)
 
+static int64_t conv_tiles(const Conv& c, int cfg) {
+  const int bn = kCfg[cfg].bn;
+  return (int64_t)((c.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((c.N + bn - 1) / bn);
+}
+
+static int pick_cfg(const Conv& c) {
+  if (c.N <= 32) return conv_tiles(c, 0) >= 256 ? 0 : 3;
+  if (c.N <= 64) return conv_tiles(c, 1) >= 128 ? 1 : 4;
+  return conv_tiles(c, 2) >= 256 ? 2 : 4;
+}
+
 static void choose_tiles(Conv& c) {
-  auto tiles = [&](int cfg) {
-    const int bn = kCfg[cfg].bn;
-    return (int64_t)((c.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((c.N + bn - 1) / bn);
-  };
-  if (c.N <= 32) c.cfg = tiles(0) >= 256 ? 0 : 3;
-  else if (c.N <= 64) c.cfg = tiles(1) >= 128 ? 1 : 4;
-  else c.cfg = tiles(2) >= 256 ? 2 : 4;
+  c.cfg = pick_cfg(c);
   c.npad = (c.N + kCfg[c.cfg].bn - 1) / kCfg[c.cfg].bn * kCfg[c.cfg].bn;
   c.nchunks = c.K / BK;
   // split K until about two workgroups per CU are in flight, keeping at least 8 chunks (128 of K) per slice
-  const int64_t t = tiles(c.cfg);
+  const int64_t t = conv_tiles(c, c.cfg);
   int splits = 1;
   if (t < 256) {
     splits = (int)((512 + t - 1) / t);
@@ -532,20 +566,43 @@ static void build_layers(pt_denoiser* d) {
     rep = nr;
   }
   conv("rgb_conv", rep, 3, 1, 3, EPI_RGB, -1, 3, -1, -1, -1);
-  size_t off = 0;
-  for (Act& a : d->acts) {
-    a.off = off;
-    off += ((size_t)a.h * a.w * a.c + 63) / 64 * 64;  // 256-byte aligned
-  }
-  d->ws_floats = off;
-  size_t woff = 0, pmax = 0;
+  size_t woff = 0;
   for (Conv& c : d->convs) {
     c.w_off = woff;
     woff += ((size_t)c.K * c.npad + 3 * (size_t)c.npad + 63) / 64 * 64;
-    if (c.splits > 1 && (size_t)c.splits * c.M * c.npad > pmax) pmax = (size_t)c.splits * c.M * c.npad;
   }
   d->w_floats = woff;
-  d->partial_floats = pmax;
+}
+
+// The conv table of a group of n frames, from the single-frame table: M = n rows per output pixel, the tile shape re-chosen
+// for that M (same column padding), the K slicing KEPT.  An output element's value depends only on the slicing of K and on
+// the fixed chunk-by-chunk MFMA chain, not on the tile shape, so every frame of the group gets the bits of a single enqueue.
+static std::vector<Conv> batch_plan(const std::vector<Conv>& single, int n) {
+  std::vector<Conv> out = single;
+  if (n == 1) return out;
+  for (Conv& c : out) {
+    c.M = n * c.out_h * c.out_w;
+    const int cfg = pick_cfg(c);
+    if (c.npad % kCfg[cfg].bn == 0) c.cfg = cfg;  // the weights are stored with the single-frame column padding
+  }
+  return out;
+}
+
+// Workspace offsets of every activation for groups of up to `frames` frames; returns the workspace floats.
+static size_t layout_acts(std::vector<Act>& acts, int frames) {
+  size_t off = 0;
+  for (Act& a : acts) {
+    a.off = off;
+    off += ((size_t)frames * a.h * a.w * a.c + 63) / 64 * 64;  // 256-byte aligned
+  }
+  return off;
+}
+
+static size_t partial_floats_of(const std::vector<Conv>& plan) {
+  size_t pmax = 0;
+  for (const Conv& c : plan)
+    if (c.splits > 1 && (size_t)c.splits * c.M * c.npad > pmax) pmax = (size_t)c.splits * c.M * c.npad;
+  return pmax;
 }
 
 // Host image of the device weight buffer: per conv wt [K][npad] (k = (ky ks + kx) Cin_stored + c), bias, scale, shift.
@@ -598,7 +655,14 @@ static void fill_weights(const pt_denoiser* d, const std::map<std::string, Tenso
   }
 }
 
-static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld) {
+static const std::vector<Conv>& plan_for(pt_denoiser* d, int n) {
+  if (n == 1) return d->convs;
+  auto it = d->plans.find(n);
+  if (it == d->plans.end()) it = d->plans.emplace(n, batch_plan(d->convs, n)).first;
+  return it->second;
+}
+
+static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
   ConvArgs a{};
   const Act& in = d->acts[c.in];
   a.in = d->d_ws + in.off;
@@ -630,11 +694,17 @@ static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out,
     a.up_h = d->acts[c.up].h, a.up_w = d->acts[c.up].w;
   }
   a.x0 = d->d_ws + d->acts[0].off;
+  a.frames = frames, a.out_hw = c.out_h * c.out_w;
+  a.frame_stride = frame_stride;
   return a;
 }
 
-static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, hipStream_t s) {
-  const ConvArgs a = conv_args(d, c, frame_out, frame_ld);
+// One conv of a group of `frames` frames (c from that group size's plan): its GEMM and, split, its reduction.
+static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames,
+                       hipStream_t s, int* launches) {
+  if (c.epi != EPI_ACT && kCfg[c.cfg].bn != 32)
+    return pt_fail(PT_EINVAL, "launch_conv: %s: the lateral and head epilogues need 32-column tiles", c.name.c_str());
+  const ConvArgs a = conv_args(d, c, frame_out, frame_ld, frame_stride, frames);
   const dim3 grid((c.M + kCfg[c.cfg].bm - 1) / kCfg[c.cfg].bm, c.npad / kCfg[c.cfg].bn, c.splits);
   switch (c.cfg) {
     case 0: hipLaunchKernelGGL((conv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
@@ -644,10 +714,12 @@ static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, in
     default: hipLaunchKernelGGL((conv_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
   }
   PTDN_HIP(hipGetLastError());
+  (*launches)++;
   if (c.splits > 1) {
     const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
     PTDN_HIP(hipGetLastError());
+    (*launches)++;
   }
   return PT_OK;
 }
@@ -687,6 +759,8 @@ int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt
   if (!d) return pt_fail(PT_ENOMEM, "pt_denoiser_create: out of host memory");
   d->width = width, d->height = height;
   build_layers(d);
+  d->ws_floats = layout_acts(d->acts, 1);
+  d->partial_floats = partial_floats_of(d->convs);
   std::vector<float> w;
   fill_weights(d, t, w);
   d->pre_blocks = (int)(((uint64_t)width * height + 255) / 256);
@@ -721,19 +795,97 @@ int pt_denoiser_create_from_file(int width, int height, const char* path, pt_den
   return pt_denoiser_create(width, height, buf.data(), buf.size(), out);
 }
 
+int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: null denoiser");
+  if (max_frames < 1) return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d < 1", max_frames);
+  if (max_frames <= d->max_frames) return PT_OK;
+  const int64_t px = (int64_t)max_frames * d->width * d->height;
+  if (max_frames > MAX_FRAMES || px > MAX_BATCH_PIXELS)
+    return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
+                   max_frames, d->width, d->height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
+  const std::vector<Conv> plan = batch_plan(d->convs, max_frames);
+  for (const Conv& c : plan)  // splitk_reduce_kernel indexes M x N elements in 32 bits
+    if ((int64_t)c.M * c.N > (int64_t)UINT32_MAX)
+      return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d: layer %s has too many elements", max_frames, c.name.c_str());
+  std::vector<Act> acts = d->acts;
+  const size_t ws_floats = layout_acts(acts, max_frames);
+  const size_t partial_floats = partial_floats_of(plan);
+  float *ws = nullptr, *partial = nullptr, *premax = nullptr;
+  hipError_t e = hipMalloc((void**)&ws, ws_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(ws, 0, ws_floats * sizeof(float));
+  if (e == hipSuccess && partial_floats) e = hipMalloc((void**)&partial, partial_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&premax, (size_t)max_frames * PRE_BLOCKS * 5 * sizeof(float));
+  if (e == hipSuccess) e = hipDeviceSynchronize();  // the old buffers may still be in use by enqueued work
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (ws) (void)hipFree(ws);
+    if (partial) (void)hipFree(partial);
+    if (premax) (void)hipFree(premax);
+    return pt_fail(PT_EHIP, "pt_denoiser_reserve_frames: %d frames (%zu + %zu workspace floats): %s; the old workspace is kept",
+                   max_frames, ws_floats, partial_floats, hipGetErrorString(e));
+  }
+  (void)hipFree(d->d_ws);
+  if (d->d_partial) (void)hipFree(d->d_partial);
+  (void)hipFree(d->d_premax);
+  d->d_ws = ws, d->d_partial = partial, d->d_premax = premax;
+  d->acts = acts;
+  d->ws_floats = ws_floats, d->partial_floats = partial_floats;
+  d->max_frames = max_frames;
+  return PT_OK;
+}
+
+int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                               size_t rgb_stride_floats, void* hip_stream) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: null denoiser");
+  d->last_groups = d->last_launches = 0;
+  if (!d_frames) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: null d_frames");
+  if (n_frames < 1) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: n_frames %d < 1", n_frames);
+  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
+  if (frame_stride_floats < (size_t)pixels * 14)
+    return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: frame_stride_floats %zu < width x height x 14 = %zu", frame_stride_floats,
+                   (size_t)pixels * 14);
+  if (d_rgb && rgb_stride_floats < (size_t)pixels * 3)
+    return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: rgb_stride_floats %zu < width x height x 3 = %zu", rgb_stride_floats,
+                   (size_t)pixels * 3);
+  hipStream_t s = (hipStream_t)hip_stream;
+  float* x0 = d->d_ws + d->acts[0].off;
+  for (int f0 = 0; f0 < n_frames; f0 += d->max_frames) {
+    const int g = n_frames - f0 < d->max_frames ? n_frames - f0 : d->max_frames;
+    float* frames = d_frames + (size_t)f0 * frame_stride_floats;
+    float* out = d_rgb ? d_rgb + (size_t)f0 * rgb_stride_floats : frames;
+    hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks, g), dim3(256), 0, s, frames, frame_stride_floats, pixels, d->d_premax);
+    PTDN_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
+                       d->d_premax, d->pre_blocks, x0, d_rgb ? 0 : 1);
+    PTDN_HIP(hipGetLastError());
+    d->last_launches += 2;
+    for (const Conv& c : plan_for(d, g)) {
+      const int rc = launch_conv(d, c, out, d_rgb ? 3 : 14, d_rgb ? rgb_stride_floats : frame_stride_floats, g, s, &d->last_launches);
+      if (rc != PT_OK) return rc;
+    }
+    d->last_groups++;
+  }
+  return PT_OK;
+}
+
+// One frame = a group of one: the single-frame table, the launches and the bits of the original single-frame path.
 int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_stream) {
   if (!d || !d_frame) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue: null denoiser or frame");
-  hipStream_t s = (hipStream_t)hip_stream;
-  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
-  hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks), dim3(256), 0, s, d_frame, pixels, d->d_premax);
-  PTDN_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256), dim3(256), 0, s, d_frame, pixels, d->d_premax, d->pre_blocks,
-                     d->d_ws + d->acts[0].off, d_rgb ? 0 : 1);
-  PTDN_HIP(hipGetLastError());
-  for (const Conv& c : d->convs) {
-    const int rc = launch_conv(d, c, d_rgb ? d_rgb : d_frame, d_rgb ? 3 : 14, s);
-    if (rc != PT_OK) return rc;
-  }
+  const size_t pixels = (size_t)d->width * d->height;
+  return pt_denoiser_enqueue_frames(d, 1, d_frame, pixels * 14, d_rgb, pixels * 3, hip_stream);
+}
+
+int pt_denoiser_denoise_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                               size_t rgb_stride_floats, float* ms_out) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_denoise_frames: null denoiser");
+  PTDN_HIP(hipEventRecord(d->ev0, nullptr));
+  const int rc = pt_denoiser_enqueue_frames(d, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, nullptr);
+  if (rc != PT_OK) return rc;
+  PTDN_HIP(hipEventRecord(d->ev1, nullptr));
+  PTDN_HIP(hipEventSynchronize(d->ev1));
+  float ms = 0.0f;
+  PTDN_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+  if (ms_out) *ms_out = ms;
   return PT_OK;
 }
 
@@ -800,9 +952,31 @@ int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
   if (!d || conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: bad arguments");
   const Conv& c = d->convs[conv];
   if (c.out0 < 0 && !d_rgb) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: the rgb head needs an output buffer");
-  const int rc = launch_conv(d, c, d_rgb, 3, nullptr);
+  int launches = 0;
+  const int rc = launch_conv(d, c, d_rgb, 3, 0, 1, nullptr, &launches);
   if (rc != PT_OK) return rc;
   PTDN_HIP(hipDeviceSynchronize());
+  return PT_OK;
+}
+
+int pt_debug_denoiser_last_enqueue(pt_denoiser* d, int* groups, int* launches) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_last_enqueue: null denoiser");
+  if (groups) *groups = d->last_groups;
+  if (launches) *launches = d->last_launches;
+  return PT_OK;
+}
+
+int pt_debug_denoiser_conv_plan(pt_denoiser* d, int n_frames, int conv, int info[6]) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: null denoiser");
+  if (n_frames < 1 || n_frames > MAX_FRAMES || (int64_t)n_frames * d->width * d->height > MAX_BATCH_PIXELS)
+    return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: n_frames %d outside the batch limits", n_frames);
+  if (conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: no conv %d", conv);
+  const Conv& c = plan_for(d, n_frames)[conv];
+  if (info) {
+    const int64_t wg = (int64_t)((c.M + kCfg[c.cfg].bm - 1) / kCfg[c.cfg].bm) * (c.npad / kCfg[c.cfg].bn) * c.splits;
+    const int v[6] = {c.M, kCfg[c.cfg].bm, kCfg[c.cfg].bn, c.splits, c.chunks_per_split, (int)wg};
+    memcpy(info, v, sizeof(v));
+  }
   return PT_OK;
 }
 #endif

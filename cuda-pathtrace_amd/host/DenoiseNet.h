@@ -4,6 +4,8 @@
 // Errors print the GPUassert line and exit, like every look-alike class.
 #ifndef DENOISENET_H
 #define DENOISENET_H
+#include <stddef.h>
+
 #include <string>
 
 #include "HipErrorCheck.h"
@@ -17,9 +19,11 @@ class DenoiseNet {
   DenoiseNet& operator=(const DenoiseNet&);
 
  public:
-  // load_pretrained + .eval() for width x height frames; weights = a PTDN file (cuda-pathtrace_amd/denoise_weights.py)
-  DenoiseNet(int width, int height, const std::string& weights) : net(NULL), width(width), height(height) {
+  // load_pretrained + .eval() for width x height frames; weights = a PTDN file (cuda-pathtrace_amd/denoise_weights.py).
+  // maxFrames > 1: workspace for batches of that many frames per group (DenoiseFrames / EnqueueFrames).
+  DenoiseNet(int width, int height, const std::string& weights, int maxFrames = 1) : net(NULL), width(width), height(height) {
     gpuErrchk(pt_denoiser_create_from_file(width, height, weights.c_str(), &net));
+    if (maxFrames > 1) gpuErrchk(pt_denoiser_reserve_frames(net, maxFrames));
   }
   ~DenoiseNet() { (void)pt_denoiser_destroy(net); }
 
@@ -31,5 +35,17 @@ class DenoiseNet {
   }
   // asynchronous on a HIP stream (NULL = default); d_rgb != NULL: [H][W][3] result there, frame untouched
   void Enqueue(float* d_frame, float* d_rgb, void* hip_stream) { gpuErrchk(pt_denoiser_enqueue(net, d_frame, d_rgb, hip_stream)); }
+
+  // n device frames strideFloats apart (e.g. the buffer of Renderer::RenderFrames), each in place, bit for bit n Denoise
+  // calls; returns device-event milliseconds for all of them
+  float DenoiseFrames(float* d_frames, int n, size_t strideFloats) {
+    float ms = 0.0f;
+    gpuErrchk(pt_denoiser_denoise_frames(net, n, d_frames, strideFloats, NULL, 0, &ms));
+    return ms;
+  }
+  // asynchronous batch; d_rgb != NULL: [H][W][3] results rgbStrideFloats apart, frames untouched
+  void EnqueueFrames(float* d_frames, int n, size_t strideFloats, float* d_rgb, size_t rgbStrideFloats, void* hip_stream) {
+    gpuErrchk(pt_denoiser_enqueue_frames(net, n, d_frames, strideFloats, d_rgb, rgbStrideFloats, hip_stream));
+  }
 };
 #endif

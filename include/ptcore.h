@@ -306,6 +306,24 @@ int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_
 /* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around the
  * network, like Renderer::Render (Renderer.h:63-75). */
 int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out);
+/* Batches.  pt_denoiser_enqueue_frames(d, n, d_frames, frame_stride, d_rgb, rgb_stride, s) does, bit for bit, what
+ *   for f in 0 .. n-1: pt_denoiser_enqueue(d, d_frames + f * frame_stride, d_rgb ? d_rgb + f * rgb_stride : NULL, s)
+ * does: every frame is pre-processed with its own channel maxima, in place (d_rgb == NULL) or out of place (frames untouched).
+ * Frames go through the network in groups of up to max_frames (1 unless reserved), each group in the launches of ONE frame:
+ * its frames are rows of the same GEMMs, with each layer's split of K kept from the single-frame plan (DENOISER.md, "Batches").
+ * Strides are in floats: frame_stride >= width x height x 14, rgb_stride >= width x height x 3 when d_rgb is given, so the
+ * strided output of pt_renderer_enqueue_frames can be passed straight in.  n_frames >= 1; any other value, a null denoiser
+ * or null frames is PT_EINVAL naming the argument, and nothing is launched.  Asynchronous on hip_stream (NULL = default).
+ * pt_denoiser_reserve_frames grows the workspace (about 114 MB per 512x512 frame plus the split-K partials) for groups of up
+ * to max_frames frames; max_frames <= the current value is a no-op.  Limits: max_frames <= 65535 and max_frames x width x
+ * height <= 2^26 pixels (PT_EINVAL beyond).  It synchronises the device before freeing the old workspace; on failure
+ * (PT_EHIP) the old workspace stays in use. */
+int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames);
+int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                               size_t rgb_stride_floats, void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = device-event milliseconds around all the groups. */
+int pt_denoiser_denoise_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                               size_t rgb_stride_floats, float* ms_out);
 
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests

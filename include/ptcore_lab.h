@@ -64,7 +64,9 @@ int pt_debug_policy_choice(int rng_mode, double waves_per_simd, int spp, int bou
  * 0 "input" (the pre-processed frame, NHWC, 16 channels of which 14-15 are zero), "block<b>.t1" / ".res" / ".out", "lat6",
  * "back<k+1><k>", "rep<k>".  shape = {rows, cols, channels}; *n_layers = their number (also for an invalid `layer`). */
 int pt_debug_denoiser_layer_info(pt_denoiser* d, int layer, int* n_layers, int shape[3], char* name, size_t name_len);
-/* Synchronises the device and copies layer `layer` ([rows][cols][channels] floats, n_floats of them) to / from the host. */
+/* Synchronises the device and copies layer `layer` ([rows][cols][channels] floats, n_floats of them) to / from the host.  With
+ * reserved batches the workspace holds [max_frames] copies of every layer; these address the first (the frame of a
+ * single enqueue, or the first frame of the last group). */
 int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats);
 int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats);
 /* Convolution `conv` of the forward pass (execution order): info = {input layer, output layer (-1: the frame / rgb
@@ -73,6 +75,12 @@ int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_i
 int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len);
 /* Runs convolution `conv` alone on the workspace as it stands (synchronous); the rgb head writes [rows][cols][3] to d_rgb. */
 int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
+/* The last enqueue (single or batch): *groups = frame groups it made, *launches = kernels it launched (0, 0 before any). */
+int pt_debug_denoiser_last_enqueue(pt_denoiser* d, int* groups, int* launches);
+/* Convolution `conv` of the plan of a group of n_frames frames (host arithmetic; any size inside the batch limits): info =
+ * {rows M, tile rows, tile columns, split-K slices, 16-wide K chunks per slice, workgroups}.  n_frames = 1 is the single-frame
+ * table that pt_debug_denoiser_conv_info reports. */
+int pt_debug_denoiser_conv_plan(pt_denoiser* d, int n_frames, int conv, int info[6]);
 
 /* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
  * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */

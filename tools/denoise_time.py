@@ -5,8 +5,12 @@ torch's own fp32 forward of the restated network (tests/denoise_restatement.py; 
 lists every layer's shape and FLOPs (2 M N K, counted from the shapes; K with the 14 real input channels).
 
   python3 tools/denoise_time.py [--sizes 512 1024] [--runs 200] [--no-torch] [--out DIR]
-  python3 tools/denoise_time.py --trace DIR/..._kernel_trace.csv --sizes 512 --out DIR
-      per-layer kernel times from a rocprofv3 --kernel-trace run of this tool (dispatches mapped to layers in launch order)
+  python3 tools/denoise_time.py --frames 1 8 32 --sizes 128 256 512 [--out DIR]
+      batches: per-frame time of pt_denoiser_enqueue_frames of n frames (one group, max_frames = n; n = 1 is
+      pt_denoiser_enqueue), the median of device-event windows around whole batches after warm-up -> frames_time.json
+  python3 tools/denoise_time.py --trace DIR/..._kernel_trace.csv --sizes 512 [--frames 32] --out DIR
+      per-layer kernel times from a rocprofv3 --kernel-trace run of this tool (dispatches mapped to layers in launch order;
+      with --frames n, of a run with that one --frames value: every batch is one sequence of the same launches)
 """
 import argparse
 import csv
@@ -25,19 +29,21 @@ import __graft_entry__ as ge  # noqa: E402
 FLOOR_TFS = 157.3  # fp32 MFMA peak (MI355X_MICROARCH.md): 256 CUs x 4 SIMDs x 64 FLOP/clk x 2.4 GHz
 
 
-def layer_table(lab, w, h, sd):
-    """[(name, M, N, K, flops, splits, tile)] in launch order, from the lab library's conv table."""
+def layer_table(lab, w, h, sd, frames=1):
+    """[(name, M, N, K, flops, splits, tile)] in launch order, from the lab library's conv table (the plan of a group of
+    `frames` frames: M and FLOPs of the whole group)."""
     dn = lab.Denoiser(w, h, sd)
     try:
         layers = dn.layers()
+        plan = dn.conv_plan(frames)
         rows = []
-        for name, inf in dn.convs():
+        for (name, inf), p in zip(dn.convs(), plan):
             ih, iw, cin = layers[inf["in"]][1]
             cin_real = 14 if inf["in"] == 0 else cin
             oh, ow = (ih - 1) // inf["stride"] + 1, (iw - 1) // inf["stride"] + 1
-            M, N, K = oh * ow, inf["N"], inf["ks"] ** 2 * cin_real
-            rows.append(dict(name=name, M=M, N=N, K=K, flops=2.0 * M * N * K, splits=inf["splits"],
-                             tile=f'{inf["bm"]}x{inf["bn"]}'))
+            M, N, K = frames * oh * ow, inf["N"], inf["ks"] ** 2 * cin_real
+            assert M == p["M"]
+            rows.append(dict(name=name, M=M, N=N, K=K, flops=2.0 * M * N * K, splits=p["splits"], tile=f'{p["bm"]}x{p["bn"]}'))
         return rows
     finally:
         dn.destroy()
@@ -58,6 +64,40 @@ def time_hip(pt, w, h, sd, runs, warmup):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             dn.enqueue(d_frame.data_ptr(), None, s.cuda_stream)
+            e1.record(s)
+            e1.synchronize()
+            if i >= warmup:
+                times.append(e0.elapsed_time(e1))
+    finally:
+        torch.cuda.synchronize()
+        dn.destroy()
+    return np.array(times)
+
+
+def time_hip_frames(pt, w, h, sd, n, runs, warmup):
+    """Device-event ms of whole batches of n frames (n different poses) through ONE enqueue_frames call each (n = 1:
+    pt_denoiser_enqueue); every run starts from the rendered frames."""
+    import torch
+
+    frames = []
+    for k in range(n):
+        eye = (50.0 + 0.7 * k, 52.0 - 0.3 * k, 295.6 - 1.1 * k)
+        basis = pt.camera_basis(eye, yaw=-90.0 + 0.9 * k, pitch=-0.4 * k, width=w, height=h)
+        frames.append(pt.render_frame(w, h, 4, basis=basis, eye=eye)[0])
+    d_src = torch.from_numpy(np.stack(frames)).cuda()
+    d_frames = d_src.clone()
+    dn = pt.Denoiser(w, h, sd, max_frames=n)
+    s = torch.cuda.current_stream()
+    times = []
+    try:
+        for i in range(warmup + runs):
+            d_frames.copy_(d_src)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            if n == 1:
+                dn.enqueue(d_frames.data_ptr(), None, s.cuda_stream)
+            else:
+                dn.enqueue_frames(d_frames.data_ptr(), n, stream=s.cuda_stream)
             e1.record(s)
             e1.synchronize()
             if i >= warmup:
@@ -94,9 +134,16 @@ def time_torch(w, h, sd, runs, warmup):
 
 def from_trace(path, rows):
     """Median kernel time of each layer from a rocprofv3 kernel trace: per frame the two pre-processing kernels, then per
-    layer its conv kernel (+ the split-K reduction)."""
-    with open(path) as f:
-        recs = list(csv.DictReader(f))
+    layer its conv kernel (+ the split-K reduction).  path: a kernel_trace.csv or a rocpd database (*_results.db, the
+    default output of newer rocprofv3), whose `kernels` view carries the same three columns."""
+    if path.endswith(".db"):
+        import sqlite3
+
+        with sqlite3.connect(path) as db:
+            recs = [dict(Kernel_Name=n, Start_Timestamp=b, End_Timestamp=e) for n, b, e in db.execute("select name, start, end from kernels")]
+    else:
+        with open(path) as f:
+            recs = list(csv.DictReader(f))
     key_name = next(k for k in recs[0] if k.lower() in ("kernel_name", "kernelname"))
     key_s = next(k for k in recs[0] if k.lower() in ("start_timestamp", "begin_ns", "start"))
     key_e = next(k for k in recs[0] if k.lower() in ("end_timestamp", "end_ns", "end"))
@@ -132,6 +179,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--frames", type=int, nargs="+", default=None)
     a = ap.parse_args()
     if not a.trace:
         import torch
@@ -144,11 +192,14 @@ def main():
     if a.out:
         os.makedirs(a.out, exist_ok=True)
     if a.trace:
-        path = a.trace if os.path.isfile(a.trace) else sorted(glob.glob(os.path.join(a.trace, "**", "*kernel_trace.csv"), recursive=True))[-1]
+        path = a.trace if os.path.isfile(a.trace) else sorted(glob.glob(os.path.join(a.trace, "**", "*kernel_trace.csv"), recursive=True)
+                                                              + glob.glob(os.path.join(a.trace, "**", "*_results.db"), recursive=True))[-1]
         size = a.sizes[0]
-        rows = layer_table(lab, size, size, sd)
+        nf = a.frames[0] if a.frames else 1
+        rows = layer_table(lab, size, size, sd, nf)
         frames, ms = from_trace(path, rows)
-        lines = [f"per-layer kernel times at {size}x{size}, median over {frames} frames of {os.path.basename(path)}",
+        what = f"groups of {nf} frames (M, GFLOP and ms of the whole group)" if nf > 1 else "frames"
+        lines = [f"per-layer kernel times at {size}x{size}, median over {frames} {what} of {os.path.basename(path)}",
                  f"{'layer':28s} {'M':>7s} {'N':>5s} {'K':>5s} {'GFLOP':>7s} {'tile':>8s} {'split':>5s} {'ms':>8s} {'TF/s':>7s}"]
         lines.append(f"{'pre_max + pre_apply':28s} {'':>7s} {'':>5s} {'':>5s} {'':>7s} {'':>8s} {'':>5s} {ms['pre_max + pre_apply']:8.4f}")
         tot_ms, tot_fl = ms["pre_max + pre_apply"], 0.0
@@ -162,9 +213,31 @@ def main():
         text = "\n".join(lines)
         print(text)
         if a.out:
-            open(os.path.join(a.out, f"layers_{size}.txt"), "w").write(text + "\n")
+            name = f"layers_{size}.txt" if nf == 1 else f"layers_{size}_n{nf}.txt"
+            open(os.path.join(a.out, name), "w").write(text + "\n")
         return
     pt.set_device(0)
+    if a.frames:
+        res = {"device": pt.device_info()["name"], "fingerprint": pt.build_fingerprint(), "runs": a.runs, "warmup": a.warmup,
+               "weights": "denoise_weights.random_state_dict(seed=1)", "frame": "Cornell box, 4 spp, n poses",
+               "note": "ms_per_frame = median device-event window of one batch / n; n = 1 is pt_denoiser_enqueue", "sizes": {}}
+        for s in a.sizes:
+            entry = {}
+            for n in a.frames:
+                t = time_hip_frames(pt, s, s, sd, n, a.runs, a.warmup)
+                entry[str(n)] = {"batch_ms_median": float(np.median(t)), "batch_ms_min": float(t.min()),
+                                 "ms_per_frame": float(np.median(t)) / n}
+            one = entry.get("1", {}).get("ms_per_frame")
+            for n, e in entry.items():
+                if one:
+                    e["speedup_vs_single"] = one / e["ms_per_frame"]
+                print(f"{s}x{s} n={n}: batch {e['batch_ms_median']:.4f} ms, {e['ms_per_frame']:.4f} ms per frame"
+                      + (f" ({e['speedup_vs_single']:.2f}x single)" if one else ""), flush=True)
+            res["sizes"][str(s)] = entry
+        if a.out:
+            with open(os.path.join(a.out, "frames_time.json"), "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = {"device": pt.device_info()["name"], "fingerprint": pt.build_fingerprint(), "runs": a.runs, "warmup": a.warmup,
            "weights": "denoise_weights.random_state_dict(seed=1)", "frame": "Cornell box, 4 spp, default camera", "sizes": {}}
     for s in a.sizes:
