@@ -147,6 +147,9 @@ ABI = {
     "pt_denoiser_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "pt_denoiser_create_from_file": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_vp)]),
     "pt_denoiser_destroy": (ctypes.c_int, [_vp]),
+    "pt_denoiser_create_opts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _vp, ctypes.POINTER(_vp)]),
+    "pt_denoiser_create_opts_from_file": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _vp, ctypes.POINTER(_vp)]),
+    "pt_denoiser_precision": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "pt_denoiser_enqueue": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "pt_denoiser_denoise": (ctypes.c_int, [_vp, _vp, _vp, _fp]),
     "pt_denoiser_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -183,6 +186,7 @@ LAB_ABI = {
     "pt_debug_denoiser_conv_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                    ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_debug_denoiser_memory": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "pt_debug_denoiser_last_enqueue": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_denoiser_conv_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
@@ -728,24 +732,44 @@ def denoiser_weights_check(weights):
     check(lib.pt_denoiser_weights_check(blob, len(blob)))
 
 
+DENOISE_F32, DENOISE_F16 = 0, 1
+_DENOISE_PRECISIONS = {"float32": DENOISE_F32, "half": DENOISE_F16}
+
+
+class DenoiserOpts(ctypes.Structure):
+    """pt_denoiser_opts (include/ptcore.h)."""
+    _fields_ = [("precision", ctypes.c_int32), ("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+def denoise_precision(precision):
+    """PT_DENOISE_* of a precision name ("float32" or "half"); anything else is a ValueError."""
+    if precision not in _DENOISE_PRECISIONS:
+        raise ValueError(f"precision {precision!r}: 'float32' or 'half'")
+    return _DENOISE_PRECISIONS[precision]
+
+
 class Denoiser:
     """ctypes view of pt_denoiser: the reference's DenoiseCNN step (train.py:test, main.cu:146-152) for width x height frames.
     weights: a PTDN file path, its bytes, or a reference-keyed state_dict.  max_frames > 1 reserves the workspace for batches
-    of that many frames per group (pt_denoiser_reserve_frames)."""
+    of that many frames per group (pt_denoiser_reserve_frames).  precision: "float32" (the default, exact to fp32 rounding)
+    or "half" (fp16 operands and storage, fp32 accumulation: the toleranced mode of DENOISER.md, "Half precision")."""
 
-    def __init__(self, width, height, weights, max_frames=1):
+    def __init__(self, width, height, weights, max_frames=1, precision="float32"):
+        self.handle = None
+        opts = DenoiserOpts(precision=denoise_precision(precision), max_frames=max_frames)
         blob = denoiser_weights_bytes(weights)
         h = _vp()
-        check(lib.pt_denoiser_create(width, height, blob, len(blob), ctypes.byref(h)))
+        check(lib.pt_denoiser_create_opts(width, height, blob, len(blob), ctypes.byref(opts), ctypes.byref(h)))
         self.handle = h.value
         self.width, self.height = width, height
-        self.max_frames = 1
-        if max_frames > 1:
-            try:
-                self.reserve_frames(max_frames)
-            except PtError:
-                self.destroy()
-                raise
+        self.max_frames = max_frames
+
+    @property
+    def precision(self):
+        """"float32" or "half" (pt_denoiser_precision)."""
+        v = ctypes.c_int(-1)
+        check(lib.pt_denoiser_precision(self.handle, ctypes.byref(v)))
+        return {n: k for k, n in _DENOISE_PRECISIONS.items()}[v.value]
 
     def reserve_frames(self, n):
         """Workspace for groups of up to n frames (a smaller n is a no-op)."""
@@ -815,6 +839,17 @@ class Denoiser:
     def run_conv(self, conv, d_rgb=None):
         check(lib.pt_debug_denoiser_run_conv(self.handle, conv, d_rgb))
 
+    def memory(self):
+        """Bytes (pt_debug_denoiser_memory): {"element", "workspace", "partials", "weights", "layers": [(name, offset, bytes
+        of one frame)]}."""
+        info = (ctypes.c_uint64 * 6)()
+        layers = []
+        for i, (name, _) in enumerate(self.layers()):
+            check(lib.pt_debug_denoiser_memory(self.handle, i, info))
+            layers.append((name, int(info[1]), int(info[2])))
+        return {"element": int(info[0]), "workspace": int(info[3]), "partials": int(info[4]), "weights": int(info[5]),
+                "layers": layers}
+
     def last_enqueue(self):
         """(groups, kernel launches) of the last enqueue (pt_debug_denoiser_last_enqueue)."""
         g, n = ctypes.c_int(0), ctypes.c_int(0)
@@ -843,12 +878,12 @@ class Denoiser:
             pass
 
 
-def denoise_frame(frame, weights, out_of_place=False, denoiser=None):
+def denoise_frame(frame, weights, out_of_place=False, denoiser=None, precision="float32"):
     """Convenience for tests: upload a host [H][W][14] frame, denoise it on the GPU, download.  Returns the frame after the
-    in-place step, or (frame untouched, rgb [H][W][3]) with out_of_place=True."""
+    in-place step, or (frame untouched, rgb [H][W][3]) with out_of_place=True.  precision: of the denoiser made here."""
     frame = np.ascontiguousarray(frame, dtype=np.float32)
     h, w = frame.shape[:2]
-    dn = denoiser or Denoiser(w, h, weights)
+    dn = denoiser or Denoiser(w, h, weights, precision=precision)
     d_frame = DeviceBuffer(frame.nbytes).upload(frame)
     d_rgb = DeviceBuffer(h * w * 12) if out_of_place else None
     try:
@@ -863,13 +898,13 @@ def denoise_frame(frame, weights, out_of_place=False, denoiser=None):
             dn.destroy()
 
 
-def denoise_frames(frames, weights, out_of_place=False, denoiser=None):
+def denoise_frames(frames, weights, out_of_place=False, denoiser=None, precision="float32"):
     """The batched twin of denoise_frame: host frames [N][H][W][14] through ONE pt_denoiser_denoise_frames call (a denoiser
     reserved for all N frames unless one is given).  Returns the frames after the in-place step, or (frames untouched,
     rgb [N][H][W][3]) with out_of_place=True."""
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
-    dn = denoiser or Denoiser(w, h, weights, max_frames=n)
+    dn = denoiser or Denoiser(w, h, weights, max_frames=n, precision=precision)
     d_frames = DeviceBuffer(frames.nbytes).upload(frames)
     d_rgb = DeviceBuffer(n * h * w * 12) if out_of_place else None
     try:

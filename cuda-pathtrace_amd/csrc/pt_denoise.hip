@@ -1,5 +1,6 @@
 // pt_denoise.hip -- the reference's denoising network (DenoiseCNN, denoise_cnn/model.py, run by train.py:test() from the
-// interactive loop, src/main.cu:92-122,146-152) as fp32 MFMA inference behind pt_denoiser_* (include/ptcore.h).
+// interactive loop, src/main.cu:92-122,146-152) as fp32 MFMA inference behind pt_denoiser_* (include/ptcore.h), and, opt-in
+// (PT_DENOISE_F16), the same network on fp16 operands and storage with fp32 accumulation (pt_denoise_half.h).
 // Design and numbers: DENOISER.md.  Kernels: the two pre-processing kernels (channel maxima, then the divisions and the
 // channel-padded NHWC copy), ONE implicit-GEMM convolution template (compile-time tile shape, run-time epilogue kind) and the
 // deterministic split-K reduction that applies the same epilogue.  Host side: the PTDN weight loader, the layer table and the
@@ -325,6 +326,8 @@ __global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ fram
     for (int k = 0; k < 5; k++) c[9 + k] = v[9 + k];
 }
 
+#include "pt_denoise_half.h"
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 const int kChannels[7] = {14, 32, 64, 128, 256, 512, 1024};
 
@@ -448,7 +451,9 @@ struct Conv {
   int cin, ks, stride, N, nsplit, epi;
   int in_h, in_w, out_h, out_w, M, K;
   int cfg, npad, splits, chunks_per_split, nchunks;
-  size_t w_off;  // floats into the weight buffer: wt [K][npad], bias, scale, shift [npad] each
+  size_t w_off;  // floats into the host weight image: wt [K][npad], bias, scale, shift [npad] each
+  size_t p_off;  // floats into d_w: bias, scale, shift (fp32 mode: w_off + K * npad, behind wt; half mode: packed)
+  size_t h_off;  // half mode: halves into d_wh, wt [K / 8][npad][8]
 };
 
 struct TileCfg {
@@ -456,6 +461,17 @@ struct TileCfg {
 };
 // conv_kernel<TM, TN, WM, WN> instances: 256x32, 128x64, 128x128 for large layers, 128x32 and 64x64 for small ones (+ split-K)
 static const TileCfg kCfg[5] = {{256, 32}, {128, 64}, {128, 128}, {128, 32}, {64, 64}};
+
+// The plan table of each precision: the tile shape of a layer (the wide tile of its column class when the layer fills at
+// least `wide_tiles` of them, else the small one) and its K slicing (split until `target_wgs` workgroups are in flight, at
+// least `min_chunks` 16-wide chunks per slice).  Half: an fp16 MFMA retires a chunk in 1/16 of the time and the kernel
+// stages 4 chunks between two barriers, so a slice is at least 16 chunks (256 of K, 4 stages) to be worth its fp32
+// partials and its reduction (DENOISER.md, "Half precision").
+struct PlanRule {
+  int wide_tiles[3];  // N <= 32, N <= 64, N > 64
+  int target_wgs, min_chunks;
+};
+static const PlanRule kPlan[2] = {{{256, 128, 256}, 512, 8}, {{256, 128, 256}, 512, 16}};
 
 }  // namespace ptdn
 
@@ -465,11 +481,14 @@ struct pt_denoiser {
   int width, height, device;
   std::vector<Act> acts;
   std::vector<Conv> convs;
-  float* d_w = nullptr;
-  float* d_ws = nullptr;
+  int precision = PT_DENOISE_F32;
+  size_t esz = sizeof(float);                 // bytes of a stored activation element
+  float* d_w = nullptr;                       // fp32: weights + bias/scale/shift; half: bias/scale/shift only
+  _Float16* d_wh = nullptr;                   // half: the convolution weights
+  char* d_ws = nullptr;                       // activations, ws_floats elements of esz bytes
   float* d_partial = nullptr;
   float* d_premax = nullptr;
-  size_t ws_floats = 0, w_floats = 0, partial_floats = 0;
+  size_t ws_floats = 0, w_floats = 0, partial_floats = 0, p_floats = 0, wh_halves = 0;
   int pre_blocks = 0;
   int max_frames = 1;                         // frames per group (pt_denoiser_reserve_frames)
   std::map<int, std::vector<Conv>> plans;     // batch_plan of each group size used so far
@@ -491,22 +510,22 @@ static int64_t conv_tiles(const Conv& c, int cfg) {
   return (int64_t)((c.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((c.N + bn - 1) / bn);
 }
 
-static int pick_cfg(const Conv& c) {
-  if (c.N <= 32) return conv_tiles(c, 0) >= 256 ? 0 : 3;
-  if (c.N <= 64) return conv_tiles(c, 1) >= 128 ? 1 : 4;
-  return conv_tiles(c, 2) >= 256 ? 2 : 4;
+static int pick_cfg(const Conv& c, const PlanRule& p) {
+  if (c.N <= 32) return conv_tiles(c, 0) >= p.wide_tiles[0] ? 0 : 3;
+  if (c.N <= 64) return conv_tiles(c, 1) >= p.wide_tiles[1] ? 1 : 4;
+  return conv_tiles(c, 2) >= p.wide_tiles[2] ? 2 : 4;
 }
 
-static void choose_tiles(Conv& c) {
-  c.cfg = pick_cfg(c);
+static void choose_tiles(Conv& c, const PlanRule& p) {
+  c.cfg = pick_cfg(c, p);
   c.npad = (c.N + kCfg[c.cfg].bn - 1) / kCfg[c.cfg].bn * kCfg[c.cfg].bn;
   c.nchunks = c.K / BK;
   // split K until about two workgroups per CU are in flight, keeping at least 8 chunks (128 of K) per slice
   const int64_t t = conv_tiles(c, c.cfg);
   int splits = 1;
-  if (t < 256) {
-    splits = (int)((512 + t - 1) / t);
-    const int most = c.nchunks / 8 > 0 ? c.nchunks / 8 : 1;
+  if (t < p.target_wgs / 2) {
+    splits = (int)((p.target_wgs + t - 1) / t);
+    const int most = c.nchunks / p.min_chunks > 0 ? c.nchunks / p.min_chunks : 1;
     if (splits > most) splits = most;
   }
   c.chunks_per_split = (c.nchunks + splits - 1) / splits;
@@ -535,7 +554,7 @@ static void build_layers(pt_denoiser* d) {
     c.out_h = (a.h - 1) / stride + 1, c.out_w = (a.w - 1) / stride + 1;
     c.M = c.out_h * c.out_w;
     c.K = ks * ks * c.cin;
-    choose_tiles(c);
+    choose_tiles(c, kPlan[d->precision]);
     d->convs.push_back(c);
   };
   char n[64];
@@ -566,34 +585,40 @@ static void build_layers(pt_denoiser* d) {
     rep = nr;
   }
   conv("rgb_conv", rep, 3, 1, 3, EPI_RGB, -1, 3, -1, -1, -1);
-  size_t woff = 0;
+  size_t woff = 0, poff = 0, hoff = 0;
   for (Conv& c : d->convs) {
     c.w_off = woff;
     woff += ((size_t)c.K * c.npad + 3 * (size_t)c.npad + 63) / 64 * 64;
+    c.h_off = hoff;
+    hoff += ((size_t)c.K * c.npad + 127) / 128 * 128;
+    c.p_off = d->precision == PT_DENOISE_F16 ? poff : c.w_off + (size_t)c.K * c.npad;
+    poff += (3 * (size_t)c.npad + 63) / 64 * 64;
   }
-  d->w_floats = woff;
+  d->w_floats = woff, d->p_floats = poff, d->wh_halves = hoff;
 }
 
 // The conv table of a group of n frames, from the single-frame table: M = n rows per output pixel, the tile shape re-chosen
 // for that M (same column padding), the K slicing KEPT.  An output element's value depends only on the slicing of K and on
 // the fixed chunk-by-chunk MFMA chain, not on the tile shape, so every frame of the group gets the bits of a single enqueue.
-static std::vector<Conv> batch_plan(const std::vector<Conv>& single, int n) {
+static std::vector<Conv> batch_plan(const std::vector<Conv>& single, int n, const PlanRule& p) {
   std::vector<Conv> out = single;
   if (n == 1) return out;
   for (Conv& c : out) {
     c.M = n * c.out_h * c.out_w;
-    const int cfg = pick_cfg(c);
+    const int cfg = pick_cfg(c, p);
     if (c.npad % kCfg[cfg].bn == 0) c.cfg = cfg;  // the weights are stored with the single-frame column padding
   }
   return out;
 }
 
-// Workspace offsets of every activation for groups of up to `frames` frames; returns the workspace floats.
-static size_t layout_acts(std::vector<Act>& acts, int frames) {
+// Workspace offsets (in elements of esz bytes) of every activation for groups of up to `frames` frames; returns the
+// workspace elements.
+static size_t layout_acts(std::vector<Act>& acts, int frames, size_t esz) {
+  const size_t al = 256 / esz;  // 256-byte aligned
   size_t off = 0;
   for (Act& a : acts) {
     a.off = off;
-    off += ((size_t)frames * a.h * a.w * a.c + 63) / 64 * 64;  // 256-byte aligned
+    off += ((size_t)frames * a.h * a.w * a.c + al - 1) / al * al;
   }
   return off;
 }
@@ -658,14 +683,15 @@ static void fill_weights(const pt_denoiser* d, const std::map<std::string, Tenso
 static const std::vector<Conv>& plan_for(pt_denoiser* d, int n) {
   if (n == 1) return d->convs;
   auto it = d->plans.find(n);
-  if (it == d->plans.end()) it = d->plans.emplace(n, batch_plan(d->convs, n)).first;
+  if (it == d->plans.end()) it = d->plans.emplace(n, batch_plan(d->convs, n, kPlan[d->precision])).first;
   return it->second;
 }
 
 static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
   ConvArgs a{};
   const Act& in = d->acts[c.in];
-  a.in = d->d_ws + in.off;
+  float* ws = reinterpret_cast<float*>(d->d_ws);
+  a.in = ws + in.off;
   a.in_h = c.in_h, a.in_w = c.in_w, a.cin = c.cin;
   a.wt = d->d_w + c.w_off;
   a.npad = c.npad, a.ks = c.ks, a.stride = c.stride;
@@ -673,11 +699,11 @@ static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out,
   a.nchunks = c.nchunks, a.chunks_per_split = c.chunks_per_split;
   a.partial = c.splits > 1 ? d->d_partial : nullptr;
   a.epi = c.epi;
-  a.bias = a.wt + (size_t)c.K * c.npad;
+  a.bias = d->d_w + c.p_off;
   a.scale = a.bias + c.npad;
   a.shift = a.scale + c.npad;
   if (c.out0 >= 0) {
-    a.out0 = d->d_ws + d->acts[c.out0].off;
+    a.out0 = ws + d->acts[c.out0].off;
     a.ld0 = d->acts[c.out0].c;
   } else {
     a.out0 = frame_out;
@@ -685,15 +711,53 @@ static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out,
   }
   a.nsplit = c.nsplit;
   if (c.out1 >= 0) {
-    a.out1 = d->d_ws + d->acts[c.out1].off;
+    a.out1 = ws + d->acts[c.out1].off;
     a.ld1 = d->acts[c.out1].c;
   }
-  if (c.res >= 0) a.res = d->d_ws + d->acts[c.res].off;
+  if (c.res >= 0) a.res = ws + d->acts[c.res].off;
   if (c.up >= 0) {
-    a.up = d->d_ws + d->acts[c.up].off;
+    a.up = ws + d->acts[c.up].off;
     a.up_h = d->acts[c.up].h, a.up_w = d->acts[c.up].w;
   }
-  a.x0 = d->d_ws + d->acts[0].off;
+  a.x0 = ws + d->acts[0].off;
+  a.frames = frames, a.out_hw = c.out_h * c.out_w;
+  a.frame_stride = frame_stride;
+  return a;
+}
+
+// The same for a half denoiser: half activations and weights, fp32 bias/scale/shift, the head's output in fp32.
+static HConvArgs hconv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
+  HConvArgs a{};
+  _Float16* ws = reinterpret_cast<_Float16*>(d->d_ws);
+  a.in = ws + d->acts[c.in].off;
+  a.in_h = c.in_h, a.in_w = c.in_w, a.cin = c.cin;
+  a.wt = d->d_wh + c.h_off;
+  a.npad = c.npad, a.ks = c.ks, a.stride = c.stride;
+  a.out_w = c.out_w, a.out_h = c.out_h, a.M = c.M, a.N = c.N;
+  a.nchunks = c.nchunks, a.chunks_per_split = c.chunks_per_split;
+  a.partial = c.splits > 1 ? d->d_partial : nullptr;
+  a.epi = c.epi;
+  a.bias = d->d_w + c.p_off;
+  a.scale = a.bias + c.npad;
+  a.shift = a.scale + c.npad;
+  if (c.out0 >= 0) {
+    a.out0 = ws + d->acts[c.out0].off;
+    a.ld0 = d->acts[c.out0].c;
+  } else {
+    a.rgb = frame_out;
+    a.ld0 = frame_ld;
+  }
+  a.nsplit = c.nsplit;
+  if (c.out1 >= 0) {
+    a.out1 = ws + d->acts[c.out1].off;
+    a.ld1 = d->acts[c.out1].c;
+  }
+  if (c.res >= 0) a.res = ws + d->acts[c.res].off;
+  if (c.up >= 0) {
+    a.up = ws + d->acts[c.up].off;
+    a.up_h = d->acts[c.up].h, a.up_w = d->acts[c.up].w;
+  }
+  a.x0 = ws + d->acts[0].off;
   a.frames = frames, a.out_hw = c.out_h * c.out_w;
   a.frame_stride = frame_stride;
   return a;
@@ -704,8 +768,27 @@ static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, in
                        hipStream_t s, int* launches) {
   if (c.epi != EPI_ACT && kCfg[c.cfg].bn != 32)
     return pt_fail(PT_EINVAL, "launch_conv: %s: the lateral and head epilogues need 32-column tiles", c.name.c_str());
-  const ConvArgs a = conv_args(d, c, frame_out, frame_ld, frame_stride, frames);
   const dim3 grid((c.M + kCfg[c.cfg].bm - 1) / kCfg[c.cfg].bm, c.npad / kCfg[c.cfg].bn, c.splits);
+  if (d->precision == PT_DENOISE_F16) {
+    const HConvArgs a = hconv_args(d, c, frame_out, frame_ld, frame_stride, frames);
+    switch (c.cfg) {
+      case 0: hipLaunchKernelGGL((hconv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+      case 1: hipLaunchKernelGGL((hconv_kernel<1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((hconv_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, a); break;
+      case 3: hipLaunchKernelGGL((hconv_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+      default: hipLaunchKernelGGL((hconv_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
+    }
+    PTDN_HIP(hipGetLastError());
+    (*launches)++;
+    if (c.splits > 1) {
+      const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
+      hipLaunchKernelGGL(hsplitk_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
+      PTDN_HIP(hipGetLastError());
+      (*launches)++;
+    }
+    return PT_OK;
+  }
+  const ConvArgs a = conv_args(d, c, frame_out, frame_ld, frame_stride, frames);
   switch (c.cfg) {
     case 0: hipLaunchKernelGGL((conv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
     case 1: hipLaunchKernelGGL((conv_kernel<1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
@@ -733,6 +816,7 @@ int pt_denoiser_weights_check(const void* blob, size_t bytes) {
 int pt_denoiser_destroy(pt_denoiser* d) {
   if (!d) return PT_OK;
   if (d->d_w) (void)hipFree(d->d_w);
+  if (d->d_wh) (void)hipFree(d->d_wh);
   if (d->d_ws) (void)hipFree(d->d_ws);
   if (d->d_partial) (void)hipFree(d->d_partial);
   if (d->d_premax) (void)hipFree(d->d_premax);
@@ -742,14 +826,53 @@ int pt_denoiser_destroy(pt_denoiser* d) {
   return PT_OK;
 }
 
-int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt_denoiser** out) {
+// Half mode: every convolution weight must be representable (the conversion rounds to nearest even; it does not saturate).
+static int check_half_range(const std::map<std::string, Tensor>& t, const char* who) {
+  for (const auto& kv : t) {
+    if (kv.second.shape.size() != 4) continue;  // convolution weights; bias and batch-norm tensors stay fp32
+    for (size_t i = 0; i < kv.second.count; i++) {
+      const float v = ld_f32(kv.second, i);
+      if (fabsf(v) > HALF_MAX)
+        return pt_fail(PT_EINVAL, "%s: tensor '%s' holds %g at element %zu: outside the fp16 range of +-65504 (PT_DENOISE_F16)", who,
+                       kv.first.c_str(), (double)v, i);
+    }
+  }
+  return PT_OK;
+}
+
+// The half image of the convolution weights: each conv's [K][npad] floats re-laid out as [K / 8][npad][8] halves (a lane's
+// B fragment, 8 consecutive k of one column, is 16 contiguous bytes), rounded to nearest even; and the packed parameters.
+static void half_weights(const pt_denoiser* d, const std::vector<float>& w, std::vector<_Float16>& wh, std::vector<float>& wp) {
+  wh.assign(d->wh_halves, (_Float16)0.0f);
+  wp.assign(d->p_floats, 0.0f);
+  for (const Conv& c : d->convs) {
+    const float* wt = w.data() + c.w_off;
+    _Float16* o = wh.data() + c.h_off;
+    for (int k = 0; k < c.K; k++)
+      for (int n = 0; n < c.npad; n++) o[((size_t)(k >> 3) * c.npad + n) * 8 + (k & 7)] = (_Float16)wt[(size_t)k * c.npad + n];
+    memcpy(wp.data() + c.p_off, wt + (size_t)c.K * c.npad, 3 * (size_t)c.npad * sizeof(float));
+  }
+}
+
+int pt_denoiser_create_opts(int width, int height, const void* blob, size_t bytes, const pt_denoiser_opts* opts, pt_denoiser** out) {
   if (!out) return pt_fail(PT_EINVAL, "pt_denoiser_create: null output pointer");
   *out = nullptr;
+  if (!opts) return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: null options");
+  if (opts->precision != PT_DENOISE_F32 && opts->precision != PT_DENOISE_F16)
+    return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: precision %d is neither PT_DENOISE_F32 (0) nor PT_DENOISE_F16 (1)", opts->precision);
+  if (opts->max_frames < 1) return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: max_frames %d < 1", opts->max_frames);
+  for (int i = 0; i < 6; i++)
+    if (opts->reserved[i] != 0) return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: reserved[%d] = %d must be 0", i, opts->reserved[i]);
   if (width <= 0 || height <= 0 || (int64_t)width * height > 4096 * 4096)
     return pt_fail(PT_EINVAL, "pt_denoiser_create: frame size %d x %d outside 1 .. 4096 x 4096 pixels", width, height);
+  if (opts->max_frames > MAX_FRAMES || (int64_t)opts->max_frames * width * height > MAX_BATCH_PIXELS)
+    return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
+                   opts->max_frames, width, height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
   std::map<std::string, Tensor> t;
   int rc = parse_weights(blob, bytes, &t, "pt_denoiser_create");
   if (rc != PT_OK) return rc;
+  const bool half = opts->precision == PT_DENOISE_F16;
+  if (half && (rc = check_half_range(t, "pt_denoiser_create_opts")) != PT_OK) return rc;
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
@@ -758,18 +881,25 @@ int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt
   pt_denoiser* d = new (std::nothrow) pt_denoiser();
   if (!d) return pt_fail(PT_ENOMEM, "pt_denoiser_create: out of host memory");
   d->width = width, d->height = height;
+  d->precision = opts->precision;
+  d->esz = half ? sizeof(_Float16) : sizeof(float);
   build_layers(d);
-  d->ws_floats = layout_acts(d->acts, 1);
+  d->ws_floats = layout_acts(d->acts, 1, d->esz);
   d->partial_floats = partial_floats_of(d->convs);
-  std::vector<float> w;
+  std::vector<float> w, wp;
+  std::vector<_Float16> wh;
   fill_weights(d, t, w);
+  if (half) half_weights(d, w, wh, wp);
+  const std::vector<float>& wf = half ? wp : w;  // what d_w holds
   d->pre_blocks = (int)(((uint64_t)width * height + 255) / 256);
   if (d->pre_blocks > PRE_BLOCKS) d->pre_blocks = PRE_BLOCKS;
   e = hipGetDevice(&d->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&d->d_w, d->w_floats * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d->d_w, w.data(), d->w_floats * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&d->d_ws, d->ws_floats * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_w, wf.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d->d_w, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && half) e = hipMalloc((void**)&d->d_wh, wh.size() * sizeof(_Float16));
+  if (e == hipSuccess && half) e = hipMemcpy(d->d_wh, wh.data(), wh.size() * sizeof(_Float16), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_ws, d->ws_floats * d->esz);
+  if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_floats * d->esz);
   if (e == hipSuccess && d->partial_floats) e = hipMalloc((void**)&d->d_partial, d->partial_floats * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->d_premax, PRE_BLOCKS * 5 * sizeof(float));
   if (e == hipSuccess) e = hipEventCreate(&d->ev0);
@@ -779,11 +909,21 @@ int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt
     pt_denoiser_destroy(d);
     return rc;
   }
+  if (opts->max_frames > 1 && (rc = pt_denoiser_reserve_frames(d, opts->max_frames)) != PT_OK) {
+    pt_denoiser_destroy(d);
+    return rc;
+  }
   *out = d;
   return PT_OK;
 }
 
-int pt_denoiser_create_from_file(int width, int height, const char* path, pt_denoiser** out) {
+int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt_denoiser** out) {
+  pt_denoiser_opts opts{};
+  opts.precision = PT_DENOISE_F32, opts.max_frames = 1;
+  return pt_denoiser_create_opts(width, height, blob, bytes, &opts, out);
+}
+
+int pt_denoiser_create_opts_from_file(int width, int height, const char* path, const pt_denoiser_opts* opts, pt_denoiser** out) {
   if (!path) return pt_fail(PT_EINVAL, "pt_denoiser_create_from_file: null path");
   FILE* f = fopen(path, "rb");
   if (!f) return pt_fail(PT_EINVAL, "pt_denoiser_create_from_file: cannot open '%s'", path);
@@ -792,7 +932,19 @@ int pt_denoiser_create_from_file(int width, int height, const char* path, pt_den
   size_t got;
   while ((got = fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
   fclose(f);
-  return pt_denoiser_create(width, height, buf.data(), buf.size(), out);
+  return pt_denoiser_create_opts(width, height, buf.data(), buf.size(), opts, out);
+}
+
+int pt_denoiser_create_from_file(int width, int height, const char* path, pt_denoiser** out) {
+  pt_denoiser_opts opts{};
+  opts.precision = PT_DENOISE_F32, opts.max_frames = 1;
+  return pt_denoiser_create_opts_from_file(width, height, path, &opts, out);
+}
+
+int pt_denoiser_precision(const pt_denoiser* d, int* out) {
+  if (!d || !out) return pt_fail(PT_EINVAL, "pt_denoiser_precision: null %s", d ? "output pointer" : "denoiser");
+  *out = d->precision;
+  return PT_OK;
 }
 
 int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
@@ -803,16 +955,17 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
   if (max_frames > MAX_FRAMES || px > MAX_BATCH_PIXELS)
     return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
                    max_frames, d->width, d->height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
-  const std::vector<Conv> plan = batch_plan(d->convs, max_frames);
+  const std::vector<Conv> plan = batch_plan(d->convs, max_frames, kPlan[d->precision]);
   for (const Conv& c : plan)  // splitk_reduce_kernel indexes M x N elements in 32 bits
     if ((int64_t)c.M * c.N > (int64_t)UINT32_MAX)
       return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d: layer %s has too many elements", max_frames, c.name.c_str());
   std::vector<Act> acts = d->acts;
-  const size_t ws_floats = layout_acts(acts, max_frames);
+  const size_t ws_floats = layout_acts(acts, max_frames, d->esz);
   const size_t partial_floats = partial_floats_of(plan);
-  float *ws = nullptr, *partial = nullptr, *premax = nullptr;
-  hipError_t e = hipMalloc((void**)&ws, ws_floats * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(ws, 0, ws_floats * sizeof(float));
+  char* ws = nullptr;
+  float *partial = nullptr, *premax = nullptr;
+  hipError_t e = hipMalloc((void**)&ws, ws_floats * d->esz);
+  if (e == hipSuccess) e = hipMemset(ws, 0, ws_floats * d->esz);
   if (e == hipSuccess && partial_floats) e = hipMalloc((void**)&partial, partial_floats * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&premax, (size_t)max_frames * PRE_BLOCKS * 5 * sizeof(float));
   if (e == hipSuccess) e = hipDeviceSynchronize();  // the old buffers may still be in use by enqueued work
@@ -821,7 +974,7 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
     if (ws) (void)hipFree(ws);
     if (partial) (void)hipFree(partial);
     if (premax) (void)hipFree(premax);
-    return pt_fail(PT_EHIP, "pt_denoiser_reserve_frames: %d frames (%zu + %zu workspace floats): %s; the old workspace is kept",
+    return pt_fail(PT_EHIP, "pt_denoiser_reserve_frames: %d frames (%zu + %zu workspace elements): %s; the old workspace is kept",
                    max_frames, ws_floats, partial_floats, hipGetErrorString(e));
   }
   (void)hipFree(d->d_ws);
@@ -848,15 +1001,21 @@ int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, si
     return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: rgb_stride_floats %zu < width x height x 3 = %zu", rgb_stride_floats,
                    (size_t)pixels * 3);
   hipStream_t s = (hipStream_t)hip_stream;
-  float* x0 = d->d_ws + d->acts[0].off;
+  const bool half = d->precision == PT_DENOISE_F16;
+  float* x0 = reinterpret_cast<float*>(d->d_ws) + d->acts[0].off;
+  _Float16* x0h = reinterpret_cast<_Float16*>(d->d_ws) + d->acts[0].off;
   for (int f0 = 0; f0 < n_frames; f0 += d->max_frames) {
     const int g = n_frames - f0 < d->max_frames ? n_frames - f0 : d->max_frames;
     float* frames = d_frames + (size_t)f0 * frame_stride_floats;
     float* out = d_rgb ? d_rgb + (size_t)f0 * rgb_stride_floats : frames;
     hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks, g), dim3(256), 0, s, frames, frame_stride_floats, pixels, d->d_premax);
     PTDN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
-                       d->d_premax, d->pre_blocks, x0, d_rgb ? 0 : 1);
+    if (half)
+      hipLaunchKernelGGL(hpre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
+                         d->d_premax, d->pre_blocks, x0h, d_rgb ? 0 : 1);
+    else
+      hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
+                         d->d_premax, d->pre_blocks, x0, d_rgb ? 0 : 1);
     PTDN_HIP(hipGetLastError());
     d->last_launches += 2;
     for (const Conv& c : plan_for(d, g)) {
@@ -920,7 +1079,13 @@ int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PTDN_HIP(hipDeviceSynchronize());
-  PTDN_HIP(hipMemcpy(h_out, d->d_ws + a.off, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (d->precision == PT_DENOISE_F16) {  // the host sees float32 in both modes (every half is one exactly)
+    std::vector<_Float16> tmp(n);
+    PTDN_HIP(hipMemcpy(tmp.data(), d->d_ws + a.off * d->esz, n * sizeof(_Float16), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) h_out[i] = (float)tmp[i];
+    return PT_OK;
+  }
+  PTDN_HIP(hipMemcpy(h_out, d->d_ws + a.off * d->esz, n * sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 
@@ -931,7 +1096,13 @@ int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_i
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PTDN_HIP(hipDeviceSynchronize());
-  PTDN_HIP(hipMemcpy(d->d_ws + a.off, h_in, n * sizeof(float), hipMemcpyHostToDevice));
+  if (d->precision == PT_DENOISE_F16) {  // rounded to nearest even, saturating like every store of the half mode
+    std::vector<_Float16> tmp(n);
+    for (size_t i = 0; i < n; i++) tmp[i] = (_Float16)fminf(fmaxf(h_in[i], -HALF_MAX), HALF_MAX);
+    PTDN_HIP(hipMemcpy(d->d_ws + a.off * d->esz, tmp.data(), n * sizeof(_Float16), hipMemcpyHostToDevice));
+    return PT_OK;
+  }
+  PTDN_HIP(hipMemcpy(d->d_ws + a.off * d->esz, h_in, n * sizeof(float), hipMemcpyHostToDevice));
   return PT_OK;
 }
 
@@ -956,6 +1127,19 @@ int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
   const int rc = launch_conv(d, c, d_rgb, 3, 0, 1, nullptr, &launches);
   if (rc != PT_OK) return rc;
   PTDN_HIP(hipDeviceSynchronize());
+  return PT_OK;
+}
+
+int pt_debug_denoiser_memory(pt_denoiser* d, int layer, uint64_t info[6]) {
+  if (!d || !info) return pt_fail(PT_EINVAL, "pt_debug_denoiser_memory: null denoiser or output");
+  if (layer < 0 || layer >= (int)d->acts.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_memory: no layer %d", layer);
+  const Act& a = d->acts[layer];
+  info[0] = d->esz;
+  info[1] = a.off * d->esz;
+  info[2] = (uint64_t)a.h * a.w * a.c * d->esz;
+  info[3] = d->ws_floats * d->esz;
+  info[4] = d->partial_floats * sizeof(float);
+  info[5] = d->precision == PT_DENOISE_F16 ? d->wh_halves * sizeof(_Float16) + d->p_floats * sizeof(float) : d->w_floats * sizeof(float);
   return PT_OK;
 }
 

@@ -21,9 +21,19 @@ class DenoiseNet {
  public:
   // load_pretrained + .eval() for width x height frames; weights = a PTDN file (cuda-pathtrace_amd/denoise_weights.py).
   // maxFrames > 1: workspace for batches of that many frames per group (DenoiseFrames / EnqueueFrames).
-  DenoiseNet(int width, int height, const std::string& weights, int maxFrames = 1) : net(NULL), width(width), height(height) {
-    gpuErrchk(pt_denoiser_create_from_file(width, height, weights.c_str(), &net));
-    if (maxFrames > 1) gpuErrchk(pt_denoiser_reserve_frames(net, maxFrames));
+  // precision: PT_DENOISE_F32 (default) or PT_DENOISE_F16, the toleranced half mode (fp16 operands and storage, fp32
+  // accumulation; include/ptcore.h states its contract).
+  DenoiseNet(int width, int height, const std::string& weights, int maxFrames = 1, int precision = PT_DENOISE_F32)
+      : net(NULL), width(width), height(height) {
+    pt_denoiser_opts opts = pt_denoiser_opts();
+    opts.precision = precision;
+    opts.max_frames = maxFrames;
+    gpuErrchk(pt_denoiser_create_opts_from_file(width, height, weights.c_str(), &opts, &net));
+  }
+  int Precision() const {
+    int p = PT_DENOISE_F32;
+    gpuErrchk(pt_denoiser_precision(net, &p));
+    return p;
   }
   ~DenoiseNet() { (void)pt_denoiser_destroy(net); }
 

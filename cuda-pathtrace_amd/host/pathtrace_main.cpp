@@ -62,6 +62,7 @@ static void usage() {
                "  --gpus arg                    row-tile the frame over N devices starting at --device (RCCL gather)\n"
                "  --preview arg                 also write the display-packed frame (Denoiser) as a binary PPM\n"
                "  --denoise-weights arg         with -d: PTDN weight file of the denoising network\n"
+               "  --denoise-precision arg       with -d: float (default) | half (fp16 operands, fp32 accumulation)\n"
                "  --progressive arg             refine the still frame in N passes of -s samples each (one buffer)\n"
                "  --adaptive arg                with --progressive: stop pixels whose mean luminance has a relative\n"
                "                                standard error <= arg; ends early when no pixel is active\n"
@@ -82,7 +83,8 @@ int main(int argc, const char** argv) {
   std::string outputName = "output/out";
   std::string rng = "xorwow";
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
-  std::string posesFile, previewFile, denoiseWeights;
+  std::string posesFile, previewFile, denoiseWeights, denoisePrecision;
+  bool denoisePrecisionGiven = false;
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
   bool progressiveGiven = false, framesGiven = false, gpusGiven = false;
@@ -131,6 +133,7 @@ int main(int argc, const char** argv) {
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
     else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
+    else if (a == "--denoise-precision") { denoisePrecision = value("--denoise-precision"); denoisePrecisionGiven = true; }
     else {
       std::cerr << "ERROR: unrecognised option '" << a << "'" << std::endl << std::endl;
       usage();
@@ -166,6 +169,16 @@ int main(int argc, const char** argv) {
     std::cerr << "ERROR: -d needs the network's weights: --denoise-weights FILE (a PTDN file written by "
                  "cuda-pathtrace_amd/denoise_weights.py from a state_dict trained with the reference's train.py)" << std::endl;
     return 1;
+  }
+  if (denoisePrecisionGiven) {  // (before any device is touched)
+    if (!denoising) {
+      std::cerr << "ERROR: --denoise-precision needs -d: it chooses the precision of the denoising network" << std::endl;
+      return 1;
+    }
+    if (denoisePrecision != "half" && denoisePrecision != "float") {
+      std::cerr << "ERROR: --denoise-precision '" << denoisePrecision << "': half or float" << std::endl;
+      return 1;
+    }
   }
   if (denoising && batch) {
     std::cerr << "ERROR: -d cannot be combined with --batch: the denoiser runs after every frame of the loop" << std::endl;
@@ -246,7 +259,8 @@ int main(int argc, const char** argv) {
     single = new Renderer(width, height, samplesPerPixel, threadsPerBlock, opts);
   }
   // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
-  DenoiseNet* net = denoising ? new DenoiseNet(width, height, denoiseWeights) : NULL;
+  DenoiseNet* net =
+      denoising ? new DenoiseNet(width, height, denoiseWeights, 1, denoisePrecision == "half" ? PT_DENOISE_F16 : PT_DENOISE_F32) : NULL;
   float denoiseTime = 0.0f;
   auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);

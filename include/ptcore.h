@@ -298,6 +298,31 @@ int pt_denoiser_weights_check(const void* blob, size_t bytes);
 int pt_denoiser_create(int width, int height, const void* blob, size_t bytes, pt_denoiser** out);
 int pt_denoiser_create_from_file(int width, int height, const char* path, pt_denoiser** out);
 int pt_denoiser_destroy(pt_denoiser* d);
+/* Half precision (opt-in; pt_denoiser_create is PT_DENOISE_F32 and unchanged).  PT_DENOISE_F16 runs the same network with
+ * fp16 operands and storage and fp32 accumulation (v_mfma_f32_32x32x16_f16): the convolution weights are rounded once (to
+ * nearest even) at create time, every stored activation -- the workspace copy of the pre-processed frame included -- is
+ * fp16, and every epilogue (bias, ReLU, batch norm, residual, upsample + lateral, albedo multiply and clamp) is computed in
+ * fp32 and rounded once on its store.  Every such store SATURATES to +-65504 instead of producing an infinity (what a NaN
+ * becomes is unspecified, as it is for the fp32 mode's ReLU).  What lands in the caller's frame is fp32 as before: channels
+ * 0-2 the clamped result, 3-8 untouched, 9-13 divided in fp32 exactly as in the fp32 mode (bit for bit).  Bias and the folded
+ * batch norm stay fp32.  Tolerance contract (like fast_math's: tests/test_denoiser_half_gpu.py holds it): against the
+ * float64 network on the same frame, the [0, 1] output's error is within 2 x rms + 1e-5 and 3 x max + 1e-4 of the error of
+ * the float64 network with the same roundings inserted (tests/denoise_half_model.py); that model's own error on 64 x 64
+ * frames with seeded random weights is 0.8e-3 .. 3.1e-3 max, 1.4e-4 .. 5.2e-4 rms (half an 8-bit display step is 2.0e-3).
+ * The values measured on the GPU are in DENOISER.md, "Half precision".  Runs are deterministic and batches keep the
+ * bit-for-bit contract of pt_denoiser_enqueue_frames within the mode.  The workspace is half the fp32 mode's bytes.
+ * opts: precision = PT_DENOISE_F32 or PT_DENOISE_F16; max_frames >= 1 = pt_denoiser_reserve_frames(max_frames) at create
+ * time; reserved words must be 0.  Anything else, or (PT_DENOISE_F16) a convolution weight beyond +-65504, is PT_EINVAL
+ * naming the argument or the tensor, before a device is touched. */
+enum { PT_DENOISE_F32 = 0, PT_DENOISE_F16 = 1 };
+typedef struct pt_denoiser_opts {
+  int32_t precision;  /* PT_DENOISE_*                      */
+  int32_t max_frames; /* frames per group, >= 1            */
+  int32_t reserved[6]; /* must be 0                        */
+} pt_denoiser_opts;
+int pt_denoiser_create_opts(int width, int height, const void* blob, size_t bytes, const pt_denoiser_opts* opts, pt_denoiser** out);
+int pt_denoiser_create_opts_from_file(int width, int height, const char* path, const pt_denoiser_opts* opts, pt_denoiser** out);
+int pt_denoiser_precision(const pt_denoiser* d, int* out); /* *out = PT_DENOISE_F32 or PT_DENOISE_F16 */
 /* train.py:test(model, boost_tensor) + modify_tensor (main.cu:106,150-152) on the device frame d_frame ([height][width][14]),
  * asynchronous on hip_stream (NULL = default stream).  d_rgb == NULL: the reference's in-place semantics.  d_rgb != NULL:
  * the result goes to d_rgb ([height][width][3]) and d_frame is left byte for byte untouched.  One denoiser's enqueues share

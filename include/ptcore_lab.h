@@ -75,6 +75,12 @@ int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_i
 int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len);
 /* Runs convolution `conv` alone on the workspace as it stands (synchronous); the rgb head writes [rows][cols][3] to d_rgb. */
 int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
+/* Memory of the denoiser and of activation buffer `layer`, in bytes: info = {bytes per stored activation element (4, or 2
+ * for a PT_DENOISE_F16 denoiser), the layer's offset into the workspace, the layer's size for ONE frame, the whole activation
+ * workspace (all max_frames frames), the split-K partials (fp32 in both modes), the device weights}.  The activation and
+ * set_activation calls above exchange float32 with the host in both modes (converted on the way; a half denoiser rounds
+ * what is set to nearest even, saturating). */
+int pt_debug_denoiser_memory(pt_denoiser* d, int layer, uint64_t info[6]);
 /* The last enqueue (single or batch): *groups = frame groups it made, *launches = kernels it launched (0, 0 before any). */
 int pt_debug_denoiser_last_enqueue(pt_denoiser* d, int* groups, int* launches);
 /* Convolution `conv` of the plan of a group of n_frames frames (host arithmetic; any size inside the batch limits): info =
