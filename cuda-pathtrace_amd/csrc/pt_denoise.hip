@@ -1,11 +1,15 @@
 // pt_denoise.hip -- the reference's denoising network (DenoiseCNN, denoise_cnn/model.py, run by train.py:test() from the
 // interactive loop, src/main.cu:92-122,146-152) as fp32 MFMA inference behind pt_denoiser_* (include/ptcore.h), and, opt-in
-// (PT_DENOISE_F16), the same network on fp16 operands and storage with fp32 accumulation (pt_denoise_half.h).
-// Design and numbers: DENOISER.md.  Kernels: the two pre-processing kernels (channel maxima, then the divisions and the
-// channel-padded NHWC copy), ONE implicit-GEMM convolution template (compile-time tile shape, run-time epilogue kind) and the
-// deterministic split-K reduction that applies the same epilogue.  Host side: the PTDN weight loader, the layer table and the
-// workspace, fixed at create time for the denoiser's width and height and grown by pt_denoiser_reserve_frames for batches:
-// a batch of n frames runs through the same launches as one frame, its rows m = (frame, pixel) (DENOISER.md, "Batches").
+// (PT_DENOISE_F16), the same network on fp16 operands and storage with fp32 accumulation.  Design and numbers: DENOISER.md.
+// ONE kernel family, templated on T, the element type of a stored activation (float / _Float16): the two pre-processing
+// kernels (channel maxima, then the divisions and the channel-padded NHWC copy), the implicit-GEMM convolution (compile-time
+// tile shape, run-time epilogue kind) and the deterministic split-K reduction that applies the same epilogue.  Everything
+// outside an MFMA is computed in fp32 in both modes: T decides only how a stored value is read (widened by a cast) and
+// written (to_stored: the half mode's one rounding) and which of conv_kernel's two main loops runs (32x32x2 f32 MFMA or
+// 32x32x16 f16 MFMA) between the set-up and the C/D store they share.  Host side: the PTDN weight loader, the
+// layer table and the workspace, fixed at create time for the denoiser's width and height and grown by
+// pt_denoiser_reserve_frames for batches: a batch of n frames runs through the same launches as one frame, its rows
+// m = (frame, pixel) (DENOISER.md, "Batches").
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,6 +18,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pt_internal.h"
@@ -26,6 +31,7 @@
 namespace ptdn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 enum { EPI_ACT = 0, EPI_LAT = 1, EPI_RGB = 2 };
 constexpr int BK = 16;              // K per staged chunk (every stored Cin is a multiple of 16: one chunk never straddles a tap)
@@ -34,12 +40,18 @@ constexpr int PRE_BLOCKS = 256;     // partial maxima of the pre-processing redu
 constexpr float KEPS = 0.00316f;    // train.py:48-55, model.py forward
 constexpr int64_t MAX_BATCH_PIXELS = (int64_t)1 << 26;  // max_frames x width x height: every row index m stays inside int32
 constexpr int MAX_FRAMES = 65535;                        // frames of one group: gridDim.y of the pre-processing kernels
+constexpr float HALF_MAX = 65504.0f;
+constexpr int HSC = 4;  // half GEMM: 16-wide K chunks staged per LDS buffer (64 of K between two barriers)
 
 // Rows m = f * out_h * out_w + pixel over the `frames` frames of a group; every activation is [frames][h][w][c], contiguous.
+// T = the element of a stored activation and of the convolution weights; split-K partials, bias / scale / shift and the
+// head's output are fp32 in both modes.
+template <class T>
 struct ConvArgs {
-  const float* in;  // NHWC [frames][in_h][in_w][cin]
+  const T* in;  // NHWC [frames][in_h][in_w][cin]
   int in_h, in_w, cin;
-  const float* wt;  // [K][npad], row k = (ky * ks + kx) * cin + c
+  const T* wt;  // float: [K][npad], row k = (ky * ks + kx) * cin + c; _Float16: [K / 8][npad][8], element j of group g,
+                // column n = W[k = 8 g + j][n]
   int npad, ks, stride;
   int out_w, M, N;
   int nchunks, chunks_per_split;
@@ -48,20 +60,40 @@ struct ConvArgs {
   const float* bias;  // [npad]
   const float* scale; // [npad] folded batch-norm (1 / 0 where there is none)
   const float* shift;
-  float* out0;        // columns [0, nsplit): out0[m * ld0 + n]
+  T* out0;            // columns [0, nsplit): out0[m * ld0 + n]
   int ld0, nsplit;
-  float* out1;        // columns [nsplit, N): out1[m * ld1 + n - nsplit]
+  T* out1;            // columns [nsplit, N): out1[m * ld1 + n - nsplit]
   int ld1;
-  const float* res;   // EPI_ACT: residual added after the affine, [M][ld0]
-  const float* up;    // EPI_LAT: the coarser map [up_h][up_w][32], bilinearly upsampled (align_corners) and added
+  const T* res;       // EPI_ACT: residual added after the affine, [M][ld0]
+  const T* up;        // EPI_LAT: the coarser map [up_h][up_w][32], bilinearly upsampled (align_corners) and added
   int up_h, up_w, out_h;
-  const float* x0;    // EPI_RGB: the pre-processed input (albedo = channels 6-8)
+  const T* x0;        // EPI_RGB: the pre-processed input (albedo = channels 6-8)
+  float* rgb;         // EPI_RGB: the fp32 frame (channels 0-2) or rgb buffer; see head_out
   int frames, out_hw; // frames of the group (M = frames * out_hw)
-  size_t frame_stride; // EPI_RGB: floats from one frame's output to the next (out0 + f * frame_stride + pixel * ld0)
+  size_t frame_stride; // EPI_RGB: floats from one frame's output to the next (head_out + f * frame_stride + pixel * ld0)
 };
 
+// Where the head writes.  The fp32 head keeps writing through out0 (conv_args points it at the frame): loading `rgb`
+// instead re-allocates the scalar registers of every fp32 kernel that holds the head epilogue.
+__device__ __forceinline__ float* head_out(const ConvArgs<float>& a) { return a.out0; }
+__device__ __forceinline__ float* head_out(const ConvArgs<_Float16>& a) { return a.rgb; }
+
+// The one rounding of a stored value.  float: none.  _Float16: clamp to the finite fp16 range in fp32, then convert (round
+// to nearest even), so an overflow never becomes an infinity.  Stored values are read back with a plain (float) cast.
+__device__ __forceinline__ _Float16 sat_half(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -HALF_MAX, HALF_MAX); }
+template <class T>
+__device__ __forceinline__ T to_stored(float v) {
+  if constexpr (std::is_same<T, float>::value)
+    return v;
+  else
+    return sat_half(v);
+}
+
 // The frame of row m and the row's pixel inside it (one frame: no division).
-__device__ __forceinline__ int frame_of(const ConvArgs& a, int m) { return a.frames > 1 ? m / a.out_hw : 0; }
+template <class T>
+__device__ __forceinline__ int frame_of(const ConvArgs<T>& a, int m) {
+  return a.frames > 1 ? m / a.out_hw : 0;
+}
 
 // ReLU that returns +0 for every non-positive input (torch: x <= 0 -> 0)
 __device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
@@ -70,7 +102,8 @@ __device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
 // coordinate is formed EXACTLY (integer quotient and remainder; weight = remainder / (out - 1), one rounding) rather than as
 // torch's float32 scale * index, whose rounding moves a sample by up to an ulp of the coordinate (DENOISER.md); the
 // interpolation itself is THNN's: h0 (w0 x00 + w1 x01) + h1 (w0 x10 + w1 x11).
-__device__ __forceinline__ float upsample(const ConvArgs& a, int f, int pix, int n) {
+template <class T>
+__device__ __forceinline__ float upsample(const ConvArgs<T>& a, int f, int pix, int n) {
   const int oy = pix / a.out_w, ox = pix - oy * a.out_w;
   int h1 = 0, w1 = 0;
   float h1l = 0.0f, w1l = 0.0f;
@@ -86,52 +119,60 @@ __device__ __forceinline__ float upsample(const ConvArgs& a, int f, int pix, int
   }
   const int hp = h1 < a.up_h - 1 ? 1 : 0, wp = w1 < a.up_w - 1 ? 1 : 0;
   const float h0l = 1.0f - h1l, w0l = 1.0f - w1l;
-  const float* p = a.up + ((size_t)(f * a.up_h + h1) * a.up_w + w1) * 32 + n;
+  const T* p = a.up + ((size_t)(f * a.up_h + h1) * a.up_w + w1) * 32 + n;
   const size_t dy = (size_t)hp * a.up_w * 32, dx = (size_t)wp * 32;
-  return h0l * (w0l * p[0] + w1l * p[dx]) + h1l * (w0l * p[dy] + w1l * p[dy + dx]);
+  return h0l * (w0l * (float)p[0] + w1l * (float)p[dx]) + h1l * (w0l * (float)p[dy] + w1l * (float)p[dy + dx]);
 }
 
 // conv, ReLU, folded BN (ResBlock: model.py:20-30), + residual (conv2)
-__device__ __forceinline__ void epilogue_act(const ConvArgs& a, int m, int n, float acc) {
+template <class T>
+__device__ __forceinline__ void epilogue_act(const ConvArgs<T>& a, int m, int n, float acc) {
   float v = __builtin_fmaf(relu(acc + a.bias[n]), a.scale[n], a.shift[n]);
   if (n < a.nsplit) {
     const size_t o = (size_t)m * a.ld0 + n;
-    if (a.res) v = v + a.res[o];
-    a.out0[o] = v;
+    if (a.res) v = v + (float)a.res[o];
+    a.out0[o] = to_stored<T>(v);
   } else {
-    a.out1[(size_t)m * a.ld1 + (n - a.nsplit)] = v;
+    a.out1[(size_t)m * a.ld1 + (n - a.nsplit)] = to_stored<T>(v);
   }
 }
 
-// The fused epilogue of every layer (m < M, n < N).
-__device__ __forceinline__ void epilogue(const ConvArgs& a, int m, int n, float acc) {
+// The fused epilogue of every layer (m < M, n < N), computed in fp32 and rounded once on the store; the head writes fp32.
+template <class T>
+__device__ __forceinline__ void epilogue(const ConvArgs<T>& a, int m, int n, float acc) {
   if (a.epi == EPI_ACT) {
     epilogue_act(a, m, n, acc);
   } else if (a.epi == EPI_LAT) {  // upsample(rep) + ReLU(lat_k(raw_k)), model.py:72-74
     const float v = relu(acc + a.bias[n]);
     const int f = frame_of(a, m);
-    a.out0[(size_t)m * a.ld0 + n] = upsample(a, f, m - f * a.out_hw, n) + v;
+    a.out0[(size_t)m * a.ld0 + n] = to_stored<T>(upsample(a, f, m - f * a.out_hw, n) + v);
   } else {  // rgb head: clamp(rgb_conv(rep) * (0.00316 + albedo), 0, 1), model.py:101-103
     float v = acc + a.bias[n];
-    v = v * (KEPS + a.x0[(size_t)m * XC + 6 + n]);
+    v = v * (KEPS + (float)a.x0[(size_t)m * XC + 6 + n]);
     const int f = frame_of(a, m);
-    a.out0[(size_t)f * a.frame_stride + (size_t)(m - f * a.out_hw) * a.ld0 + n] = fminf(fmaxf(v, 0.0f), 1.0f);
+    head_out(a)[(size_t)f * a.frame_stride + (size_t)(m - f * a.out_hw) * a.ld0 + n] = fminf(fmaxf(v, 0.0f), 1.0f);
   }
 }
 
 // Implicit-GEMM convolution: rows = output pixels, columns = output channels, K = taps x Cin.  4 waves; wave (wm, wn) owns
-// TM x TN tiles of 32 x 32 computed with v_mfma_f32_32x32x2_f32.  Inside a 16-wide K chunk, MFMA step kk takes k = kk from lane
-// half 0 and k = 8 + kk from lane half 1, so a lane's A operands for the whole chunk are 8 CONSECUTIVE channels of its pixel --
-// two float4 loads straight from the NHWC activation, no LDS (no other wave reads those rows).  The B chunk (weights) is
-// shared by the 4 waves and double-buffered in LDS.  blockIdx.z = split-K slice (partials to a.partial, summed in order by
-// splitk_reduce_kernel: deterministic, no atomics).  Rows run over the group's frames: a window is zero-padded at its own
-// frame's borders (iy is checked against in_h before the frame's first input row iyb is added).
-template <int TM, int TN, int WM, int WN>
-__global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
+// TM x TN tiles of 32 x 32.  blockIdx.z = split-K slice (partials to a.partial, summed in order by splitk_reduce_kernel:
+// deterministic, no atomics).  Rows run over the group's frames: a window is zero-padded at its own frame's borders (iy is
+// checked against in_h before the frame's first input row iyb is added).  The set-up, the accumulators and the C/D store
+// are the same for both element types; each has its OWN main loop, because their staging differs for measured reasons
+// (DENOISER.md, "Half precision"):
+//  * float, v_mfma_f32_32x32x2_f32: inside a 16-wide K chunk, MFMA step kk takes k = kk from lane half 0 and k = 8 + kk from
+//    lane half 1, so a lane's A operands for the whole chunk are 8 CONSECUTIVE channels of its pixel -- two float4 loads
+//    straight from the NHWC activation, no LDS (no other wave reads those rows).  The B chunk (weights) is shared by the 4
+//    waves and double-buffered in LDS.
+//  * _Float16, v_mfma_f32_32x32x16_f16: one MFMA consumes a whole 16-wide K chunk.  Lane (r = lane & 31, h = lane >> 5)
+//    supplies A[row r][k = 8 h + j], j = 0..7 -- 8 consecutive channels of its pixel, ONE 16-byte load from the NHWC half
+//    activation -- and B[k = 8 h + j][column r], 16 contiguous bytes of the [K / 8][npad][8] weights, read from an LDS stage
+//    of HSC chunks ([2 HSC groups][BN columns][8]) that the 4 waves share, double-buffered.  The chunks of a slice are
+//    accumulated in order, one MFMA each, whatever the tile shape: an output's bits depend on the K slicing alone.
+template <class T, int TM, int TN, int WM, int WN>
+__global__ void __launch_bounds__(256) conv_kernel(ConvArgs<T> a) {
   static_assert(WM * WN == 4, "four waves");
-  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, LDB = BN + 4;
-  constexpr int BF4 = BK * BN / 4, BPT = (BF4 + 255) / 256;
-  __shared__ float4 Bs4[2][BK * LDB / 4];
+  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave - (wave / WN) * WN;
   const int h = lane >> 5, r = lane & 31;
@@ -155,7 +196,20 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
     iy0[i] = oy * a.stride - pad;
     ix0[i] = ox * a.stride - pad;
   }
-  // A chunk c of this lane: 8 consecutive channels of its pixel per 32-row tile (zeros outside the image = padding)
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[i][j][e] = 0.0f;
+
+  if constexpr (std::is_same<T, float>::value) {
+    constexpr int LDB = BN + 4;
+    constexpr int BF4 = BK * BN / 4, BPT = (BF4 + 255) / 256;
+    __shared__ float4 Bs4[2][BK * LDB / 4];
+    // A chunk c of this lane: 8 consecutive channels of its pixel per 32-row tile (zeros outside the image = padding)
 #define PTDN_LOAD_A(c, ra)                                                                                        \
   do {                                                                                                            \
     const int k0_ = (c) * BK;                                                                                     \
@@ -173,8 +227,8 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
       ra[i][4] = v1.x, ra[i][5] = v1.y, ra[i][6] = v1.z, ra[i][7] = v1.w;                                         \
     }                                                                                                             \
   } while (0)
-  // B chunk c (BK x BN weights of this block's columns): float4 number tid (and tid + 256) of the chunk per thread
-  static_assert(BPT <= 2, "at most two float4 of B per thread");
+    // B chunk c (BK x BN weights of this block's columns): float4 number tid (and tid + 256) of the chunk per thread
+    static_assert(BPT <= 2, "at most two float4 of B per thread");
 #define PTDN_B_ADDR(c, f) (a.wt + (size_t)((c) * BK + (f) / (BN / 4)) * a.npad + nb + ((f) % (BN / 4)) * 4)
 #define PTDN_LOAD_B(c, rb0, rb1)                                                                                  \
   do {                                                                                                            \
@@ -186,57 +240,124 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
     if (tid < BF4) Bs4[buf][(tid / (BN / 4)) * (LDB / 4) + tid % (BN / 4)] = rb0;                                 \
     if (BPT > 1 && tid + 256 < BF4) Bs4[buf][((tid + 256) / (BN / 4)) * (LDB / 4) + (tid + 256) % (BN / 4)] = rb1; \
   } while (0)
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; i++)
-#pragma unroll
-    for (int j = 0; j < TN; j++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[i][j][e] = 0.0f;
-
-  if (c_begin < c_end) {
-    float ra[TM][8];
-    float4 rb0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb1 = rb0;
-    PTDN_LOAD_A(c_begin, ra);
-    PTDN_LOAD_B(c_begin, rb0, rb1);
-    PTDN_STORE_B(0, rb0, rb1);
-    __syncthreads();
-    for (int c = c_begin; c < c_end; c++) {
-      const int buf = (c - c_begin) & 1;
-      const bool more = c + 1 < c_end;
-      float na[TM][8];
-      if (more) {
-        PTDN_LOAD_A(c + 1, na);
-        PTDN_LOAD_B(c + 1, rb0, rb1);
-      }
-      const float* bs = reinterpret_cast<const float*>(Bs4[buf]) + h * 8 * LDB + nw + r;
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++) {
-        float bv[TN];
-#pragma unroll
-        for (int j = 0; j < TN; j++) bv[j] = bs[kk * LDB + j * 32];
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-          for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[i][kk], bv[j], acc[i][j], 0, 0, 0);
-      }
-      if (more) {
-        PTDN_STORE_B(buf ^ 1, rb0, rb1);
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-          for (int e = 0; e < 8; e++) ra[i][e] = na[i][e];
-      }
+    if (c_begin < c_end) {
+      float ra[TM][8];
+      float4 rb0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb1 = rb0;
+      PTDN_LOAD_A(c_begin, ra);
+      PTDN_LOAD_B(c_begin, rb0, rb1);
+      PTDN_STORE_B(0, rb0, rb1);
       __syncthreads();
+      for (int c = c_begin; c < c_end; c++) {
+        const int buf = (c - c_begin) & 1;
+        const bool more = c + 1 < c_end;
+        float na[TM][8];
+        if (more) {
+          PTDN_LOAD_A(c + 1, na);
+          PTDN_LOAD_B(c + 1, rb0, rb1);
+        }
+        const float* bs = reinterpret_cast<const float*>(Bs4[buf]) + h * 8 * LDB + nw + r;
+#pragma unroll
+        for (int kk = 0; kk < 8; kk++) {
+          float bv[TN];
+#pragma unroll
+          for (int j = 0; j < TN; j++) bv[j] = bs[kk * LDB + j * 32];
+#pragma unroll
+          for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[i][kk], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (more) {
+          PTDN_STORE_B(buf ^ 1, rb0, rb1);
+#pragma unroll
+          for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int e = 0; e < 8; e++) ra[i][e] = na[i][e];
+        }
+        __syncthreads();
+      }
     }
-  }
 #undef PTDN_LOAD_A
 #undef PTDN_LOAD_B
 #undef PTDN_STORE_B
 #undef PTDN_B_ADDR
+  } else {
+    constexpr int ROWS = 2 * HSC, UNITS = ROWS * BN, UPT = UNITS / 256;  // 16-byte units of a stage, per thread
+    static_assert(UNITS % 256 == 0, "whole units per thread");
+    __shared__ half8 Bs[2][UNITS];
+    // A fragments of the stage that starts at chunk c (zeros outside the image and past the slice's end)
+#define PTDN_HLOAD_A(c, ra)                                                                                       \
+  do {                                                                                                            \
+    _Pragma("unroll") for (int s_ = 0; s_ < HSC; s_++) {                                                          \
+      const int k0_ = ((c) + s_) * BK;                                                                            \
+      const int t_ = k0_ / a.cin, ch_ = k0_ - t_ * a.cin + h * 8;                                                 \
+      const int ky_ = t_ / a.ks, kx_ = t_ - ky_ * a.ks;                                                           \
+      _Pragma("unroll") for (int i = 0; i < TM; i++) {                                                            \
+        const int iy = iy0[i] + ky_, ix = ix0[i] + kx_;                                                           \
+        half8 v_ = {0, 0, 0, 0, 0, 0, 0, 0};                                                                      \
+        if ((c) + s_ < c_end && mv[i] && (unsigned)iy < (unsigned)a.in_h && (unsigned)ix < (unsigned)a.in_w)      \
+          v_ = *reinterpret_cast<const half8*>(a.in + ((size_t)(iyb[i] + iy) * a.in_w + ix) * a.cin + ch_);       \
+        ra[i][s_] = v_;                                                                                           \
+      }                                                                                                           \
+    }                                                                                                             \
+  } while (0)
+    // B stage: unit u = (group row, column) of the stage; rows past the slice's end are not read (nor used)
+#define PTDN_HLOAD_B(c, rb)                                                                                       \
+  do {                                                                                                            \
+    _Pragma("unroll") for (int q_ = 0; q_ < UPT; q_++) {                                                          \
+      const int u_ = tid + q_ * 256, row_ = u_ / BN, col_ = u_ - row_ * BN;                                       \
+      if (2 * (c) + row_ < 2 * c_end)                                                                             \
+        rb[q_] = *reinterpret_cast<const half8*>(a.wt + ((size_t)(2 * (c) + row_) * a.npad + nb + col_) * 8);     \
+    }                                                                                                             \
+  } while (0)
+#define PTDN_HSTORE_B(buf, rb)                                                                                    \
+  do {                                                                                                            \
+    _Pragma("unroll") for (int q_ = 0; q_ < UPT; q_++) Bs[buf][tid + q_ * 256] = rb[q_];                          \
+  } while (0)
+    if (c_begin < c_end) {
+      half8 ra[TM][HSC], rb[UPT];
+#pragma unroll
+      for (int q = 0; q < UPT; q++) rb[q] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+      PTDN_HLOAD_A(c_begin, ra);
+      PTDN_HLOAD_B(c_begin, rb);
+      PTDN_HSTORE_B(0, rb);
+      __syncthreads();
+      int buf = 0;
+      for (int c = c_begin; c < c_end; c += HSC, buf ^= 1) {
+        const bool more = c + HSC < c_end;
+        half8 na[TM][HSC];
+        if (more) {
+          PTDN_HLOAD_A(c + HSC, na);
+          PTDN_HLOAD_B(c + HSC, rb);
+        }
+        const half8* bs = Bs[buf] + h * BN + nw + r;
+#pragma unroll
+        for (int s = 0; s < HSC; s++) {
+          if (c + s < c_end) {  // uniform over the workgroup
+            half8 bv[TN];
+#pragma unroll
+            for (int j = 0; j < TN; j++) bv[j] = bs[2 * s * BN + j * 32];
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+              for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ra[i][s], bv[j], acc[i][j], 0, 0, 0);
+          }
+        }
+        if (more) {
+          PTDN_HSTORE_B(buf ^ 1, rb);
+#pragma unroll
+          for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int s = 0; s < HSC; s++) ra[i][s] = na[i][s];
+        }
+        __syncthreads();
+      }
+    }
+#undef PTDN_HLOAD_A
+#undef PTDN_HLOAD_B
+#undef PTDN_HSTORE_B
+  }
 
-  // C/D map of the 32x32 f32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+  // C/D map of the 32x32 MFMA (the same for every operand type): column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 h
 #pragma unroll
   for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -257,8 +378,9 @@ __global__ void __launch_bounds__(256) conv_kernel(ConvArgs a) {
     }
 }
 
-// Split-K: the slices' partial sums added in slice order (bit-identical from run to run), then the layer's epilogue.
-__global__ void __launch_bounds__(256) splitk_reduce_kernel(ConvArgs a, int splits) {
+// Split-K: the slices' fp32 partial sums added in slice order (bit-identical from run to run), then the layer's epilogue.
+template <class T>
+__global__ void __launch_bounds__(256) splitk_reduce_kernel(ConvArgs<T> a, int splits) {
   const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
   if (idx >= (uint32_t)a.M * (uint32_t)a.N) return;
   const int m = (int)(idx / (uint32_t)a.N), n = (int)(idx - (uint32_t)m * (uint32_t)a.N);
@@ -297,8 +419,10 @@ __global__ void __launch_bounds__(256) pre_max_kernel(const float* __restrict__ 
 // the divisor of torch 0.2/0.3, whose torch.max(t) returned a Python float.  Writes the 16-channel NHWC copy the network
 // reads (channels 14, 15 = 0) and, in place, the normalised channels 9-13 back into the frame (channels 3-8 are unchanged,
 // 0-2 are overwritten by the rgb head).  blockIdx.y = frame of the group, divided by its own maxima; x0 is [frame][pixel][16].
+// The frame receives the same fp32 values in both modes; only the workspace copy x0 is stored as T (16-byte stores).
+template <class T>
 __global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ frames, size_t frame_stride, uint32_t pixels,
-                                                       const float* __restrict__ part, int nparts, float* __restrict__ x0, int inplace) {
+                                                       const float* __restrict__ part, int nparts, T* __restrict__ x0, int inplace) {
   __shared__ float div[5];
   if (threadIdx.x < 5) {
     float m = -INFINITY;
@@ -318,15 +442,20 @@ __global__ void __launch_bounds__(256) pre_apply_kernel(float* __restrict__ fram
 #pragma unroll
   for (int k = 0; k < 5; k++) v[9 + k] = v[9 + k] / div[k];
   v[14] = v[15] = 0.0f;
-  float4* o = reinterpret_cast<float4*>(x0 + ((size_t)blockIdx.y * pixels + p) * XC);
+  constexpr int VE = 16 / sizeof(T);  // elements of a 16-byte store
+  typedef T vec __attribute__((ext_vector_type(VE)));
+  vec* o = reinterpret_cast<vec*>(x0 + ((size_t)blockIdx.y * pixels + p) * XC);
 #pragma unroll
-  for (int q = 0; q < 4; q++) o[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  for (int q = 0; q < XC / VE; q++) {
+    vec w;
+#pragma unroll
+    for (int k = 0; k < VE; k++) w[k] = to_stored<T>(v[VE * q + k]);
+    o[q] = w;
+  }
   if (inplace)
 #pragma unroll
     for (int k = 0; k < 5; k++) c[9 + k] = v[9 + k];
 }
-
-#include "pt_denoise_half.h"
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 const int kChannels[7] = {14, 32, 64, 128, 256, 512, 1024};
@@ -459,7 +588,7 @@ struct Conv {
 struct TileCfg {
   int bm, bn;
 };
-// conv_kernel<TM, TN, WM, WN> instances: 256x32, 128x64, 128x128 for large layers, 128x32 and 64x64 for small ones (+ split-K)
+// conv_kernel<T, TM, TN, WM, WN> instances: 256x32, 128x64, 128x128 for large layers, 128x32 and 64x64 for small ones (+ split-K)
 static const TileCfg kCfg[5] = {{256, 32}, {128, 64}, {128, 128}, {128, 32}, {64, 64}};
 
 // The plan table of each precision: the tile shape of a layer (the wide tile of its column class when the layer fills at
@@ -485,10 +614,10 @@ struct pt_denoiser {
   size_t esz = sizeof(float);                 // bytes of a stored activation element
   float* d_w = nullptr;                       // fp32: weights + bias/scale/shift; half: bias/scale/shift only
   _Float16* d_wh = nullptr;                   // half: the convolution weights
-  char* d_ws = nullptr;                       // activations, ws_floats elements of esz bytes
+  char* d_ws = nullptr;                       // activations, ws_elems elements of esz bytes
   float* d_partial = nullptr;
   float* d_premax = nullptr;
-  size_t ws_floats = 0, w_floats = 0, partial_floats = 0, p_floats = 0, wh_halves = 0;
+  size_t ws_elems = 0, w_floats = 0, partial_floats = 0, p_floats = 0, wh_halves = 0;
   int pre_blocks = 0;
   int max_frames = 1;                         // frames per group (pt_denoiser_reserve_frames)
   std::map<int, std::vector<Conv>> plans;     // batch_plan of each group size used so far
@@ -520,7 +649,8 @@ static void choose_tiles(Conv& c, const PlanRule& p) {
   c.cfg = pick_cfg(c, p);
   c.npad = (c.N + kCfg[c.cfg].bn - 1) / kCfg[c.cfg].bn * kCfg[c.cfg].bn;
   c.nchunks = c.K / BK;
-  // split K until about two workgroups per CU are in flight, keeping at least 8 chunks (128 of K) per slice
+  // split K until about two workgroups per CU are in flight, keeping at least PlanRule::min_chunks chunks per slice (8 =
+  // 128 of K in fp32, 16 = 256 of K in half)
   const int64_t t = conv_tiles(c, c.cfg);
   int splits = 1;
   if (t < p.target_wgs / 2) {
@@ -687,51 +817,18 @@ static const std::vector<Conv>& plan_for(pt_denoiser* d, int n) {
   return it->second;
 }
 
-static ConvArgs conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
-  ConvArgs a{};
-  const Act& in = d->acts[c.in];
-  float* ws = reinterpret_cast<float*>(d->d_ws);
-  a.in = ws + in.off;
-  a.in_h = c.in_h, a.in_w = c.in_w, a.cin = c.cin;
-  a.wt = d->d_w + c.w_off;
-  a.npad = c.npad, a.ks = c.ks, a.stride = c.stride;
-  a.out_w = c.out_w, a.out_h = c.out_h, a.M = c.M, a.N = c.N;
-  a.nchunks = c.nchunks, a.chunks_per_split = c.chunks_per_split;
-  a.partial = c.splits > 1 ? d->d_partial : nullptr;
-  a.epi = c.epi;
-  a.bias = d->d_w + c.p_off;
-  a.scale = a.bias + c.npad;
-  a.shift = a.scale + c.npad;
-  if (c.out0 >= 0) {
-    a.out0 = ws + d->acts[c.out0].off;
-    a.ld0 = d->acts[c.out0].c;
-  } else {
-    a.out0 = frame_out;
-    a.ld0 = frame_ld;
-  }
-  a.nsplit = c.nsplit;
-  if (c.out1 >= 0) {
-    a.out1 = ws + d->acts[c.out1].off;
-    a.ld1 = d->acts[c.out1].c;
-  }
-  if (c.res >= 0) a.res = ws + d->acts[c.res].off;
-  if (c.up >= 0) {
-    a.up = ws + d->acts[c.up].off;
-    a.up_h = d->acts[c.up].h, a.up_w = d->acts[c.up].w;
-  }
-  a.x0 = ws + d->acts[0].off;
-  a.frames = frames, a.out_hw = c.out_h * c.out_w;
-  a.frame_stride = frame_stride;
-  return a;
-}
-
-// The same for a half denoiser: half activations and weights, fp32 bias/scale/shift, the head's output in fp32.
-static HConvArgs hconv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
-  HConvArgs a{};
-  _Float16* ws = reinterpret_cast<_Float16*>(d->d_ws);
+// The kernel arguments of one conv for a denoiser that stores T: activations and weights of T, fp32 bias / scale / shift
+// and split-K partials, the head's output in fp32.
+template <class T>
+static ConvArgs<T> conv_args(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames) {
+  ConvArgs<T> a{};
+  T* ws = reinterpret_cast<T*>(d->d_ws);
   a.in = ws + d->acts[c.in].off;
   a.in_h = c.in_h, a.in_w = c.in_w, a.cin = c.cin;
-  a.wt = d->d_wh + c.h_off;
+  if constexpr (std::is_same<T, float>::value)
+    a.wt = d->d_w + c.w_off;
+  else
+    a.wt = d->d_wh + c.h_off;
   a.npad = c.npad, a.ks = c.ks, a.stride = c.stride;
   a.out_w = c.out_w, a.out_h = c.out_h, a.M = c.M, a.N = c.N;
   a.nchunks = c.nchunks, a.chunks_per_split = c.chunks_per_split;
@@ -745,6 +842,7 @@ static HConvArgs hconv_args(const pt_denoiser* d, const Conv& c, float* frame_ou
     a.ld0 = d->acts[c.out0].c;
   } else {
     a.rgb = frame_out;
+    if constexpr (std::is_same<T, float>::value) a.out0 = frame_out;  // head_out
     a.ld0 = frame_ld;
   }
   a.nsplit = c.nsplit;
@@ -763,49 +861,69 @@ static HConvArgs hconv_args(const pt_denoiser* d, const Conv& c, float* frame_ou
   return a;
 }
 
-// One conv of a group of `frames` frames (c from that group size's plan): its GEMM and, split, its reduction.
-static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames,
-                       hipStream_t s, int* launches) {
-  if (c.epi != EPI_ACT && kCfg[c.cfg].bn != 32)
-    return pt_fail(PT_EINVAL, "launch_conv: %s: the lateral and head epilogues need 32-column tiles", c.name.c_str());
+template <class T>
+static int launch_conv_t(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames,
+                         hipStream_t s, int* launches) {
   const dim3 grid((c.M + kCfg[c.cfg].bm - 1) / kCfg[c.cfg].bm, c.npad / kCfg[c.cfg].bn, c.splits);
-  if (d->precision == PT_DENOISE_F16) {
-    const HConvArgs a = hconv_args(d, c, frame_out, frame_ld, frame_stride, frames);
-    switch (c.cfg) {
-      case 0: hipLaunchKernelGGL((hconv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((hconv_kernel<1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((hconv_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL((hconv_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL((hconv_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
-    }
-    PTDN_HIP(hipGetLastError());
-    (*launches)++;
-    if (c.splits > 1) {
-      const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
-      hipLaunchKernelGGL(hsplitk_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
-      PTDN_HIP(hipGetLastError());
-      (*launches)++;
-    }
-    return PT_OK;
-  }
-  const ConvArgs a = conv_args(d, c, frame_out, frame_ld, frame_stride, frames);
+  const ConvArgs<T> a = conv_args<T>(d, c, frame_out, frame_ld, frame_stride, frames);
   switch (c.cfg) {
-    case 0: hipLaunchKernelGGL((conv_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL((conv_kernel<1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((conv_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((conv_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((conv_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
+    case 0: hipLaunchKernelGGL((conv_kernel<T, 2, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((conv_kernel<T, 1, 2, 4, 1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((conv_kernel<T, 2, 2, 2, 2>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((conv_kernel<T, 1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((conv_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
   }
   PTDN_HIP(hipGetLastError());
   (*launches)++;
   if (c.splits > 1) {
     const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
+    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
     PTDN_HIP(hipGetLastError());
     (*launches)++;
   }
   return PT_OK;
 }
+
+// One conv of a group of `frames` frames (c from that group size's plan): its GEMM and, split, its reduction.
+static int launch_conv(const pt_denoiser* d, const Conv& c, float* frame_out, int frame_ld, size_t frame_stride, int frames,
+                       hipStream_t s, int* launches) {
+  if (c.epi != EPI_ACT && kCfg[c.cfg].bn != 32)
+    return pt_fail(PT_EINVAL, "launch_conv: %s: the lateral and head epilogues need 32-column tiles", c.name.c_str());
+  return d->precision == PT_DENOISE_F16 ? launch_conv_t<_Float16>(d, c, frame_out, frame_ld, frame_stride, frames, s, launches)
+                                        : launch_conv_t<float>(d, c, frame_out, frame_ld, frame_stride, frames, s, launches);
+}
+
+// The pre-processing of a group of g frames: the channel maxima, then the divisions and the stored copy x0.
+template <class T>
+static int launch_pre(const pt_denoiser* d, float* frames, size_t frame_stride, uint32_t pixels, int g, int inplace, hipStream_t s) {
+  T* x0 = reinterpret_cast<T*>(d->d_ws) + d->acts[0].off;
+  hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks, g), dim3(256), 0, s, frames, frame_stride, pixels, d->d_premax);
+  PTDN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pre_apply_kernel<T>, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride, pixels, d->d_premax,
+                     d->pre_blocks, x0, inplace);
+  PTDN_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+#if PT_BUILD_EXPERIMENTS
+// Lab accessors: the host sees float32 in both modes (every half is one exactly); what it sets is rounded to nearest even,
+// saturating like every store of the half mode.
+template <class T>
+static int copy_out(const pt_denoiser* d, const Act& a, float* h_out, size_t n) {
+  std::vector<T> tmp(n);
+  PTDN_HIP(hipMemcpy(tmp.data(), d->d_ws + a.off * sizeof(T), n * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; i++) h_out[i] = (float)tmp[i];
+  return PT_OK;
+}
+template <class T>
+static int copy_in(const pt_denoiser* d, const Act& a, const float* h_in, size_t n) {
+  std::vector<T> tmp(n);
+  for (size_t i = 0; i < n; i++)
+    tmp[i] = std::is_same<T, float>::value ? (T)h_in[i] : (T)fminf(fmaxf(h_in[i], -HALF_MAX), HALF_MAX);
+  PTDN_HIP(hipMemcpy(d->d_ws + a.off * sizeof(T), tmp.data(), n * sizeof(T), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+#endif
 
 extern "C" {
 
@@ -884,7 +1002,7 @@ int pt_denoiser_create_opts(int width, int height, const void* blob, size_t byte
   d->precision = opts->precision;
   d->esz = half ? sizeof(_Float16) : sizeof(float);
   build_layers(d);
-  d->ws_floats = layout_acts(d->acts, 1, d->esz);
+  d->ws_elems = layout_acts(d->acts, 1, d->esz);
   d->partial_floats = partial_floats_of(d->convs);
   std::vector<float> w, wp;
   std::vector<_Float16> wh;
@@ -898,8 +1016,8 @@ int pt_denoiser_create_opts(int width, int height, const void* blob, size_t byte
   if (e == hipSuccess) e = hipMemcpy(d->d_w, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess && half) e = hipMalloc((void**)&d->d_wh, wh.size() * sizeof(_Float16));
   if (e == hipSuccess && half) e = hipMemcpy(d->d_wh, wh.data(), wh.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&d->d_ws, d->ws_floats * d->esz);
-  if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_floats * d->esz);
+  if (e == hipSuccess) e = hipMalloc((void**)&d->d_ws, d->ws_elems * d->esz);
+  if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_elems * d->esz);
   if (e == hipSuccess && d->partial_floats) e = hipMalloc((void**)&d->d_partial, d->partial_floats * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->d_premax, PRE_BLOCKS * 5 * sizeof(float));
   if (e == hipSuccess) e = hipEventCreate(&d->ev0);
@@ -960,12 +1078,12 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
     if ((int64_t)c.M * c.N > (int64_t)UINT32_MAX)
       return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d: layer %s has too many elements", max_frames, c.name.c_str());
   std::vector<Act> acts = d->acts;
-  const size_t ws_floats = layout_acts(acts, max_frames, d->esz);
+  const size_t ws_elems = layout_acts(acts, max_frames, d->esz);
   const size_t partial_floats = partial_floats_of(plan);
   char* ws = nullptr;
   float *partial = nullptr, *premax = nullptr;
-  hipError_t e = hipMalloc((void**)&ws, ws_floats * d->esz);
-  if (e == hipSuccess) e = hipMemset(ws, 0, ws_floats * d->esz);
+  hipError_t e = hipMalloc((void**)&ws, ws_elems * d->esz);
+  if (e == hipSuccess) e = hipMemset(ws, 0, ws_elems * d->esz);
   if (e == hipSuccess && partial_floats) e = hipMalloc((void**)&partial, partial_floats * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&premax, (size_t)max_frames * PRE_BLOCKS * 5 * sizeof(float));
   if (e == hipSuccess) e = hipDeviceSynchronize();  // the old buffers may still be in use by enqueued work
@@ -975,14 +1093,14 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
     if (partial) (void)hipFree(partial);
     if (premax) (void)hipFree(premax);
     return pt_fail(PT_EHIP, "pt_denoiser_reserve_frames: %d frames (%zu + %zu workspace elements): %s; the old workspace is kept",
-                   max_frames, ws_floats, partial_floats, hipGetErrorString(e));
+                   max_frames, ws_elems, partial_floats, hipGetErrorString(e));
   }
   (void)hipFree(d->d_ws);
   if (d->d_partial) (void)hipFree(d->d_partial);
   (void)hipFree(d->d_premax);
   d->d_ws = ws, d->d_partial = partial, d->d_premax = premax;
   d->acts = acts;
-  d->ws_floats = ws_floats, d->partial_floats = partial_floats;
+  d->ws_elems = ws_elems, d->partial_floats = partial_floats;
   d->max_frames = max_frames;
   return PT_OK;
 }
@@ -1001,25 +1119,16 @@ int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, si
     return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: rgb_stride_floats %zu < width x height x 3 = %zu", rgb_stride_floats,
                    (size_t)pixels * 3);
   hipStream_t s = (hipStream_t)hip_stream;
-  const bool half = d->precision == PT_DENOISE_F16;
-  float* x0 = reinterpret_cast<float*>(d->d_ws) + d->acts[0].off;
-  _Float16* x0h = reinterpret_cast<_Float16*>(d->d_ws) + d->acts[0].off;
   for (int f0 = 0; f0 < n_frames; f0 += d->max_frames) {
     const int g = n_frames - f0 < d->max_frames ? n_frames - f0 : d->max_frames;
     float* frames = d_frames + (size_t)f0 * frame_stride_floats;
     float* out = d_rgb ? d_rgb + (size_t)f0 * rgb_stride_floats : frames;
-    hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks, g), dim3(256), 0, s, frames, frame_stride_floats, pixels, d->d_premax);
-    PTDN_HIP(hipGetLastError());
-    if (half)
-      hipLaunchKernelGGL(hpre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
-                         d->d_premax, d->pre_blocks, x0h, d_rgb ? 0 : 1);
-    else
-      hipLaunchKernelGGL(pre_apply_kernel, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride_floats, pixels,
-                         d->d_premax, d->pre_blocks, x0, d_rgb ? 0 : 1);
-    PTDN_HIP(hipGetLastError());
+    int rc = d->precision == PT_DENOISE_F16 ? launch_pre<_Float16>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s)
+                                            : launch_pre<float>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s);
+    if (rc != PT_OK) return rc;
     d->last_launches += 2;
     for (const Conv& c : plan_for(d, g)) {
-      const int rc = launch_conv(d, c, out, d_rgb ? 3 : 14, d_rgb ? rgb_stride_floats : frame_stride_floats, g, s, &d->last_launches);
+      rc = launch_conv(d, c, out, d_rgb ? 3 : 14, d_rgb ? rgb_stride_floats : frame_stride_floats, g, s, &d->last_launches);
       if (rc != PT_OK) return rc;
     }
     d->last_groups++;
@@ -1050,15 +1159,9 @@ int pt_denoiser_denoise_frames(pt_denoiser* d, int n_frames, float* d_frames, si
 
 int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out) {
   if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_denoise: null denoiser");
-  PTDN_HIP(hipEventRecord(d->ev0, nullptr));
-  const int rc = pt_denoiser_enqueue(d, d_frame, d_rgb, nullptr);
-  if (rc != PT_OK) return rc;
-  PTDN_HIP(hipEventRecord(d->ev1, nullptr));
-  PTDN_HIP(hipEventSynchronize(d->ev1));
-  float ms = 0.0f;
-  PTDN_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-  if (ms_out) *ms_out = ms;
-  return PT_OK;
+  if (!d_frame) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue: null denoiser or frame");
+  const size_t pixels = (size_t)d->width * d->height;
+  return pt_denoiser_denoise_frames(d, 1, d_frame, pixels * 14, d_rgb, pixels * 3, ms_out);
 }
 
 #if PT_BUILD_EXPERIMENTS
@@ -1079,14 +1182,7 @@ int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PTDN_HIP(hipDeviceSynchronize());
-  if (d->precision == PT_DENOISE_F16) {  // the host sees float32 in both modes (every half is one exactly)
-    std::vector<_Float16> tmp(n);
-    PTDN_HIP(hipMemcpy(tmp.data(), d->d_ws + a.off * d->esz, n * sizeof(_Float16), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) h_out[i] = (float)tmp[i];
-    return PT_OK;
-  }
-  PTDN_HIP(hipMemcpy(h_out, d->d_ws + a.off * d->esz, n * sizeof(float), hipMemcpyDeviceToHost));
-  return PT_OK;
+  return d->precision == PT_DENOISE_F16 ? copy_out<_Float16>(d, a, h_out, n) : copy_out<float>(d, a, h_out, n);
 }
 
 int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats) {
@@ -1096,14 +1192,7 @@ int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_i
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PTDN_HIP(hipDeviceSynchronize());
-  if (d->precision == PT_DENOISE_F16) {  // rounded to nearest even, saturating like every store of the half mode
-    std::vector<_Float16> tmp(n);
-    for (size_t i = 0; i < n; i++) tmp[i] = (_Float16)fminf(fmaxf(h_in[i], -HALF_MAX), HALF_MAX);
-    PTDN_HIP(hipMemcpy(d->d_ws + a.off * d->esz, tmp.data(), n * sizeof(_Float16), hipMemcpyHostToDevice));
-    return PT_OK;
-  }
-  PTDN_HIP(hipMemcpy(d->d_ws + a.off * d->esz, h_in, n * sizeof(float), hipMemcpyHostToDevice));
-  return PT_OK;
+  return d->precision == PT_DENOISE_F16 ? copy_in<_Float16>(d, a, h_in, n) : copy_in<float>(d, a, h_in, n);
 }
 
 int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len) {
@@ -1137,7 +1226,7 @@ int pt_debug_denoiser_memory(pt_denoiser* d, int layer, uint64_t info[6]) {
   info[0] = d->esz;
   info[1] = a.off * d->esz;
   info[2] = (uint64_t)a.h * a.w * a.c * d->esz;
-  info[3] = d->ws_floats * d->esz;
+  info[3] = d->ws_elems * d->esz;
   info[4] = d->partial_floats * sizeof(float);
   info[5] = d->precision == PT_DENOISE_F16 ? d->wh_halves * sizeof(_Float16) + d->p_floats * sizeof(float) : d->w_floats * sizeof(float);
   return PT_OK;

@@ -181,8 +181,10 @@ def test_product_assembly_has_fp16_mfma_only_in_the_half_kernels_and_no_scratch(
     assert len(paths) == 1, paths
     asm = open(paths[0]).read()
     fns = _functions(asm)
-    half = {n: b for n, b in fns.items() if "hconv_kernel" in n}
-    fp32 = {n: b for n, b in fns.items() if "ptdn11conv_kernel" in n}
+    # one kernel family templated on the stored element: the Itanium mangling of the first template argument is DF16_ for
+    # _Float16 and f for float
+    half = {n: b for n, b in fns.items() if "ptdn11conv_kernelIDF16_" in n}
+    fp32 = {n: b for n, b in fns.items() if "ptdn11conv_kernelIfL" in n}
     assert len(half) == 5 and len(fp32) == 5, sorted(fns)
     for n, b in half.items():
         assert "v_mfma_f32_32x32x16_f16" in b and "v_mfma_f32_32x32x2_f32" not in b, n
@@ -190,13 +192,20 @@ def test_product_assembly_has_fp16_mfma_only_in_the_half_kernels_and_no_scratch(
     for n, b in fp32.items():
         assert "v_mfma_f32_32x32x2_f32" in b and "_f16" not in b.replace(n, ""), n
     # the saturating store: clamp in fp32 (v_med3_f32), then convert
-    for key in ("hsplitk_reduce_kernel", "hpre_apply_kernel"):
+    for key in ("splitk_reduce_kernelIDF16_", "pre_apply_kernelIDF16_"):
         (body,) = [b for n, b in fns.items() if key in n]
         assert "v_med3_f32" in body and ("v_cvt_f16_f32" in body or "v_cvt_pk_f16_f32" in body), key
+    # the mirror image: no float instance picked up the half store or a half load
+    (reduce32,) = [b for n, b in fns.items() if "splitk_reduce_kernelIfE" in n]
+    (pre32,) = [b for n, b in fns.items() if "pre_apply_kernelIfE" in n]
+    for b in list(fp32.values()) + [reduce32, pre32]:
+        name = b.split(":", 1)[0]
+        code = b.replace(name, "")
+        assert not re.search(r"v_cvt\w*_f16", code) and "v_cvt_f32_f16" not in code and "v_med3_f32" not in code, name
     # no scratch in any kernel of the file: the metadata of every half kernel says 0 bytes
     meta = re.findall(r"\.name:\s+(_ZN4ptdn\w+)\n\s+\.private_segment_fixed_size:\s+(\d+)", asm)
     names = [n for n, _ in meta]
-    for key in ("hconv_kernel", "hsplitk_reduce_kernel", "hpre_apply_kernel"):
+    for key in ("conv_kernelIDF16_", "splitk_reduce_kernelIDF16_", "pre_apply_kernelIDF16_"):
         assert any(key in n for n in names), key
     assert all(int(sz) == 0 for _, sz in meta), meta
     for n, b in half.items():
