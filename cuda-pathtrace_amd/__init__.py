@@ -215,7 +215,7 @@ if IS_LAB:
 
 
 def variants():
-    """Kernel variants compiled into the loaded library (product: 0, 6, 8, 9, 10, 13, 14; lab: 0..14)."""
+    """Kernel variants compiled into the loaded library (product: 0, 6, 8, 9, 10, 13, 14; lab adds 1-5, 7, 11, 12)."""
     out = []
     o = RendererOpts()
     for v in range(15):

@@ -35,45 +35,62 @@ int pt_fail(int code, const char* fmt, ...) {
   } while (0)
 
 struct pt_renderer {
-  int width, height, spp, threads_per_block;
-  pt_renderer_opts opts;
-  uint32_t tile_pixels;
-  uint32_t frame;
-  uint32_t* d_state;  // xorwow persistent state (Renderer::d_states), or nullptr
-  hipEvent_t ev_start, ev_stop;
-  int device;
-  int launch_variant;      // what fill_args chose for the launch being prepared
+  int width = 0, height = 0, spp = 0, threads_per_block = 0;
+  pt_renderer_opts opts{};
+  uint32_t tile_pixels = 0;
+  uint32_t frame = 0;
+  uint32_t* d_state = nullptr;  // xorwow persistent state (Renderer::d_states), or nullptr
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  int device = 0;
+  int launch_variant = 0;  // what fill_args chose for the launch being prepared
   // automatic variant choice (opts.variant == PT_VARIANT_AUTO)
-  bool auto_variant;
-  uint64_t resident_pixels; // one-lane-per-pixel lanes the device holds at four waves per SIMD
-  double waves_per_simd;    // one-lane-per-pixel waves of the tile per SIMD
-  bool small_tile;         // fewer than three one-lane-per-pixel waves per SIMD (many-sphere scenes: four lanes per pixel pay there)
-  bool spec_ok;            // variant 8's speculation has not been failing on this scene
-  uint32_t* d_fail;        // device counter written by variant 8
-  uint32_t* h_fail;        // pinned host copy, valid once ev_fail has completed
-  hipEvent_t ev_fail;
-  bool fail_pending;
-  uint32_t* d_accel;       // variant 11's grid tables (rebuilt on the device before every frame)
-  uint32_t* d_chunk;       // sample chunking (pt_kernel.hip): PT_CHUNK_WORDS words per tile pixel + one flag per pixel block; allocated
-                           // by the first launch that chunks (never for renderers whose kernels do not), or null
-  uint32_t chunks;         // how many chunks a frame of this renderer is split into when the kernel supports it (0 = off): variant 6 ...
-  uint32_t chunks13;       // ... variant 13 ...
-  uint32_t chunks_split;   // ... and the split kernels (variants 8, 9)
-  uint64_t chunk_wait_ticks;  // how long a chunk waits for its predecessor (wall-clock ticks of the device)
-  long chunk_wait_ms;         // ... the same in milliseconds (env PT_CHUNK_TIMEOUT_MS, default 4000)
-  uint32_t repaired;          // frames whose broken chunk chain pt_renderer_render repaired (pt_renderer_check reports it)
-  float* d_vertices;          // pt_renderer_set_display: the display vertices every frame also writes, or null
-  uint32_t* d_err;         // device error word (PT_DEVERR_*), raised by a kernel that could not go on correctly
-  uint32_t* h_err;         // pinned host copy, valid once ev_err has completed
-  hipEvent_t ev_err;
-  bool err_pending;        // a chunked launch's error word is on its way to h_err
-  uint32_t debug;          // PT_DEBUG_* (lab library only, env PT_LAB_DEBUG)
+  bool auto_variant = false;
+  uint64_t resident_pixels = 0;  // one-lane-per-pixel lanes the device holds at four waves per SIMD
+  double waves_per_simd = 1e9;   // one-lane-per-pixel waves of the tile per SIMD
+  bool small_tile = false;       // fewer than three one-lane-per-pixel waves per SIMD (many-sphere scenes: four lanes per pixel pay there)
+  bool spec_ok = true;           // variant 8's speculation has not been failing on this scene
+  uint32_t* d_fail = nullptr;    // device counter written by variant 8
+  uint32_t* h_fail = nullptr;    // pinned host copy, valid once ev_fail has completed
+  hipEvent_t ev_fail = nullptr;
+  bool fail_pending = false;
+  uint32_t* d_accel = nullptr;   // variant 11's grid tables (rebuilt on the device before every frame)
+  uint32_t* d_chunk = nullptr;   // sample chunking (pt_kernel.hip): PT_CHUNK_WORDS words per tile pixel + one flag per pixel block; allocated
+                                 // by the first launch that chunks (never for renderers whose kernels do not), or null
+  // how many chunks a frame of this renderer is split into when the kernel supports it (0 = off), per chunk family of the
+  // variant table: variant 6, the split kernels (variants 8, 9), the pooled grid kernel (variant 13)
+  uint32_t chunks[PT_CHUNK_FAMILIES] = {};
+  uint64_t chunk_wait_ticks = 0;  // how long a chunk waits for its predecessor (wall-clock ticks of the device)
+  long chunk_wait_ms = 0;         // ... the same in milliseconds (env PT_CHUNK_TIMEOUT_MS, default 4000)
+  uint32_t repaired = 0;          // frames whose broken chunk chain pt_renderer_render repaired (pt_renderer_check reports it)
+  float* d_vertices = nullptr;    // pt_renderer_set_display: the display vertices every frame also writes, or null
+  uint32_t* d_err = nullptr;      // device error word (PT_DEVERR_*), raised by a kernel that could not go on correctly
+  uint32_t* h_err = nullptr;      // pinned host copy, valid once ev_err has completed
+  hipEvent_t ev_err = nullptr;
+  bool err_pending = false;       // a chunked launch's error word is on its way to h_err
+  uint32_t debug = 0;             // PT_DEBUG_* (lab library only, env PT_LAB_DEBUG)
   // The renderer owns single-instance device scratch (generator state, d_accel, d_fail): launches of one
   // renderer must execute in submission order even when the caller alternates streams.
-  hipEvent_t ev_last;      // recorded after every launch on the stream it went to
-  hipStream_t last_stream;
-  bool have_last;
+  hipEvent_t ev_last = nullptr;   // recorded after every launch on the stream it went to
+  hipStream_t last_stream = nullptr;
+  bool have_last = false;
 };
+
+// the chunk count of the variant's chunk family (0: the variant belongs to none)
+static uint32_t chunks_of(const pt_renderer* r, int variant) {
+  const int family = pt_kernel_variant(variant).chunk_family;
+  return family == PT_CHUNK_NONE ? 0u : r->chunks[family];
+}
+static void chunks_off(pt_renderer* r) {
+  for (uint32_t& c : r->chunks) c = 0u;
+}
+
+// the numbers of the variants whose property `has` is `want`, as "0, 6, 8": the lists in messages follow the variant table
+static const char* variant_list(char (&buf)[64], bool VariantInfo::*has, bool want = true) {
+  buf[0] = 0;
+  for (int v = 0, at = 0; v < pt_kernel_num_variants(); v++)
+    if (pt_kernel_variant(v).*has == want) at += snprintf(buf + at, sizeof(buf) - (size_t)at, at ? ", %d" : "%d", v);
+  return buf;
+}
 
 // Order this launch after the renderer's previous one if that went to a different stream.
 static int order_after_last(pt_renderer* r, hipStream_t stream) {
@@ -161,9 +178,9 @@ static int effective_variant(pt_renderer* r, int n_spheres) {
   const bool planar = r->opts.layout == PT_LAYOUT_PLANAR;
   const bool ref = pt_kernel_ref_bounces(n_spheres, r->opts.max_bounces, 9, planar) != 0;
   uint32_t chunked_mask = 0u;
-  for (int v : {6, 8, 9}) {
-    const uint32_t c = v == 6 ? r->chunks : r->chunks_split;
-    if (c >= 2u && pt_kernel_chunked(v, n_spheres, r->opts.max_bounces, planar, r->spp, c)) chunked_mask |= 1u << v;
+  for (const KernelCost& k : kKernelCost[0]) {  // (the candidates of cheapest_variant)
+    const uint32_t c = chunks_of(r, k.variant);
+    if (c >= 2u && pt_kernel_chunked(k.variant, n_spheres, r->opts.max_bounces, planar, r->spp, c)) chunked_mask |= 1u << k.variant;
   }
   return cheapest_variant(r->opts.rng_mode, r->waves_per_simd, r->spp, r->opts.max_bounces > 0 ? r->opts.max_bounces : 1, ref, chunked_mask);
 }
@@ -184,6 +201,50 @@ static uint32_t fit_chunks(int want, int spp, int max_samples) {
   while (want >= 2 && want < PT_CHUNKS_MAX && (spp + want - 1) / want > max_samples) want *= 2;
   if (want < 2 || want > PT_CHUNKS_MAX || (spp + want - 1) / want > max_samples) return 0u;
   return (uint32_t)want;
+}
+
+// The chunk counts of a new renderer, one per chunk family.
+// Sample chunking pays on frames that make few rounds of long workgroups (tools/shape_sweep.py): at least 512 samples per
+// pixel and at most 8 one-lane waves per SIMD slot-round.  opts.chunks / env PT_CHUNKS: 0 = this policy, 1 = never, n = n chunks.
+// The hand-over buffer (104 B per tile pixel) is allocated by the first launch that really chunks (chunk_buffer()).
+static void set_chunk_counts(pt_renderer* r, const hipDeviceProp_t& prop) {
+  // opts.chunks / env PT_CHUNKS, one reading for all three kernel families: 0 = the policies below, 1 = never, n = n chunks
+  const int asked = requested_chunks(r->opts.chunks);
+  int want = asked;
+  if (want == 0 && r->spp >= 512 && r->tile_pixels > 0) {
+    const uint64_t slots = (uint64_t)prop.multiProcessorCount * 4u * 4u * 64u;  // pixels resident at 4 waves per SIMD
+    // The whole frame: two chunks (one hand-over per pixel; 49.95 -> 49.48 ms, eight: 49.40).  Row tiles -- what a rank of a multi-GPU
+    // run renders -- are one or two rounds of waves and gain more from more chunks (tools/chunk_tile.py, profiles/r03/README.md;
+    // chunks 1 / 2 / 4 / 6 / 8): 1/4 frame 13.03 / 13.31 / 12.71 / 13.03 / 12.62 ms, 1/2 frame 25.50 / 25.28 / 25.39 / 25.58 / 24.89,
+    // 3/16 frame 10.31 / 10.05 / 10.15 / 9.81 / 10.61 (the steps: chunks x waves per SIMD against the five resident).
+    if ((uint64_t)r->tile_pixels <= 8u * slots)
+      want = r->waves_per_simd > 8.5 ? PT_CHUNKS : (r->waves_per_simd > 3.25 ? PT_CHUNKS_TILE : PT_CHUNKS_SMALL_TILE);
+  }
+  r->chunks[PT_CHUNK_ONE_LANE] = fit_chunks(want, r->spp, PT_CHUNK_MAX_SAMPLES);
+  // The pooled grid kernel (variant 13): 512-pixel workgroups, two resident per CU, 25 ms each at 1000 spheres x 256 spp --
+  // a 1024^2 frame is FOUR rounds of them and its time is whatever the last round's stragglers make it (measured: 98 or 107 ms
+  // from one frame to the next, profiles/r03/README.md).  Enough chunks for about thirty-two rounds, each at least 32 samples
+  // long (closed / open at 256 spp, chunks 1: 98-109 / 38.4 ms, 2: 101.5 / 36.4, 4: 97.3 / 35.4, 8: 96.0 / 35.1, 16: 97.9 / 36.3).
+  // Its samples are a hundred times as long as the nine-sphere kernel's (about 0.1 ms per sample and workgroup at 1000
+  // spheres), so a chunk is capped at PT_CHUNK_MAX_SAMPLES_GRID samples: the worst chained wait -- all chunks of a block
+  // co-resident, chunk k waits k chunk durations -- stays a fraction of a second.
+  int want13 = asked;
+  if (want13 == 0 && r->tile_pixels > 0) {
+    const uint64_t resident = (uint64_t)prop.multiProcessorCount * 2u;  // workgroups
+    const uint64_t groups = ((uint64_t)r->tile_pixels + 511u) / 512u;
+    const uint64_t rounds = (groups + resident - 1) / resident;
+    want13 = rounds >= 32 ? 1 : (int)((32 + rounds - 1) / rounds);
+    if (want13 > PT_CHUNKS_GRID_MAX) want13 = PT_CHUNKS_GRID_MAX;
+    while (want13 >= 2 && r->spp / want13 < 32) want13 /= 2;
+    // Round 5: a tile whose workgroups fill at most HALF the chip's slots gains nothing from chunk workgroups -- they are resident
+    // at once and only wait for their predecessors, in slots the working ones could have had to themselves (rows 512..640 of
+    // the 1000-sphere frame, closed / open: 8 chunks 29.1 / 19.1 ms, none 17.9 / 10.4; profiles/r05/cfg4_tile_chunks.txt)
+    if (groups * 2u <= resident) want13 = 1;
+  }
+  r->chunks[PT_CHUNK_GRID] = fit_chunks(want13, r->spp, PT_CHUNK_MAX_SAMPLES_GRID);
+  // the split kernels (small tiles of the reference configuration: one or two rounds of waves by construction): four chunks
+  // (tools/chunk_tile.py, profiles/r03/tile_policy_bitops.txt)
+  r->chunks[PT_CHUNK_SPLIT] = fit_chunks(asked == 0 && r->spp >= 512 ? PT_CHUNKS_SPLIT : asked, r->spp, PT_CHUNK_MAX_SAMPLES);
 }
 
 extern "C" {
@@ -292,9 +353,11 @@ int pt_renderer_create(int width, int height, int samples_per_pixel, int threads
     return pt_fail(PT_EINVAL, "pt_renderer_create: fast_math has one kernel; leave variant at -1");
   if (o.chunks < 0 || o.chunks > PT_CHUNKS_MAX || o.reserved != 0)
     return pt_fail(PT_EINVAL, "pt_renderer_create: chunks %d (0 = automatic, 1 = off, 2..%d), reserved %d (must be 0)", o.chunks, PT_CHUNKS_MAX, o.reserved);
-  if (o.variant != PT_VARIANT_AUTO && !pt_kernel_has_variant(o.variant))
-    return pt_fail(PT_EINVAL, "pt_renderer_create: kernel variant %d is not in this build (product variants: 0, 6, 8, 9, 10, 13; "
-                              "the experiments 1-5, 7, 11, 12 live in libptcore_lab.so)", o.variant);
+  if (o.variant != PT_VARIANT_AUTO && !pt_kernel_has_variant(o.variant)) {
+    char product[64], lab[64];
+    return pt_fail(PT_EINVAL, "pt_renderer_create: kernel variant %d is not in this build (product variants: %s; the experiments %s live in libptcore_lab.so)",
+                   o.variant, variant_list(product, &VariantInfo::product), variant_list(lab, &VariantInfo::product, false));
+  }
   // 32-bit pixel ids like the reference (pathtrace.cu:206): width*height must fit uint32
   if ((uint64_t)width * (uint64_t)height > 0xFFFFFFFFull) return pt_fail(PT_EINVAL, "pt_renderer_create: image too large");
 
@@ -310,38 +373,10 @@ int pt_renderer_create(int width, int height, int samples_per_pixel, int threads
   r->threads_per_block = threads_per_block;
   r->opts = o;
   r->tile_pixels = (uint32_t)(o.row_end - o.row_begin) * (uint32_t)width;
-  r->frame = 0;
-  r->d_state = nullptr;
-  r->ev_start = r->ev_stop = nullptr;
   r->auto_variant = (o.variant == PT_VARIANT_AUTO);
-  r->small_tile = false;
-  r->resident_pixels = 0;
-  r->waves_per_simd = 1e9;
-  r->spec_ok = true;
-  r->d_fail = nullptr;
-  r->h_fail = nullptr;
-  r->ev_fail = nullptr;
-  r->fail_pending = false;
-  r->d_accel = nullptr;
-  r->d_chunk = nullptr;
-  r->chunks = 0;
-  r->chunks13 = 0;
-  r->chunks_split = 0;
-  r->chunk_wait_ticks = 0;
-  r->chunk_wait_ms = 0;
-  r->repaired = 0;
-  r->d_vertices = nullptr;
-  r->d_err = nullptr;
-  r->h_err = nullptr;
-  r->ev_err = nullptr;
-  r->err_pending = false;
-  r->debug = 0;
-  r->ev_last = nullptr;
-  r->last_stream = nullptr;
-  r->have_last = false;
   hipError_t e = hipGetDevice(&r->device);
+  hipDeviceProp_t prop;
   if (e == hipSuccess) {
-    hipDeviceProp_t prop;
     e = hipGetDeviceProperties(&prop, r->device);
     if (e == hipSuccess) {
       const uint64_t simds = (uint64_t)prop.multiProcessorCount * 4u;
@@ -355,51 +390,8 @@ int pt_renderer_create(int width, int height, int samples_per_pixel, int threads
   if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_fail, sizeof(uint32_t), hipHostMallocDefault);
   if (e == hipSuccess) { *r->h_fail = 0; e = hipEventCreateWithFlags(&r->ev_fail, hipEventDisableTiming); }
   if (e == hipSuccess) e = hipMalloc((void**)&r->d_accel, pt_kernel_accel_bytes());
-  // Sample chunking pays on frames that make few rounds of long workgroups (tools/shape_sweep.py): at least 512 samples per
-  // pixel and at most 8 one-lane waves per SIMD slot-round.  opts.chunks / env PT_CHUNKS: 0 = this policy, 1 = never, n = n chunks.
-  // The hand-over buffer (104 B per tile pixel) is allocated by the first launch that really chunks (chunk_buffer()).
   if (e == hipSuccess) {
-    // opts.chunks / env PT_CHUNKS, one reading for all three kernel families: 0 = the policies below, 1 = never, n = n chunks
-    const int asked = requested_chunks(o.chunks);
-    hipDeviceProp_t prop;
-    const bool have_prop = hipGetDeviceProperties(&prop, r->device) == hipSuccess;
-    int want = asked;
-    if (want == 0 && r->spp >= 512 && r->tile_pixels > 0 && have_prop) {
-      const uint64_t slots = (uint64_t)prop.multiProcessorCount * 4u * 4u * 64u;  // pixels resident at 4 waves per SIMD
-      // The whole frame: two chunks (one hand-over per pixel; 49.95 -> 49.48 ms, eight: 49.40).  Row tiles -- what a rank of a multi-GPU
-      // run renders -- are one or two rounds of waves and gain more from more chunks (tools/chunk_tile.py, profiles/r03/README.md;
-      // chunks 1 / 2 / 4 / 6 / 8): 1/4 frame 13.03 / 13.31 / 12.71 / 13.03 / 12.62 ms, 1/2 frame 25.50 / 25.28 / 25.39 / 25.58 / 24.89,
-      // 3/16 frame 10.31 / 10.05 / 10.15 / 9.81 / 10.61 (the steps: chunks x waves per SIMD against the five resident).
-      if ((uint64_t)r->tile_pixels <= 8u * slots)
-        want = r->waves_per_simd > 8.5 ? PT_CHUNKS : (r->waves_per_simd > 3.25 ? PT_CHUNKS_TILE : PT_CHUNKS_SMALL_TILE);
-    }
-    r->chunks = fit_chunks(want, r->spp, PT_CHUNK_MAX_SAMPLES);
-    // The pooled grid kernel (variant 13): 512-pixel workgroups, two resident per CU, 25 ms each at 1000 spheres x 256 spp --
-    // a 1024^2 frame is FOUR rounds of them and its time is whatever the last round's stragglers make it (measured: 98 or 107 ms
-    // from one frame to the next, profiles/r03/README.md).  Enough chunks for about thirty-two rounds, each at least 32 samples
-    // long (closed / open at 256 spp, chunks 1: 98-109 / 38.4 ms, 2: 101.5 / 36.4, 4: 97.3 / 35.4, 8: 96.0 / 35.1, 16: 97.9 / 36.3).
-    // Its samples are a hundred times as long as the nine-sphere kernel's (about 0.1 ms per sample and workgroup at 1000
-    // spheres), so a chunk is capped at PT_CHUNK_MAX_SAMPLES_GRID samples: the worst chained wait -- all chunks of a block
-    // co-resident, chunk k waits k chunk durations -- stays a fraction of a second.
-    {
-      int want13 = asked;
-      if (want13 == 0 && r->tile_pixels > 0 && have_prop) {
-        const uint64_t resident = (uint64_t)prop.multiProcessorCount * 2u;  // workgroups
-        const uint64_t groups = ((uint64_t)r->tile_pixels + 511u) / 512u;
-        const uint64_t rounds = (groups + resident - 1) / resident;
-        want13 = rounds >= 32 ? 1 : (int)((32 + rounds - 1) / rounds);
-        if (want13 > PT_CHUNKS_GRID_MAX) want13 = PT_CHUNKS_GRID_MAX;
-        while (want13 >= 2 && r->spp / want13 < 32) want13 /= 2;
-        // Round 5: a tile whose workgroups fill at most HALF the chip's slots gains nothing from chunk workgroups -- they are resident
-        // at once and only wait for their predecessors, in slots the working ones could have had to themselves (rows 512..640 of
-        // the 1000-sphere frame, closed / open: 8 chunks 29.1 / 19.1 ms, none 17.9 / 10.4; profiles/r05/cfg4_tile_chunks.txt)
-        if (groups * 2u <= resident) want13 = 1;
-      }
-      r->chunks13 = fit_chunks(want13, r->spp, PT_CHUNK_MAX_SAMPLES_GRID);
-    }
-    // the split kernels (small tiles of the reference configuration: one or two rounds of waves by construction): four chunks
-    // (tools/chunk_tile.py, profiles/r03/tile_policy_bitops.txt)
-    r->chunks_split = fit_chunks(asked == 0 && r->spp >= 512 ? PT_CHUNKS_SPLIT : asked, r->spp, PT_CHUNK_MAX_SAMPLES);
+    set_chunk_counts(r, prop);
     int khz = 0;  // s_memrealtime ticks per millisecond
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->device) != hipSuccess || khz <= 0) khz = 100000;
     long wait_ms = 4000;
@@ -455,10 +447,6 @@ int pt_renderer_destroy(pt_renderer* r) {
 // Does a launch of this renderer with this variant and scene chain a pixel's samples through several workgroups?  Allocates the
 // hand-over buffer the first time the answer is yes; an allocation failure turns chunking off for good (it is a scheduling
 // aid, never a reason for a renderer not to work).
-static uint32_t chunks_of(const pt_renderer* r, int variant) {
-  return (variant == 13 || variant == 14) ? r->chunks13 : (variant == 8 || variant == 9) ? r->chunks_split : r->chunks;
-}
-
 static bool chunk_buffer(pt_renderer* r, int variant, int n_spheres) {
   const uint32_t chunks = chunks_of(r, variant);
   if (chunks < 2u || !pt_kernel_chunked(variant, n_spheres, r->opts.max_bounces, r->opts.layout == PT_LAYOUT_PLANAR, r->spp, chunks))
@@ -468,9 +456,7 @@ static bool chunk_buffer(pt_renderer* r, int variant, int n_spheres) {
   if (hipMalloc((void**)&r->d_chunk, ((size_t)PT_CHUNK_WORDS * r->tile_pixels + blocks) * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();  // not sticky: the launch that follows must not inherit it
     r->d_chunk = nullptr;
-    r->chunks = 0;
-    r->chunks13 = 0;
-    r->chunks_split = 0;
+    chunks_off(r);
     return false;
   }
   return true;
@@ -489,9 +475,7 @@ static int take_device_error(pt_renderer* r, bool wait, uint32_t* err) {
   if (*err == 0u) return PT_OK;
   *r->h_err = 0u;
   PT_HIP(hipMemset(r->d_err, 0, sizeof(uint32_t)));
-  r->chunks = 0;
-  r->chunks13 = 0;
-  r->chunks_split = 0;
+  chunks_off(r);
   return PT_OK;
 }
 
@@ -558,7 +542,7 @@ static hipError_t launch(pt_renderer* r, const PixelKernelArgs& a, hipStream_t s
 }
 
 static int watch_begin(pt_renderer* r, hipStream_t stream, bool* watching) {
-  *watching = r->auto_variant && (r->launch_variant == 8 || r->launch_variant == 9) && !r->fail_pending;
+  *watching = r->auto_variant && pt_kernel_variant(r->launch_variant).split() && !r->fail_pending;
   if (*watching) PT_HIP(hipMemsetAsync(r->d_fail, 0, sizeof(uint32_t), stream));
   return PT_OK;
 }
@@ -647,7 +631,7 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
     rc = order_after_last(r, (hipStream_t)hip_stream);
     if (rc != PT_OK) break;
     {
-      const hipError_t e = pt_launch_frames_kernel(fa, r->opts.rng_mode, (hipStream_t)hip_stream);
+      const hipError_t e = pt_launch_frames_kernel(fa, r->opts.rng_mode, variant, (hipStream_t)hip_stream);
       if (e != hipSuccess) { rc = pt_fail(PT_EHIP, "pt_renderer_enqueue_frames: %s", hipGetErrorString(e)); break; }
     }
     rc = mark_last(r, (hipStream_t)hip_stream);
@@ -721,48 +705,39 @@ int pt_renderer_check(pt_renderer* r, int wait, uint32_t* repaired_frames) {
 // The reference's interactive loop renders a resting camera's frame again and again from fresh samples (main.cu:146-177,
 // pathtrace.cu:212-256); a session adds samples to one frame instead.  Its record holds each pixel's whole state between passes.
 struct pt_progressive {
-  pt_renderer* r;
-  uint32_t* d_rec;            // PT_CHUNK_WORDS words per tile pixel, [word][pixel] (pixel_kernel RESUME), or null for an empty tile
-  int64_t samples;            // samples per pixel so far
-  float cam[15];              // the first pass's basis and eye ...
-  const pt_sphere* spheres;   // ... and scene: later passes must bring the same
-  int n_spheres;
-  hipEvent_t ev_start, ev_stop;
+  pt_renderer* r = nullptr;
+  uint32_t* d_rec = nullptr;            // PT_CHUNK_WORDS words per tile pixel, [word][pixel] (pixel_kernel RESUME), or null for an empty tile
+  int64_t samples = 0;                  // samples per pixel so far
+  float cam[15] = {};                   // the first pass's basis and eye ...
+  const pt_sphere* spheres = nullptr;   // ... and scene: later passes must bring the same
+  int n_spheres = 0;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // adaptive sampling (pt_progressive_set_adaptive, pt_adaptive.hip): off unless d_adaptive is set
-  void* d_adaptive;           // one allocation: counts, list, mask, block sums, words (AdaptiveState)
-  AdaptiveState ast;
-  AdaptiveRule rule;
-  pt_adaptive_opts opts;
-  bool forced;                // the next pass takes mask bit 0 as it is (lab library: pt_debug_progressive_set_active)
+  void* d_adaptive = nullptr;           // one allocation: counts, list, mask, block sums, words (AdaptiveState)
+  AdaptiveState ast{};
+  AdaptiveRule rule{};
+  pt_adaptive_opts opts{};
+  bool forced = false;                  // the next pass takes mask bit 0 as it is (lab library: pt_debug_progressive_set_active)
 };
 
-// the automatic policy's choice restricted to the kernels with a resume build: where it would pick 8 or 9, variant 6
+// the automatic policy's choice restricted to the kernels with a resume build: where it would pick a split kernel, variant 6
 static int session_variant(pt_renderer* r, int n_spheres) {
   const int v = effective_variant(r, n_spheres);
-  return (v == 8 || v == 9) ? 6 : v;
+  return pt_kernel_variant(v).split() ? PT_DEFAULT_VARIANT : v;
 }
 
 int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
   if (!out) return pt_fail(PT_EINVAL, "pt_progressive_create: out is NULL");
   *out = nullptr;
   if (!r) return pt_fail(PT_EINVAL, "pt_progressive_create: renderer is NULL");
-  if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants 6, 10, 13, 14)");
+  char resume[64];
+  variant_list(resume, &VariantInfo::resume);
+  if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants %s)", resume);
   if (!r->auto_variant && !pt_kernel_has_resume(r->opts.variant))
-    return pt_fail(PT_EINVAL, "pt_progressive_create: kernel variant %d has no progressive passes (resume builds: variants 6, 10, 13, 14)", r->opts.variant);
+    return pt_fail(PT_EINVAL, "pt_progressive_create: kernel variant %d has no progressive passes (resume builds: variants %s)", r->opts.variant, resume);
   pt_progressive* p = new (std::nothrow) pt_progressive();
   if (!p) return pt_fail(PT_ENOMEM, "pt_progressive_create: out of host memory");
   p->r = r;
-  p->d_rec = nullptr;
-  p->samples = 0;
-  memset(p->cam, 0, sizeof(p->cam));
-  p->spheres = nullptr;
-  p->n_spheres = 0;
-  p->ev_start = p->ev_stop = nullptr;
-  p->d_adaptive = nullptr;
-  memset(&p->ast, 0, sizeof(p->ast));
-  memset(&p->rule, 0, sizeof(p->rule));
-  memset(&p->opts, 0, sizeof(p->opts));
-  p->forced = false;
   hipError_t e = hipSuccess;
   if (r->tile_pixels) e = hipMalloc((void**)&p->d_rec, (size_t)PT_CHUNK_WORDS * r->tile_pixels * sizeof(uint32_t));
   if (e == hipSuccess) e = hipEventCreate(&p->ev_start);
@@ -1127,12 +1102,11 @@ int pt_renderer_kernel_info(pt_renderer* r, int n_spheres, pt_kernel_info* info)
                                         : pt_kernel_symbol(r->opts.rng_mode, variant, n_spheres, r->opts.max_bounces,
                                                            r->opts.layout == PT_LAYOUT_PLANAR)));
   const int block = fast ? PT_BLOCK_THREADS : pt_kernel_block_threads(variant);
+  const int lanes = fast ? 1 : pt_kernel_variant(variant).lanes;  // per pixel
   info->block_threads = block;
-  info->grid_blocks = (int)((r->tile_pixels + block - 1) / block);
+  info->grid_blocks = (int)(((uint64_t)r->tile_pixels * (uint64_t)lanes + block - 1) / block);
   info->lds_bytes = (int)(fast ? pt_fast_kernel_lds_bytes(n_spheres) : pt_kernel_lds_bytes(n_spheres, variant));
   info->variant = variant;
-  if (variant == 8 || variant == 9)
-    info->grid_blocks = (int)(((uint64_t)r->tile_pixels * (variant == 8 ? 4 : 2) + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
   if (!fast && chunks_of(r, variant) >= 2u &&
       pt_kernel_chunked(variant, n_spheres, r->opts.max_bounces, r->opts.layout == PT_LAYOUT_PLANAR, r->spp, chunks_of(r, variant)))
     info->grid_blocks *= (int)chunks_of(r, variant);  // sample chunking: that many workgroups per pixel block

@@ -204,10 +204,32 @@ struct AdaptiveKernelArgs : ResumeKernelArgs {
 #define PT_DEBUG_DROP_CHUNK_FLAG 1u  // pixel block 0, chunk 0 does not publish its flag (tests/test_chunk_chain_gpu.py)
 
 #ifndef PT_BUILD_EXPERIMENTS
-#define PT_BUILD_EXPERIMENTS 0  // 1: also build variants 1-5, 7, 9, 12 (libptcore_lab.so)
+#define PT_BUILD_EXPERIMENTS 0  // 1: also build the lab variants 1-5, 7, 11, 12 (libptcore_lab.so)
 #endif
 #define PT_VARIANT_FAST 100     // reported by pt_renderer_kernel_info for a fast_math renderer (pt_fast.hip)
 #define PT_FAST_LDS_SPHERES 64  // the fast kernel stages scenes up to this size into LDS, larger ones are read in place
+// What the host knows about a kernel variant.  The table of these rows (kVariants, pt_kernel.hip) is the ONE place where a
+// variant number means something: the selector, the launchers and pt_capi.hip read the row, none compares numbers.
+enum { PT_LEAN_NEVER, PT_LEAN_BIG, PT_LEAN_ALWAYS };  // LDS layout (pt_scene_lds.h): lean above PT_SCREEN_MAX_SPHERES / always
+enum { PT_LDS_PLAIN, PT_LDS_PACKED, PT_LDS_WALLS };   // beside the scene image: a packed FP32 copy (variant 3), the wall block (6)
+enum { PT_GRID_NONE, PT_GRID_LANE, PT_GRID_POOLED };  // walks the uniform grid, every lane for itself / tests pooled per wave
+enum { PT_CHUNK_NONE = -1, PT_CHUNK_ONE_LANE, PT_CHUNK_SPLIT, PT_CHUNK_GRID, PT_CHUNK_FAMILIES };  // whose chunk-count policy (pt_capi.hip)
+struct VariantInfo {
+  bool product;       // in libptcore.so (every variant is in libptcore_lab.so)
+  int lanes;          // lanes per pixel: 1, or 2 / 4 in the split kernels (pixel_kernel_split)
+  int threads;        // workgroup size
+  int lean;           // PT_LEAN_*
+  int lds_extra;      // PT_LDS_*
+  int grid;           // PT_GRID_*
+  bool wide;          // ... in 1024-thread workgroups under the wide LDS budget
+  bool ref_builds;    // has builds for the reference configurations (9 spheres, 5 or 8 bounces as constants)
+  bool resume;        // has resume and adaptive builds (progressive passes)
+  bool frames;        // has frames builds (of its reference configurations)
+  int chunk_family;   // PT_CHUNK_*
+  bool can_chunk;     // launches may chain a pixel's samples through several workgroups (pt_kernel_chunked)
+  constexpr bool split() const { return lanes > 1; }
+};
+const VariantInfo& pt_kernel_variant(int variant);  // (a number outside the table: a row that is in no build and has no property)
 int pt_kernel_num_variants(void);
 bool pt_kernel_chunked(int variant, int n_spheres, int max_bounces, bool planar, int spp, uint32_t chunks);
 int pt_kernel_ref_bounces(int n_spheres, int max_bounces, int variant, bool planar);  // bounce cap of the reference-configuration build a launch runs, 0 = generic build
@@ -219,8 +241,8 @@ int pt_kernel_max_spheres(int variant);
 hipError_t pt_launch_pixel_kernel(const PixelKernelArgs& a, int rng_mode, int variant, hipStream_t stream);
 // frame batches: is there a kernel for these launch parameters (reference scene, variant 6, interleaved layout), and the launch
 bool pt_kernel_has_frames(int variant, int n_spheres, int max_bounces, bool planar);
-hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, hipStream_t stream);
-// progressive passes: the resume builds of variants 6 (reference configurations included), 10, 13 and 14
+hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, int variant, hipStream_t stream);
+// progressive passes: the resume builds (VariantInfo::resume)
 bool pt_kernel_has_resume(int variant);
 const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar);
 hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream);

@@ -1015,83 +1015,129 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS)
 }  // namespace pt
 
 // ---- launchers (host) ---------------------------------------------------------------------
+#include <utility>
+
+// The kernel variants, one row each (VariantInfo, pt_kernel.h; what the variants are: the list there).  A new variant or a new
+// build flavour is registered HERE: the selector, the launchers and pt_capi.hip follow the row.
+static constexpr int kNumVariants = 15;
+static constexpr int kT = PT_BLOCK_THREADS, kTG = PT_GRID_BLOCK_THREADS, kTW = PT_GRID_WIDE_THREADS;
+static constexpr VariantInfo kVariants[kNumVariants] = {
+    //        product lanes threads lean        LDS extra      grid            wide   ref    resume frames chunk family       can chunk
+    /*  0 */ {true,  1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    // 1-5, 7: measured negative results and stepping stones
+    /*  1 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  2 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  3 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PACKED, PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  4 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  5 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  6 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_WALLS,  PT_GRID_NONE,   false, true,  true,  true,  PT_CHUNK_ONE_LANE, true},
+    /*  7 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /*  8 */ {true,  4, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true},
+    /*  9 */ {true,  2, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true},
+    /* 10 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, true,  false, PT_CHUNK_NONE,     false},
+    // 11 (the grid walk with every lane testing its own spheres) and 12: superseded by 13, kept for A/B
+    /* 11 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /* 12 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false},
+    /* 13 */ {true,  1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, false, false, true,  false, PT_CHUNK_GRID,     true},
+    // 14 cannot chunk: the host has never chunked it, although its kernel (variant 13's) could and its sample cap is the grid family's
+    /* 14 */ {true,  1, kTW, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, true,  false, true,  false, PT_CHUNK_GRID,     false},
+};
+static constexpr VariantInfo kNoVariant = {false, 1, kT, PT_LEAN_NEVER, PT_LDS_PLAIN, PT_GRID_NONE, false, false, false, false, PT_CHUNK_NONE, false};
+
+const VariantInfo& pt_kernel_variant(int variant) { return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : kNoVariant; }
+int pt_kernel_num_variants(void) { return kNumVariants; }
+int pt_kernel_block_threads(int variant) { return pt_kernel_variant(variant).threads; }
+bool pt_kernel_has_variant(int variant) { return variant >= 0 && variant < kNumVariants && (PT_BUILD_EXPERIMENTS || kVariants[variant].product); }
+bool pt_kernel_has_resume(int variant) { return pt_kernel_variant(variant).resume; }
+
 // LDS layout of a launch (pt_scene_lds.h): many-sphere scenes keep only the geometry in LDS
 // (variants 6, 8 and 10 -- the ones the automatic policy uses -- are also built for that layout)
-static inline bool lds_lean(int n, int variant) {
-  return variant == 11 || variant == 12 || variant == 13 || variant == 14 || (n > PT_SCREEN_MAX_SPHERES && (variant == 6 || variant == 8 || variant == 10));
-}
-static inline bool is_split(int variant) { return variant == 8 || variant == 9; }
-static inline size_t scene_lds_f4(int n, int variant) {
-  if (lds_lean(n, variant)) return pt::kTablesF4;  // the lean builds read the caller's array directly: only the small tables
-  return (size_t)n * 4 + pt::kTablesF4 + (variant == 3 ? (size_t)((n + 1) / 2) * 2 : variant == 6 ? (size_t)pt::kWallF4 : 0);  // geometry, two material slots, the eye image, the unit-length table, the wall block (variant 6)
+static inline bool lds_lean(int n, const VariantInfo& v) { return v.lean == PT_LEAN_ALWAYS || (v.lean == PT_LEAN_BIG && n > PT_SCREEN_MAX_SPHERES); }
+static inline size_t scene_lds_f4(int n, const VariantInfo& v) {
+  if (lds_lean(n, v)) return pt::kTablesF4;  // the lean builds read the caller's array directly: only the small tables
+  return (size_t)n * 4 + pt::kTablesF4 +  // geometry, two material slots, the eye image, the unit-length table, the wall block (variant 6)
+         (v.lds_extra == PT_LDS_PACKED ? (size_t)((n + 1) / 2) * 2 : v.lds_extra == PT_LDS_WALLS ? (size_t)pt::kWallF4 : 0);
 }
 // what follows the scene image: one 64 x 14 float transpose slice per wave for the epilogue, or the
 // split kernels' exchange records
-static inline size_t tail_lds_bytes(int n, int variant) {
-  if (variant == 11 || variant == 12) return n <= pt::kGridMaxSpheres ? pt::grid_lds_bytes(n, false) : 64;  // geometry + grid tables instead of the epilogue slice
-  if (variant == 13 || variant == 14) {  // + per wave the test ring and the owners' result slots
-    const int threads = variant == 14 ? PT_GRID_WIDE_THREADS : PT_GRID_BLOCK_THREADS;
-    return (n <= pt::kGridMaxSpheres ? ((pt::grid_lds_bytes(n, true, threads) + 15) & ~(size_t)15) : 64) + (threads / 64) * pt::kPoolWaveBytes;
-  }
-  if (is_split(variant)) return (PT_BLOCK_THREADS / 64) * 64 * pt::kRecWords * sizeof(float);
+static inline size_t tail_lds_bytes(int n, const VariantInfo& v) {
+  if (v.grid == PT_GRID_LANE) return n <= pt::kGridMaxSpheres ? pt::grid_lds_bytes(n, false) : 64;  // geometry + grid tables instead of the epilogue slice
+  if (v.grid == PT_GRID_POOLED)  // + per wave the test ring and the owners' result slots
+    return (n <= pt::kGridMaxSpheres ? ((pt::grid_lds_bytes(n, true, v.threads) + 15) & ~(size_t)15) : 64) + (v.threads / 64) * pt::kPoolWaveBytes;
+  if (v.split()) return (PT_BLOCK_THREADS / 64) * 64 * pt::kRecWords * sizeof(float);
   return (PT_BLOCK_THREADS / 64) * 64 * 14 * sizeof(float);
 }
-static inline size_t scene_lds_bytes(int n, int variant) { return scene_lds_f4(n, variant) * sizeof(float4) + tail_lds_bytes(n, variant); }
-
-typedef void (*pixel_kernel_fn)(PixelKernelArgs);
+static inline size_t scene_lds_bytes(int n, const VariantInfo& v) { return scene_lds_f4(n, v) * sizeof(float4) + tail_lds_bytes(n, v); }
+size_t pt_kernel_lds_bytes(int n_spheres, int variant) { return scene_lds_bytes(n_spheres, pt_kernel_variant(variant)); }
 
 // the bounce cap of the reference-configuration build these launch parameters run (5 or 8), 0 = a generic build
-static inline int ref_config(int n, int max_bounces, int variant, bool planar) {
-  return (n == 9 && (max_bounces == 5 || max_bounces == 8) && !planar && (variant == 6 || variant == 8 || variant == 9)) ? max_bounces : 0;
+static inline int ref_config(int n, int max_bounces, const VariantInfo& v, bool planar) {
+  return (n == 9 && (max_bounces == 5 || max_bounces == 8) && !planar && v.ref_builds) ? max_bounces : 0;
 }
-int pt_kernel_ref_bounces(int n_spheres, int max_bounces, int variant, bool planar) { return ref_config(n_spheres, max_bounces, variant, planar); }
+int pt_kernel_ref_bounces(int n_spheres, int max_bounces, int variant, bool planar) { return ref_config(n_spheres, max_bounces, pt_kernel_variant(variant), planar); }
 
-static pixel_kernel_fn select_kernel(int rng_mode, int variant, bool lean, int ref) {
-  const bool philox = rng_mode == PT_RNG_PHILOX;
-  if (ref == 5 && !lean) {
-    if (variant == 6) return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5>;
-    if (variant == 8)
-      return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 4, false, 5> : pt::pixel_kernel_split<PT_RNG_XORWOW, 4, false, 5>;
-    if (variant == 9)
-      return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 2, false, 5> : pt::pixel_kernel_split<PT_RNG_XORWOW, 2, false, 5>;
-  }
-  if (ref == 8 && !lean) {
-    if (variant == 6) return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8>;
-    if (variant == 8)
-      return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 4, false, 8> : pt::pixel_kernel_split<PT_RNG_XORWOW, 4, false, 8>;
-    if (variant == 9)
-      return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 2, false, 8> : pt::pixel_kernel_split<PT_RNG_XORWOW, 2, false, 8>;
-  }
-  if (lean) {
-    switch (variant) {
-      case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, true>;
-      case 8: return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 4, true> : pt::pixel_kernel_split<PT_RNG_XORWOW, 4, true>;
-      case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, true>;
-      case 13: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true>;
-      case 14: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, true>;
-#if PT_BUILD_EXPERIMENTS  // variant 11 (the grid walk with every lane testing its own spheres): superseded by 13, kept for A/B
-      case 11: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 11, true> : pt::pixel_kernel<PT_RNG_XORWOW, 11, true>;
-      case 12: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 12, true> : pt::pixel_kernel<PT_RNG_XORWOW, 12, true>;
-#endif
-      default: return nullptr;
+// ---- the selector: which build of pixel_kernel / pixel_kernel_split a launch runs ------------------------------------------------
+// A flavour is the plain kernel, FRAMES (a batch), RESUME (a progressive pass) or RESUME + ADAPTIVE (... over a list of pixels).
+template <bool FRAMES, bool RESUME, bool ADAPTIVE>
+using kernel_fn = void (*)(typename pt::KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type);
+
+template <bool FRAMES, bool RESUME, bool ADAPTIVE, int RNG, int VAR, bool LEAN, int REFB>
+static kernel_fn<FRAMES, RESUME, ADAPTIVE> kernel_build() {
+  constexpr VariantInfo v = kVariants[VAR];
+  if constexpr (v.split()) return pt::pixel_kernel_split<RNG, v.lanes, LEAN, REFB>;
+  else return pt::pixel_kernel<RNG, (VAR == 14 ? 13 : VAR), LEAN, REFB, FRAMES, v.wide, RESUME, ADAPTIVE>;  // variant 14 is variant 13's kernel with WIDE: there is no VAR = 14 build
+}
+
+// Variant VAR's build of one flavour for a launch's LDS layout and reference configuration, or null.  Only the builds the row
+// announces are instantiated, so a library holds exactly them (libptcore.so: the product variants only).
+template <bool FRAMES, bool RESUME, bool ADAPTIVE, int RNG, int VAR>
+static kernel_fn<FRAMES, RESUME, ADAPTIVE> variant_kernel(bool lean, int ref) {
+  constexpr VariantInfo v = kVariants[VAR];
+  if constexpr ((v.product || PT_BUILD_EXPERIMENTS) && (!RESUME || v.resume) && (!FRAMES || v.frames)) {
+    if constexpr (v.ref_builds) {
+      if (ref == 5 && !lean) return kernel_build<FRAMES, RESUME, ADAPTIVE, RNG, VAR, false, 5>();
+      if (ref == 8 && !lean) return kernel_build<FRAMES, RESUME, ADAPTIVE, RNG, VAR, false, 8>();
+    }
+    if constexpr (!FRAMES) {  // (a batch has builds for the reference configurations only)
+      if constexpr (v.lean != PT_LEAN_NEVER) {
+        if (lean) return kernel_build<FRAMES, RESUME, ADAPTIVE, RNG, VAR, true, 0>();
+      }
+      if constexpr (v.lean != PT_LEAN_ALWAYS) {
+        if (!lean) return kernel_build<FRAMES, RESUME, ADAPTIVE, RNG, VAR, false, 0>();
+      }
     }
   }
-  switch (variant) {
-    case 0: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 0> : pt::pixel_kernel<PT_RNG_XORWOW, 0>;
-    case 9: return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 2> : pt::pixel_kernel_split<PT_RNG_XORWOW, 2>;
-#if PT_BUILD_EXPERIMENTS  // measured negative results and stepping stones: libptcore_lab.so only
-    case 1: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 1> : pt::pixel_kernel<PT_RNG_XORWOW, 1>;
-    case 2: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 2> : pt::pixel_kernel<PT_RNG_XORWOW, 2>;
-    case 3: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 3> : pt::pixel_kernel<PT_RNG_XORWOW, 3>;
-    case 4: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 4> : pt::pixel_kernel<PT_RNG_XORWOW, 4>;
-    case 5: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 5> : pt::pixel_kernel<PT_RNG_XORWOW, 5>;
-    case 7: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 7> : pt::pixel_kernel<PT_RNG_XORWOW, 7>;
-#endif
-    case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6> : pt::pixel_kernel<PT_RNG_XORWOW, 6>;
-    case 8: return philox ? pt::pixel_kernel_split<PT_RNG_PHILOX, 4> : pt::pixel_kernel_split<PT_RNG_XORWOW, 4>;
-    case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10> : pt::pixel_kernel<PT_RNG_XORWOW, 10>;
-    default: return nullptr;
-  }
+  return nullptr;
+}
+
+template <bool FRAMES, bool RESUME, bool ADAPTIVE, int RNG, int... VAR>
+static kernel_fn<FRAMES, RESUME, ADAPTIVE> select_kernel_of(int variant, bool lean, int ref, std::integer_sequence<int, VAR...>) {
+  static constexpr kernel_fn<FRAMES, RESUME, ADAPTIVE> (*of[])(bool, int) = {variant_kernel<FRAMES, RESUME, ADAPTIVE, RNG, VAR>...};
+  return (variant >= 0 && variant < kNumVariants) ? of[variant](lean, ref) : nullptr;
+}
+
+// variant 12's loop assumes every ray is searched for: without bounces it runs variant 11's kernel
+static inline int run_variant(int variant, int max_bounces) { return (variant == 12 && max_bounces < 1) ? 11 : variant; }
+
+template <bool FRAMES = false, bool RESUME = false, bool ADAPTIVE = false>
+static kernel_fn<FRAMES, RESUME, ADAPTIVE> select_kernel(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  const VariantInfo& v = pt_kernel_variant(variant);
+  const bool lean = lds_lean(n_spheres, v);
+  const int ref = ref_config(n_spheres, max_bounces, v, planar);
+  const std::make_integer_sequence<int, kNumVariants> all;
+  return rng_mode == PT_RNG_PHILOX ? select_kernel_of<FRAMES, RESUME, ADAPTIVE, PT_RNG_PHILOX>(variant, lean, ref, all)
+                                   : select_kernel_of<FRAMES, RESUME, ADAPTIVE, PT_RNG_XORWOW>(variant, lean, ref, all);
+}
+
+// the function a launch with these parameters runs (pt_renderer_kernel_info and the tools), null = there is no such build
+const void* pt_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  return (const void*)select_kernel<>(rng_mode, run_variant(variant, max_bounces), n_spheres, max_bounces, planar);
+}
+const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  return (const void*)select_kernel<false, true>(rng_mode, variant, n_spheres, max_bounces, planar);
+}
+const void* pt_adaptive_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
+  return (const void*)select_kernel<false, true, true>(rng_mode, variant, n_spheres, max_bounces, planar);
 }
 
 #ifdef PT_SCREEN_STATS
@@ -1118,37 +1164,14 @@ extern "C" int pt_debug_grid_stats(unsigned long long out[8], int reset) {
 }
 #endif
 
-int pt_kernel_num_variants(void) { return 15; }
-
-int pt_kernel_block_threads(int variant) {
-  return variant == 14 ? PT_GRID_WIDE_THREADS : (variant == 11 || variant == 12 || variant == 13) ? PT_GRID_BLOCK_THREADS : PT_BLOCK_THREADS;
-}
-
-bool pt_kernel_has_variant(int variant) {
-  if (variant < 0 || variant >= 15) return false;
-#if PT_BUILD_EXPERIMENTS
-  return true;
-#else
-  return variant == 0 || variant == 6 || variant == 8 || variant == 9 || variant == 10 || variant == 13 || variant == 14;
-#endif
-}
-
 size_t pt_kernel_accel_bytes(void) { return pt::kGridAccelBytes; }
-
-
-const void* pt_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
-  if (variant == 12 && max_bounces < 1) variant = 11;
-  return (const void*)select_kernel(rng_mode, variant, lds_lean(n_spheres, variant), ref_config(n_spheres, max_bounces, variant, planar));
-}
-
-size_t pt_kernel_lds_bytes(int n_spheres, int variant) { return scene_lds_bytes(n_spheres, variant); }
 
 int pt_kernel_max_spheres(int variant) {
   // variants with a lean build stage nothing for big scenes; the others are bounded by their LDS image
-  const size_t tail = tail_lds_bytes(0, variant);
-  if (variant == 6 || variant == 8 || variant == 10 || variant == 11 || variant == 12 || variant == 13 || variant == 14) return 1 << 26;  // byte offsets of the 40-byte records stay inside 32 bits
-  const size_t fixed = tail + pt::kTablesF4 * sizeof(float4);
-  if (variant == 3) return (int)((PT_LDS_BUDGET_BYTES - fixed - 2 * sizeof(float4)) / (5 * sizeof(float4)));
+  const VariantInfo& v = pt_kernel_variant(variant);
+  if (v.lean != PT_LEAN_NEVER) return 1 << 26;  // byte offsets of the 40-byte records stay inside 32 bits
+  const size_t fixed = tail_lds_bytes(0, v) + pt::kTablesF4 * sizeof(float4);
+  if (v.lds_extra == PT_LDS_PACKED) return (int)((PT_LDS_BUDGET_BYTES - fixed - 2 * sizeof(float4)) / (5 * sizeof(float4)));
   return (int)((PT_LDS_BUDGET_BYTES - fixed) / (4 * sizeof(float4)));
 }
 
@@ -1173,69 +1196,79 @@ void pt_kernel_grid_layout(int n_spheres, int threads, uint64_t out[8]) {
 
 // does a launch with these arguments chain a pixel's samples through several workgroups (sample chunking)?
 bool pt_kernel_chunked(int variant, int n_spheres, int max_bounces, bool planar, int spp, uint32_t chunks) {
-  return (((variant == 6 || variant == 8 || variant == 9) && !lds_lean(n_spheres, variant) && ref_config(n_spheres, max_bounces, variant, planar)) || variant == 13) && chunks > 1u &&
-         chunks <= (uint32_t)PT_CHUNKS_MAX && spp >= 2 * (int)chunks &&
-         (spp + (int)chunks - 1) / (int)chunks <= ((variant == 13 || variant == 14) ? PT_CHUNK_MAX_SAMPLES_GRID : PT_CHUNK_MAX_SAMPLES);
+  const VariantInfo& v = pt_kernel_variant(variant);
+  // of a variant with reference-configuration builds only those hand a pixel's state from workgroup to workgroup (kChunkable)
+  const bool build_chunks = v.can_chunk && (!v.ref_builds || (!lds_lean(n_spheres, v) && ref_config(n_spheres, max_bounces, v, planar)));
+  return build_chunks && chunks > 1u && chunks <= (uint32_t)PT_CHUNKS_MAX && spp >= 2 * (int)chunks &&
+         (spp + (int)chunks - 1) / (int)chunks <= (v.chunk_family == PT_CHUNK_GRID ? PT_CHUNK_MAX_SAMPLES_GRID : PT_CHUNK_MAX_SAMPLES);
+}
+
+// What every launch of a pixel kernel does first: fill scene_lds_f4 and the issue priority (`samples` = the samples per pixel this
+// launch renders), check the LDS budget, opt in to large dynamic LDS, enqueue the grid build of a grid variant.  Leaves the
+// launch's geometry in *s.
+struct LaunchShape {
+  unsigned block, blocks;  // workgroup size, workgroups of one pass over the tile
+  size_t lds;
+};
+static hipError_t prepare_launch(const void* fn, const VariantInfo& v, PixelKernelArgs& b, int samples, hipStream_t stream, LaunchShape* s) {
+  if (!fn) return hipErrorInvalidValue;
+  b.scene_lds_f4 = (uint32_t)scene_lds_f4(b.n_spheres, v);
+  b.prio = (samples >= PT_PRIO_MIN_SPP || b.prio != 0u) ? 1u : 0u;  // long waves always; short ones when the caller says the frame is one round
+  s->lds = scene_lds_bytes(b.n_spheres, v);
+  const size_t lds_budget = v.wide ? (size_t)PT_LDS_WIDE_BUDGET_BYTES : (size_t)PT_LDS_BUDGET_BYTES;
+  if (s->lds > lds_budget) return hipErrorInvalidValue;
+  if (s->lds > 64 * 1024) {  // beyond the default dynamic-LDS limit: opt in (gfx950 has 160 KiB per CU)
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget);
+    if (e != hipSuccess) return e;
+  }
+  if (v.grid != PT_GRID_NONE) {  // this launch's grid (the scene may have changed since the last one), in the renderer's scratch
+    if (!b.accel) return hipErrorInvalidValue;
+    hipError_t e = pt_launch_build_grid(b.spheres, b.n_spheres, const_cast<uint32_t*>(b.accel), b.eye, v.grid == PT_GRID_POOLED, stream, v.threads);
+    if (e != hipSuccess) return e;
+  }
+  s->block = (unsigned)v.threads;
+  s->blocks = (unsigned)(((uint64_t)b.tile_pixels * (uint64_t)v.lanes + s->block - 1) / s->block);
+  return hipSuccess;
 }
 
 hipError_t pt_launch_pixel_kernel(const PixelKernelArgs& a, int rng_mode, int variant, hipStream_t stream) {
-  if (variant == 12 && a.max_bounces < 1) variant = 11;  // variant 12's loop assumes every ray is searched for
-  pixel_kernel_fn fn = select_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u));
-  if (!fn) return hipErrorInvalidValue;
+  variant = run_variant(variant, a.max_bounces);
+  const auto fn = select_kernel<>(rng_mode, variant, a.n_spheres, a.max_bounces, a.planar != 0u);
   PixelKernelArgs b = a;
-  b.scene_lds_f4 = (uint32_t)scene_lds_f4(a.n_spheres, variant);
-  b.prio = (a.spp >= PT_PRIO_MIN_SPP || a.prio != 0u) ? 1u : 0u;  // long waves always; short ones when the caller says the frame is one round
-  const size_t lds = scene_lds_bytes(a.n_spheres, variant);
-  const size_t lds_budget = variant == 14 ? (size_t)PT_LDS_WIDE_BUDGET_BYTES : (size_t)PT_LDS_BUDGET_BYTES;
-  if (lds > lds_budget) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit: opt in (gfx950 has 160 KiB per CU)
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget);
-    if (e != hipSuccess) return e;
-  }
-  if (variant == 11 || variant == 12 || variant == 13 || variant == 14) {  // this frame's grid (the scene may have changed since the last one)
-    if (!a.accel) return hipErrorInvalidValue;
-    hipError_t e = pt_launch_build_grid(a.spheres, a.n_spheres, const_cast<uint32_t*>(a.accel), a.eye, variant == 13 || variant == 14, stream,
-                                        pt_kernel_block_threads(variant));
-    if (e != hipSuccess) return e;
-  }
-  const uint64_t lanes = (uint64_t)a.tile_pixels * (uint64_t)(variant == 8 ? 4 : variant == 9 ? 2 : 1);
-  const unsigned block = (unsigned)pt_kernel_block_threads(variant);
-  unsigned grid = (unsigned)((lanes + block - 1) / block);
+  LaunchShape s;
+  hipError_t e = prepare_launch((const void*)fn, pt_kernel_variant(variant), b, a.spp, stream, &s);
+  if (e != hipSuccess) return e;
   // sample chunking: only the reference-configuration builds of variant 6 and variant 13 hand a pixel's state from workgroup to workgroup
   const bool chunked = a.repair == 0u && pt_kernel_chunked(variant, a.n_spheres, a.max_bounces, a.planar != 0u, a.spp, a.chunks) && a.chunk_state && a.chunk_flag;
   if (a.repair != 0u && !a.chunk_flag) return hipErrorInvalidValue;  // a repair launch reads the flags its chunked predecessor left
   b.chunks = chunked ? a.chunks : 0u;
+  unsigned grid = s.blocks;
   if (chunked) {
-    hipError_t e = hipMemsetAsync(a.chunk_flag, 0, (size_t)grid * sizeof(uint32_t), stream);
+    e = hipMemsetAsync(a.chunk_flag, 0, (size_t)grid * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     grid *= a.chunks;
   }
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds, stream, b);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(s.block), s.lds, stream, b);
   return hipGetLastError();
 }
 
 bool pt_kernel_has_frames(int variant, int n_spheres, int max_bounces, bool planar) {
-  return variant == 6 && ref_config(n_spheres, max_bounces, variant, planar) != 0;
+  const VariantInfo& v = pt_kernel_variant(variant);
+  return v.frames && ref_config(n_spheres, max_bounces, v, planar) != 0;
 }
 
 // XORWOW: one workgroup per pixel block, looping over the batch's frames; philox: one per (frame, pixel block) (pixel_kernel, FRAMES)
-hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, hipStream_t stream) {
+hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, int variant, hipStream_t stream) {
   const PixelKernelArgs& a = fa.base;
-  const int ref = ref_config(a.n_spheres, a.max_bounces, 6, a.planar != 0u);
-  if (ref == 0 || fa.frames < 2u || fa.frames > (uint32_t)PT_FRAMES_MAX) return hipErrorInvalidValue;
-  const bool philox = rng_mode == PT_RNG_PHILOX;
-  typedef void (*frames_fn)(FramesKernelArgs);
-  frames_fn fn = ref == 5 ? (philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5, true>)
-                          : (philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8, true>);
+  if (!pt_kernel_has_frames(variant, a.n_spheres, a.max_bounces, a.planar != 0u) || fa.frames < 2u || fa.frames > (uint32_t)PT_FRAMES_MAX) return hipErrorInvalidValue;
+  const auto fn = select_kernel<true>(rng_mode, variant, a.n_spheres, a.max_bounces, a.planar != 0u);
   FramesKernelArgs b = fa;
-  b.base.scene_lds_f4 = (uint32_t)scene_lds_f4(a.n_spheres, 6);
-  b.base.prio = (a.spp >= PT_PRIO_MIN_SPP || a.prio != 0u) ? 1u : 0u;
   b.base.chunks = 0u;
   b.base.repair = 0u;
-  const size_t lds = scene_lds_bytes(a.n_spheres, 6);
-  const unsigned block = (unsigned)PT_BLOCK_THREADS;
-  const unsigned blocks = (unsigned)(((uint64_t)a.tile_pixels + block - 1) / block);
-  hipLaunchKernelGGL(fn, dim3(philox ? blocks * fa.frames : blocks), dim3(block), lds, stream, b);
+  LaunchShape s;
+  const hipError_t e = prepare_launch((const void*)fn, pt_kernel_variant(variant), b.base, a.spp, stream, &s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fn, dim3(rng_mode == PT_RNG_PHILOX ? s.blocks * fa.frames : s.blocks), dim3(s.block), s.lds, stream, b);
   return hipGetLastError();
 }
 
@@ -1248,110 +1281,31 @@ hipError_t pt_launch_setup_random(uint32_t* state, int width, int row_begin, uin
 }
 
 // ---- progressive passes (pixel_kernel, RESUME) ------------------------------------------------
-// The resume builds: variant 6 (the two reference configurations, the generic and the lean layout), 10 (both layouts), 13 and
-// its 1024-thread form 14.  Nothing else has one (pt_progressive_create refuses the rest).
-typedef void (*resume_kernel_fn)(ResumeKernelArgs);
-
-static resume_kernel_fn select_resume_kernel(int rng_mode, int variant, bool lean, int ref) {
-  const bool philox = rng_mode == PT_RNG_PHILOX;
-  if (variant == 6 && ref == 5 && !lean)
-    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5, false, false, true>;
-  if (variant == 6 && ref == 8 && !lean)
-    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8, false, false, true>;
-  if (lean) {
-    switch (variant) {
-      case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, true, 0, false, false, true>;
-      case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, true, 0, false, false, true>;
-      case 13: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, false, true>;
-      case 14: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, true, true>;
-      default: return nullptr;
-    }
-  }
-  switch (variant) {
-    case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 0, false, false, true>;
-    case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, false, 0, false, false, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, false, 0, false, false, true>;
-    default: return nullptr;
-  }
-}
-
-typedef void (*adaptive_kernel_fn)(AdaptiveKernelArgs);
-
-static adaptive_kernel_fn select_adaptive_kernel(int rng_mode, int variant, bool lean, int ref) {
-  const bool philox = rng_mode == PT_RNG_PHILOX;
-  if (variant == 6 && ref == 5 && !lean)
-    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 5, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 5, false, false, true, true>;
-  if (variant == 6 && ref == 8 && !lean)
-    return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 8, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 8, false, false, true, true>;
-  if (lean) {
-    switch (variant) {
-      case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, true, 0, false, false, true, true>;
-      case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, true, 0, false, false, true, true>;
-      case 13: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, false, true, true>;
-      case 14: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 13, true, 0, false, true, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 13, true, 0, false, true, true, true>;
-      default: return nullptr;
-    }
-  }
-  switch (variant) {
-    case 6: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 6, false, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 6, false, 0, false, false, true, true>;
-    case 10: return philox ? pt::pixel_kernel<PT_RNG_PHILOX, 10, false, 0, false, false, true, true> : pt::pixel_kernel<PT_RNG_XORWOW, 10, false, 0, false, false, true, true>;
-    default: return nullptr;
-  }
-}
-
-bool pt_kernel_has_resume(int variant) { return variant == 6 || variant == 10 || variant == 13 || variant == 14; }
-
-const void* pt_resume_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
-  return (const void*)select_resume_kernel(rng_mode, variant, lds_lean(n_spheres, variant), ref_config(n_spheres, max_bounces, variant, planar));
-}
-
 // One pass: pt_launch_pixel_kernel without sample chunking (ra.base.chunks and repair are ignored) and with the issue priority
 // decided by the pass's own sample count.  An adaptive pass launches the tile's full block count: the workgroups past the
 // device-side list length leave at once (pixel_kernel, ADAPTIVE), so nothing is read back.
-template <class Args>
-static hipError_t launch_pass(void (*fn)(Args), const Args& ra, int variant, hipStream_t stream) {
+template <bool ADAPTIVE, class Args>
+static hipError_t launch_pass(const Args& ra, int rng_mode, int variant, hipStream_t stream) {
   const PixelKernelArgs& a = ra.base;
-  if (!fn) return hipErrorInvalidValue;
+  if (!pt_kernel_has_resume(variant) || !ra.session || ra.sample_begin < 0 || ra.sample_begin >= a.spp || a.rng_state) return hipErrorInvalidValue;
+  const auto fn = select_kernel<false, true, ADAPTIVE>(rng_mode, variant, a.n_spheres, a.max_bounces, a.planar != 0u);
   Args b = ra;
-  b.base.scene_lds_f4 = (uint32_t)scene_lds_f4(a.n_spheres, variant);
-  b.base.prio = (a.spp - ra.sample_begin >= PT_PRIO_MIN_SPP || a.prio != 0u) ? 1u : 0u;
   b.base.chunks = 0u;
   b.base.chunk_state = nullptr;
   b.base.chunk_flag = nullptr;
   b.base.repair = 0u;
-  const size_t lds = scene_lds_bytes(a.n_spheres, variant);
-  const size_t lds_budget = variant == 14 ? (size_t)PT_LDS_WIDE_BUDGET_BYTES : (size_t)PT_LDS_BUDGET_BYTES;
-  if (lds > lds_budget) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget);
-    if (e != hipSuccess) return e;
-  }
-  if (variant == 13 || variant == 14) {  // the grid of this pass's scene and eye (the renderer's scratch)
-    if (!a.accel) return hipErrorInvalidValue;
-    hipError_t e = pt_launch_build_grid(a.spheres, a.n_spheres, const_cast<uint32_t*>(a.accel), a.eye, true, stream, pt_kernel_block_threads(variant));
-    if (e != hipSuccess) return e;
-  }
-  const unsigned block = (unsigned)pt_kernel_block_threads(variant);
-  const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + block - 1) / block);
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds, stream, b);
+  LaunchShape s;
+  const hipError_t e = prepare_launch((const void*)fn, pt_kernel_variant(variant), b.base, a.spp - ra.sample_begin, stream, &s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fn, dim3(s.blocks), dim3(s.block), s.lds, stream, b);
   return hipGetLastError();
 }
 
 hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream) {
-  const PixelKernelArgs& a = ra.base;
-  if (!pt_kernel_has_resume(variant) || !ra.session || ra.sample_begin < 0 || ra.sample_begin >= a.spp || a.rng_state) return hipErrorInvalidValue;
-  return launch_pass(select_resume_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u)),
-                     ra, variant, stream);
-}
-
-const void* pt_adaptive_kernel_symbol(int rng_mode, int variant, int n_spheres, int max_bounces, bool planar) {
-  return (const void*)select_adaptive_kernel(rng_mode, variant, lds_lean(n_spheres, variant), ref_config(n_spheres, max_bounces, variant, planar));
+  return launch_pass<false>(ra, rng_mode, variant, stream);
 }
 
 hipError_t pt_launch_adaptive_kernel(const AdaptiveKernelArgs& aa, int rng_mode, int variant, hipStream_t stream) {
-  const PixelKernelArgs& a = aa.base;
-  if (!pt_kernel_has_resume(variant) || !aa.session || !aa.list || !aa.list_len || aa.sample_begin < 0 || aa.sample_begin >= a.spp ||
-      a.rng_state)
-    return hipErrorInvalidValue;
-  return launch_pass(select_adaptive_kernel(rng_mode, variant, lds_lean(a.n_spheres, variant), ref_config(a.n_spheres, a.max_bounces, variant, a.planar != 0u)),
-                     aa, variant, stream);
+  if (!aa.list || !aa.list_len) return hipErrorInvalidValue;
+  return launch_pass<true>(aa, rng_mode, variant, stream);
 }
