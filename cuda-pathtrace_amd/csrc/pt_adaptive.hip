@@ -21,8 +21,9 @@ namespace pt {
 __device__ __forceinline__ void record_frame(const uint32_t* __restrict__ rec, uint32_t tile_pixels, uint32_t p, int n, float px[14]) {
   auto ld = [&](int w) { return rec[(size_t)w * tile_pixels + p]; };
   auto ldf = [&](int w) { return __uint_as_float(ld(w)); };
-  TraceOutput L{mk3(ldf(0), ldf(1), ldf(2)), mk3(ldf(3), ldf(4), ldf(5)), mk3(ldf(6), ldf(7), ldf(8)), ldf(9)};
-  const int n0 = (int)ld(10), n1 = (int)ld(11);
+  TraceOutput L{mk3(ldf(PT_REC_COLOR), ldf(PT_REC_COLOR + 1), ldf(PT_REC_COLOR + 2)), mk3(ldf(PT_REC_NORMAL), ldf(PT_REC_NORMAL + 1), ldf(PT_REC_NORMAL + 2)),
+                mk3(ldf(PT_REC_ALBEDO), ldf(PT_REC_ALBEDO + 1), ldf(PT_REC_ALBEDO + 2)), ldf(PT_REC_DEPTH)};
+  const int n0 = (int)ld(PT_REC_N_COLOR), n1 = (int)ld(PT_REC_N_HIT);
   Welford var[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -30,7 +31,7 @@ __device__ __forceinline__ void record_frame(const uint32_t* __restrict__ rec, u
     // (an opaque copy per accumulator: told that the three first-hit counts are equal, the compiler merges their variances into
     // one if/else whose else arm sits in front of the exec restore -- the shape tools/isa_exec_lint.py refuses, EXACTNESS.md A.12)
     if (k > 1) asm volatile("" : "+v"(nk));
-    var[k] = Welford{nk, ldf(12 + 2 * k), ldf(13 + 2 * k)};
+    var[k] = Welford{nk, ldf(PT_REC_MEAN + 2 * k), ldf(PT_REC_M2 + 2 * k)};
   }
   frame_values(L, var, (float)n, px);
 }
@@ -43,7 +44,7 @@ __global__ void __launch_bounds__(PT_ADAPTIVE_BLOCK) adaptive_classify_kernel(co
   const bool act = mode == 2 ? true : (mask[p] & 1u) != 0u;
   bool unconv = act;
   if (mode == 0 && act && n >= rule.min_samples) {
-    const uint32_t n0 = rec[(size_t)10 * tile_pixels + p], n1 = rec[(size_t)11 * tile_pixels + p];
+    const uint32_t n0 = rec[(size_t)PT_REC_N_COLOR * tile_pixels + p], n1 = rec[(size_t)PT_REC_N_HIT * tile_pixels + p];
     bool conv = n1 == 0u;  // (a) no sample hit anything
     if (!conv && n0 == (uint32_t)n) {  // (b) every sample scored (the colour variance skips escaped paths: :157-161)
       float px[14];

@@ -7,8 +7,8 @@
 
 namespace pt {
 
-// intersectScene: src/pathtrace.cu:93-107 -- literal loop (variants 0 and 1)
-template <int VAR>
+// intersectScene: src/pathtrace.cu:93-107 -- literal loop (tracer levels 0 and 1; LEVEL: the variant table's `tracer` column, pt_trace.h)
+template <int LEVEL>
 __device__ __forceinline__ bool intersect_scene_loop(const SceneLds& sc, int n, F3 o, F3 d, const RayConst& rc,
                                                      float& t_hit, int& idx) {
   float tNearest = 1000000.0f;
@@ -20,7 +20,7 @@ __device__ __forceinline__ bool intersect_scene_loop(const SceneLds& sc, int n, 
   for (int i = 0; i < n; i++) {
     const float4 g = sc.geom_uniform(i);
     bool h;
-    if constexpr (VAR == 0)
+    if constexpr (LEVEL == 0)
       h = intersect_sphere(o, d, rc.a, g, t);
     else
       h = intersect_sphere_v1(o, d, rc, g, t);
@@ -599,26 +599,26 @@ __device__ __forceinline__ bool intersect_scene_screened_large(const SceneLds& s
   return hit;
 }
 
-template <int VAR, bool PRIMARY = false, bool LAST = false>
+template <int LEVEL, bool PRIMARY = false, bool LAST = false>
 __device__ __forceinline__ bool intersect_scene(const SceneLds& sc, int n, F3 o, F3 d, float& t_hit, int& idx) {
   // every ray but the primary one has a unit direction: its constants come from the workgroup's table (any other a: general
   // routine).  Not in the lean layouts: their kernels mix depths in a wave (path regeneration), so both routines would run.
-  const RayConst rc = (VAR >= 6 && !PRIMARY && !sc.lean) ? make_ray_const_unit(d, sc.rden1) : make_ray_const(d);
-  if constexpr (VAR >= 5) {
+  const RayConst rc = (LEVEL >= 6 && !PRIMARY && !sc.lean) ? make_ray_const_unit(d, sc.rden1) : make_ray_const(d);
+  if constexpr (LEVEL >= 5) {
     // Screening pays when most spheres are hit by most rays (the Cornell box: a ray inside six
     // wall spheres hits all six).  In a many-sphere scene almost every test fails `det >= 0` for
     // the whole wave and the literal loop skips its FP64 part with one wave-uniform branch.
     if (!sc.lean && (sc.small_only || n <= PT_SCREEN_MAX_SPHERES))
-      return intersect_scene_screened_keys<(VAR >= 6), (PRIMARY && VAR >= 6), (LAST && VAR >= 6)>(sc, n, o, d, rc, t_hit, idx);
-    if constexpr (VAR >= 6) return intersect_scene_screened_large(sc, n, o, d, rc, t_hit, idx);
+      return intersect_scene_screened_keys<(LEVEL >= 6), (PRIMARY && LEVEL >= 6), (LAST && LEVEL >= 6)>(sc, n, o, d, rc, t_hit, idx);
+    if constexpr (LEVEL >= 6) return intersect_scene_screened_large(sc, n, o, d, rc, t_hit, idx);
     return intersect_scene_loop<1>(sc, n, o, d, rc, t_hit, idx);
   }
-  if constexpr (VAR == 3)
+  if constexpr (LEVEL == 3)
     return intersect_scene_screened_pk(sc, n, o, d, rc, t_hit, idx);
-  else if constexpr (VAR == 2 || VAR == 4)
+  else if constexpr (LEVEL == 2 || LEVEL == 4)
     return intersect_scene_screened(sc, n, o, d, rc, t_hit, idx);
   else
-    return intersect_scene_loop<VAR>(sc, n, o, d, rc, t_hit, idx);
+    return intersect_scene_loop<LEVEL>(sc, n, o, d, rc, t_hit, idx);
 }
 
 // nearest hit for P rays at once; same decisions as intersect_scene_screened_keys<true>

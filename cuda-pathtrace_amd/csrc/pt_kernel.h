@@ -177,6 +177,15 @@ struct AdaptiveKernelArgs : ResumeKernelArgs {
 // words handed from one chunk of a pixel block to the next: 10 sums, 2 counts (colour; the three first-hit accumulators share
 // one), 4 x {mean, M2}, and the 6 generator words (xorwow only; philox needs none)
 #define PT_CHUNK_WORDS 26
+// ... and where they lie, [word][pixel] (the same record is a progressive session's: include/ptcore_lab.h, pt_debug_progressive_record)
+enum {
+  PT_REC_COLOR = 0, PT_REC_NORMAL = 3, PT_REC_ALBEDO = 6,  // sums, x y z each (feature f = 0, 1, 2: PT_REC_COLOR + 3 f)
+  PT_REC_DEPTH = 9,                                        // sum (feature 3)
+  PT_REC_N_COLOR = 10, PT_REC_N_HIT = 11,                  // Welford counts: the colour's, the three first-hit accumulators' shared one
+  PT_REC_MEAN = 12, PT_REC_M2 = 13,                        // of feature f (colour, normal, albedo, depth): + 2 f
+  PT_REC_RNG = 20,                                         // xorwow d, v0 .. v4
+};
+static_assert(PT_REC_RNG + 6 == PT_CHUNK_WORDS && PT_REC_MEAN + 2 * 4 == PT_REC_RNG, "the record's layout");
 #ifndef PT_CHUNKS
 // chunks per pixel block of the automatic policy.  Measured at the headline frame (tools/chunk_sweep.py, profiles/r03):
 // 1 (off) 50.88 ms, 2: 50.14, 4: 50.22, 8: 50.07, 16: 50.23 -- two chunks take nearly all of the gain for one hand-over per
@@ -208,12 +217,15 @@ struct AdaptiveKernelArgs : ResumeKernelArgs {
 #endif
 #define PT_VARIANT_FAST 100     // reported by pt_renderer_kernel_info for a fast_math renderer (pt_fast.hip)
 #define PT_FAST_LDS_SPHERES 64  // the fast kernel stages scenes up to this size into LDS, larger ones are read in place
-// What the host knows about a kernel variant.  The table of these rows (kVariants, pt_kernel.hip) is the ONE place where a
-// variant number means something: the selector, the launchers and pt_capi.hip read the row, none compares numbers.
+// What a kernel variant is.  The table of these rows (kVariants, pt_kernel.hip) is the ONE place where a variant number means
+// something: the kernels and their traits, the selector, the launchers and pt_capi.hip read the row, none compares numbers.
 enum { PT_LEAN_NEVER, PT_LEAN_BIG, PT_LEAN_ALWAYS };  // LDS layout (pt_scene_lds.h): lean above PT_SCREEN_MAX_SPHERES / always
 enum { PT_LDS_PLAIN, PT_LDS_PACKED, PT_LDS_WALLS };   // beside the scene image: a packed FP32 copy (variant 3), the wall block (6)
 enum { PT_GRID_NONE, PT_GRID_LANE, PT_GRID_POOLED };  // walks the uniform grid, every lane for itself / tests pooled per wave
 enum { PT_CHUNK_NONE = -1, PT_CHUNK_ONE_LANE, PT_CHUNK_SPLIT, PT_CHUNK_GRID, PT_CHUNK_FAMILIES };  // whose chunk-count policy (pt_capi.hip)
+// pixel_kernel's sample loop: sample after sample / two samples per lane in lockstep, then the odd one / per-lane path
+// regeneration / regeneration with walk and shading decoupled (pixel_kernel_split has its own loop of rounds)
+enum { PT_LOOP_SAMPLES, PT_LOOP_PAIRS, PT_LOOP_REGEN, PT_LOOP_DECOUPLED };
 struct VariantInfo {
   bool product;       // in libptcore.so (every variant is in libptcore_lab.so)
   int lanes;          // lanes per pixel: 1, or 2 / 4 in the split kernels (pixel_kernel_split)
@@ -227,7 +239,14 @@ struct VariantInfo {
   bool frames;        // has frames builds (of its reference configurations)
   int chunk_family;   // PT_CHUNK_*
   bool can_chunk;     // launches may chain a pixel's samples through several workgroups (pt_kernel_chunked)
+  int min_waves;      // __launch_bounds__ waves per SIMD of the generic builds (0: no bound, pixel_kernel_split)
+  int loop;           // PT_LOOP_*
+  int tracer;         // level of the tracer it runs (pt_trace.h, pt_intersect.h): 0-6, 11 or 13
+  int kernel;         // the pixel_kernel<VAR> build that executes it: itself, or the kernel a wide row runs with WIDE
   constexpr bool split() const { return lanes > 1; }
+  // builds that can chain a pixel's samples through several workgroups of one launch (sample chunking): of a variant with
+  // reference-configuration builds only those (variants 6, 8, 9; the pooled grid kernel has none: every build)
+  constexpr bool chunk_build(bool ref) const { return can_chunk && (!ref_builds || ref); }
 };
 const VariantInfo& pt_kernel_variant(int variant);  // (a number outside the table: a row that is in no build and has no property)
 int pt_kernel_num_variants(void);

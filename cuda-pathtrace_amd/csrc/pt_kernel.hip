@@ -9,6 +9,65 @@
 
 #pragma clang fp contract(off)
 
+// The kernel variants, one row each (VariantInfo, pt_kernel.h; what the variants are: the list there).  A new variant or a new
+// build flavour is registered HERE: the kernels below, the selector, the launchers and pt_capi.hip follow the row.
+static constexpr int kNumVariants = 15;
+static constexpr int kT = PT_BLOCK_THREADS, kTG = PT_GRID_BLOCK_THREADS, kTW = PT_GRID_WIDE_THREADS;
+static constexpr int kW = PT_MIN_WAVES, kWG = PT_GRID_MIN_WAVES, kWD = PT_GRID12_MIN_WAVES, kWP = PT_POOL_MIN_WAVES;
+static constexpr VariantInfo kVariants[kNumVariants] = {
+    //        product lanes threads lean        LDS extra      grid            wide   ref    resume frames chunk family       chunks waves loop               tracer kernel
+    /*  0 */ {true,  1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   0,     0},
+    // 1-5, 7: measured negative results and stepping stones (DESIGN.md section 4)
+    /*  1 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   1,     1},
+    /*  2 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   2,     2},
+    /*  3 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PACKED, PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   3,     3},
+    /*  4 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   4,     4},
+    /*  5 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_SAMPLES,   5,     5},
+    /*  6 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_WALLS,  PT_GRID_NONE,   false, true,  true,  true,  PT_CHUNK_ONE_LANE, true,  kW,   PT_LOOP_SAMPLES,   6,     6},
+    /*  7 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_PAIRS,     6,     7},
+    /*  8 */ {true,  4, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true,  0,    PT_LOOP_SAMPLES,   6,     8},
+    /*  9 */ {true,  2, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true,  0,    PT_LOOP_SAMPLES,   6,     9},
+    /* 10 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, true,  false, PT_CHUNK_NONE,     false, kW,   PT_LOOP_REGEN,     6,     10},
+    // 11 (the grid walk with every lane testing its own spheres) and 12: superseded by 13, kept for A/B
+    /* 11 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false, kWG,  PT_LOOP_REGEN,     11,    11},
+    /* 12 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false, kWD,  PT_LOOP_DECOUPLED, 11,    12},
+    /* 13 */ {true,  1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, false, false, true,  false, PT_CHUNK_GRID,     true,  kWP,  PT_LOOP_REGEN,     13,    13},
+    // 14 is variant 13's kernel with WIDE (there is no VAR = 14 build).  It cannot chunk: the host has never chunked it, although
+    // that kernel could and its sample cap is the grid family's
+    /* 14 */ {true,  1, kTW, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, true,  false, true,  false, PT_CHUNK_GRID,     false, kWP,  PT_LOOP_REGEN,     13,    13},
+};
+static constexpr VariantInfo kNoVariant = {false, 1, kT, PT_LEAN_NEVER, PT_LDS_PLAIN, PT_GRID_NONE, false, false, false, false, PT_CHUNK_NONE, false, kW, PT_LOOP_SAMPLES, 0, 0};
+
+// What the kernels below rely on, so that a row and the builds behind it cannot disagree (r: a row, k: the row of the kernel that
+// executes it; inside pixel_kernel / pixel_kernel_split the other half: a build exists only where its kernel's row announces it)
+template <class P>
+constexpr bool every_row(P holds) {
+  for (int i = 0; i < kNumVariants; i++)
+    if (!holds(i, kVariants[i], kVariants[kVariants[i].kernel])) return false;
+  return true;
+}
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo&) { return r.kernel >= 0 && r.kernel < kNumVariants; }), "every row's kernel is a row");
+static_assert(every_row([](int i, const VariantInfo& r, const VariantInfo& k) { return (r.wide || r.kernel == i) && !k.wide; }), "only a wide row runs another row's kernel");
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo& k) { return !r.wide || (k.grid == PT_GRID_POOLED && r.threads == kTW); }), "a wide row names a pooled-grid kernel");
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo& k) { return (!r.resume || k.resume) && (!r.frames || k.frames) && (!r.ref_builds || k.ref_builds); }),
+              "a row's resume, frames and reference-configuration builds are its kernel's");
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo& k) {
+                return r.lean == k.lean && r.lds_extra == k.lds_extra && r.grid == k.grid && r.min_waves == k.min_waves && r.loop == k.loop && r.tracer == k.tracer;
+              }), "a wide row differs from its kernel's in the workgroup only");
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo&) { return !r.frames || (r.lanes == 1 && r.ref_builds); }), "frames builds: one-lane rows, reference configurations");
+static_assert(every_row([](int, const VariantInfo& r, const VariantInfo&) { return !r.split() || (!r.resume && !r.wide && r.grid == PT_GRID_NONE); }), "pixel_kernel_split: no resume, wide or grid builds");
+// the rows a kernel's template arguments name: pixel_kernel_split's by its lanes per pixel, a WIDE build's launch by its kernel
+constexpr int split_row(int lanes) {
+  for (int i = 0; i < kNumVariants; i++)
+    if (kVariants[i].split() && kVariants[i].lanes == lanes) return i;
+  return -1;
+}
+constexpr int launch_row(int kernel, bool wide) {
+  for (int i = 0; wide && i < kNumVariants; i++)
+    if (kVariants[i].wide && kVariants[i].kernel == kernel) return i;
+  return wide ? -1 : kernel;
+}
+
 namespace pt {
 
 // pixel_kernel: src/pathtrace.cu:203-257
@@ -17,10 +76,9 @@ namespace pt {
 // REFB != 0 builds the kernel for the reference's own scene size -- 9 spheres (Scene.h:23) -- and a fixed bounce cap as
 // compile-time constants: REFB = 5 is the reference's MAX_BOUNCES (pathtrace.cu:7), REFB = 8 the interactive configuration
 // (BASELINE.json configs[4]).  No generic loops, no index-width arithmetic, and a hot loop that is a third smaller.
+// (VAR is a row of kVariants: the kernel reads what it is from that row; WIDE only launches it as the wide row that names it)
 template <int VAR, bool WIDE = false>
-constexpr int kBlockThreads = (VAR == 13 && WIDE) ? PT_GRID_WIDE_THREADS : (VAR == 11 || VAR == 12 || VAR == 13) ? PT_GRID_BLOCK_THREADS : PT_BLOCK_THREADS;
-template <int VAR>
-constexpr int kMinWaves = (VAR == 11) ? PT_GRID_MIN_WAVES : (VAR == 13) ? PT_POOL_MIN_WAVES : (VAR == 12) ? PT_GRID12_MIN_WAVES : PT_MIN_WAVES;
+constexpr int kBlockThreads = kVariants[launch_row(VAR, WIDE)].threads;
 
 // the reference-configuration builds of variant 6 with the XORWOW generator fit 96 registers (12 bytes of spills, in cold code:
 // WRITE_SIZE stays at the algorithmic bytes): five waves per SIMD instead of four (headline frame 50.12 -> 49.81 ms, three
@@ -29,12 +87,8 @@ constexpr int kMinWaves = (VAR == 11) ? PT_GRID_MIN_WAVES : (VAR == 13) ? PT_POO
 // per sample) and gains 1.5 % (48.73 -> 47.98 ms, profiles/r03/README.md); the 8-bounce build (4 words) does not (0.0963 -> 0.0971 ms)
 // and keeps four waves, like every other build.
 template <int VAR, int REFB, int RNG>
-constexpr int kMinWavesR = (VAR == 6 && REFB != 0) ? (RNG == PT_RNG_XORWOW ? PT_REF_MIN_WAVES : (REFB == 5 ? PT_REF_MIN_WAVES_PHILOX : kMinWaves<VAR>)) : kMinWaves<VAR>;
-
-// builds that can chain a pixel's samples through several workgroups of one launch (sample chunking, below): the reference-
-// configuration builds of variant 6 and the pooled grid kernel
-template <int VAR, int REFB>
-constexpr bool kChunkable = (VAR == 6 && REFB != 0) || VAR == 13;
+constexpr int kMinWavesR = (kVariants[VAR].ref_builds && REFB != 0) ? (RNG == PT_RNG_XORWOW ? PT_REF_MIN_WAVES : (REFB == 5 ? PT_REF_MIN_WAVES_PHILOX : kVariants[VAR].min_waves))
+                                                                      : kVariants[VAR].min_waves;
 
 // ---- the hand-over chain of sample chunking (what it is for: pixel_kernel below) ------------------------------------------
 // chunk_flag[block]: bits 0-30 = chunks of the pixel block that have completed, bit 31 (PT_CHUNK_FAILED) = the chain is broken.
@@ -121,6 +175,9 @@ __global__ void __launch_bounds__((kBlockThreads<VAR, WIDE>), (((FRAMES || (RESU
 pixel_kernel(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type args) {  // (an XORWOW batch has one workgroup per pixel block for all its frames: the
                                                            // interactive shape fills four of a CU's five slots, so that build takes 128 registers)
   PixelKernelArgs& a = base_args<FRAMES, RESUME, ADAPTIVE>(args);
+  constexpr VariantInfo K = kVariants[VAR];  // this kernel's row
+  constexpr bool POOLED = K.grid == PT_GRID_POOLED;
+  static_assert(K.kernel == VAR && !K.split() && kVariants[launch_row(VAR, WIDE)].wide == WIDE, "a pixel_kernel build is a one-lane row's own kernel, WIDE a wide row's");
   static_assert(!ADAPTIVE || RESUME, "adaptive passes are resume builds");
   uint32_t n_active = 0u;  // (adaptive: the length of the active list; workgroup-uniform)
   if constexpr (ADAPTIVE) {
@@ -152,9 +209,11 @@ pixel_kernel(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type args) {  // (
     load_camera(fr);  // before the scene image is staged for this frame's eye
   }
   constexpr bool REF = REFB != 0;
-  constexpr bool CHUNKS = kChunkable<VAR, REFB> && !FRAMES && !RESUME;
-  static_assert(!FRAMES || (VAR == 6 && REFB != 0), "frame batches: reference-configuration builds of variant 6");
-  static_assert(!RESUME || (!FRAMES && (VAR == 6 || VAR == 10 || VAR == 13)), "progressive passes: variants 6, 10, 13 (14 = WIDE)");
+  constexpr bool CHUNKS = K.chunk_build(REF) && !FRAMES && !RESUME;
+  static_assert(!REF || K.ref_builds, "reference-configuration builds: the rows that announce them");
+  static_assert(!LEAN ? K.lean != PT_LEAN_ALWAYS : K.lean != PT_LEAN_NEVER, "the LDS layouts of the row");
+  static_assert(!FRAMES || (K.frames && REF), "frame batches: reference-configuration builds of the rows with frames (variant 6)");
+  static_assert(!RESUME || (!FRAMES && K.resume), "progressive passes: the rows with resume (variants 6, 10, 13; 14 = WIDE)");
   int sample_begin = 0;  // (a pass: the samples the session already holds; a.spp is the session's count after the pass)
   if constexpr (RESUME) sample_begin = args.sample_begin;
   const int pass_spp = a.spp - sample_begin;  // the cost heuristics below look at what this launch renders
@@ -168,19 +227,19 @@ pixel_kernel(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type args) {  // (
     if (a.repair != 0u && __hip_atomic_load(a.chunk_flag + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.repair) return;
   }
   extern __shared__ float4 lds_scene[];
-  SceneLds sc = stage_scene<VAR == 3>(a.spheres, a.n_spheres, lds_scene, LEAN, mk3(a.eye[0], a.eye[1], a.eye[2]), a.spp);
+  SceneLds sc = stage_scene<K.lds_extra == PT_LDS_PACKED>(a.spheres, a.n_spheres, lds_scene, LEAN, mk3(a.eye[0], a.eye[1], a.eye[2]), a.spp);
   // variants with a lean build run their LDS build only on scenes up to PT_SCREEN_MAX_SPHERES (launcher): the
   // many-sphere path is not even compiled into it, which keeps the hot loop's code small
-  sc.small_only = !LEAN && (VAR == 6 || VAR == 8 || VAR == 10);
+  sc.small_only = !LEAN && K.lean == PT_LEAN_BIG;
   // the 5-bounce reference-configuration builds of variant 6 screen secondary rays against the faced wall of each axis only
   // (pt_walls.h; the 8-bounce interactive build keeps the nine-sphere screen: DESIGN.md section 8)
-  if constexpr (VAR == 6 && REFB == 5 && !LEAN) stage_walls(sc, a.spheres, a.n_spheres);
-  constexpr bool kRegen = (VAR == 10 || VAR == 11 || VAR == 13);
+  if constexpr (K.lds_extra == PT_LDS_WALLS && REFB == 5 && !LEAN) stage_walls(sc, a.spheres, a.n_spheres);
+  constexpr bool kRegen = K.loop == PT_LOOP_REGEN, kDecoupled = K.loop == PT_LOOP_DECOUPLED;
   GridLds grid;
-  if constexpr (VAR == 11 || VAR == 12 || VAR == 13) {  // the frame's grid, built by build_grid_kernel just before this launch
-    grid = stage_grid<VAR == 13>(a.spheres, a.n_spheres, a.accel, lds_scene + a.scene_lds_f4);  // after the two small tables
+  if constexpr (K.grid != PT_GRID_NONE) {  // the frame's grid, built by build_grid_kernel just before this launch
+    grid = stage_grid<POOLED>(a.spheres, a.n_spheres, a.accel, lds_scene + a.scene_lds_f4);  // after the two small tables
     sc.grid = &grid;
-    if constexpr (VAR == 13)  // the test pool of each wave follows the grid image (16-byte aligned)
+    if constexpr (POOLED)  // the test pool of each wave follows the grid image (16-byte aligned)
       sc.pool = reinterpret_cast<char*>(lds_scene + a.scene_lds_f4) + ((grid_lds_bytes(a.n_spheres, true, kBlockThreads<VAR, WIDE>) + 15) & ~(size_t)15);
   }
 
@@ -255,14 +314,14 @@ frame_top:
       const uint32_t* rec = args.session;
       auto ld = [&](int w) { return rec[(size_t)w * a.tile_pixels + tp]; };
       auto ldf = [&](int w) { return __uint_as_float(ld(w)); };
-      L.color = mk3(ldf(0), ldf(1), ldf(2));
-      L.normal = mk3(ldf(3), ldf(4), ldf(5));
-      L.albedo = mk3(ldf(6), ldf(7), ldf(8));
-      L.depth = ldf(9);
-      const int n0 = (int)ld(10), n1 = (int)ld(11);
+      L.color = mk3(ldf(PT_REC_COLOR), ldf(PT_REC_COLOR + 1), ldf(PT_REC_COLOR + 2));
+      L.normal = mk3(ldf(PT_REC_NORMAL), ldf(PT_REC_NORMAL + 1), ldf(PT_REC_NORMAL + 2));
+      L.albedo = mk3(ldf(PT_REC_ALBEDO), ldf(PT_REC_ALBEDO + 1), ldf(PT_REC_ALBEDO + 2));
+      L.depth = ldf(PT_REC_DEPTH);
+      const int n0 = (int)ld(PT_REC_N_COLOR), n1 = (int)ld(PT_REC_N_HIT);
 #pragma unroll
-      for (int k = 0; k < 4; k++) var[k] = Welford{k == 0 ? n0 : n1, ldf(12 + 2 * k), ldf(13 + 2 * k)};
-      if constexpr (RNG == PT_RNG_XORWOW) rng.st = Xorwow{ld(20), ld(21), ld(22), ld(23), ld(24), ld(25)};
+      for (int k = 0; k < 4; k++) var[k] = Welford{k == 0 ? n0 : n1, ldf(PT_REC_MEAN + 2 * k), ldf(PT_REC_M2 + 2 * k)};
+      if constexpr (RNG == PT_RNG_XORWOW) rng.st = Xorwow{ld(PT_REC_RNG), ld(PT_REC_RNG + 1), ld(PT_REC_RNG + 2), ld(PT_REC_RNG + 3), ld(PT_REC_RNG + 4), ld(PT_REC_RNG + 5)};
     }
   }
   if constexpr (CHUNKS) {
@@ -275,14 +334,14 @@ frame_top:
         if (active) {
           auto ld = [&](int w) { return __hip_atomic_load(a.chunk_state + (size_t)w * a.tile_pixels + tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
           auto ldf = [&](int w) { return __uint_as_float(ld(w)); };
-          L.color = mk3(ldf(0), ldf(1), ldf(2));
-          L.normal = mk3(ldf(3), ldf(4), ldf(5));
-          L.albedo = mk3(ldf(6), ldf(7), ldf(8));
-          L.depth = ldf(9);
-          const int n0 = (int)ld(10), n1 = (int)ld(11);  // the three first-hit accumulators count together (welford_update3)
+          L.color = mk3(ldf(PT_REC_COLOR), ldf(PT_REC_COLOR + 1), ldf(PT_REC_COLOR + 2));
+          L.normal = mk3(ldf(PT_REC_NORMAL), ldf(PT_REC_NORMAL + 1), ldf(PT_REC_NORMAL + 2));
+          L.albedo = mk3(ldf(PT_REC_ALBEDO), ldf(PT_REC_ALBEDO + 1), ldf(PT_REC_ALBEDO + 2));
+          L.depth = ldf(PT_REC_DEPTH);
+          const int n0 = (int)ld(PT_REC_N_COLOR), n1 = (int)ld(PT_REC_N_HIT);  // the three first-hit accumulators count together (welford_update3)
 #pragma unroll
-          for (int k = 0; k < 4; k++) var[k] = Welford{k == 0 ? n0 : n1, ldf(12 + 2 * k), ldf(13 + 2 * k)};
-          if constexpr (RNG == PT_RNG_XORWOW) rng.st = Xorwow{ld(20), ld(21), ld(22), ld(23), ld(24), ld(25)};
+          for (int k = 0; k < 4; k++) var[k] = Welford{k == 0 ? n0 : n1, ldf(PT_REC_MEAN + 2 * k), ldf(PT_REC_M2 + 2 * k)};
+          if constexpr (RNG == PT_RNG_XORWOW) rng.st = Xorwow{ld(PT_REC_RNG), ld(PT_REC_RNG + 1), ld(PT_REC_RNG + 2), ld(PT_REC_RNG + 3), ld(PT_REC_RNG + 4), ld(PT_REC_RNG + 5)};
         }
       }
     }
@@ -317,7 +376,7 @@ frame_top:
     }
     return lerp(lerp(B0, B1, sy), lerp(B2, B3, sy), 1.0f - sx);
   };
-  if constexpr (REF && VAR == 6) {
+  if constexpr (REF) {
 #ifndef PT_NO_FOOTPRINT
     // once per pixel: the spheres this pixel's primary rays can return; the wave ranks the union at bounce 0
     if (pass_spp >= PT_FOOTPRINT_MIN_SPP) {
@@ -332,7 +391,7 @@ frame_top:
 
   int i = active ? i_begin : i_end;  // inactive lanes trace nothing ([i_begin, i_end): all samples unless the frame is chunked)
   bool prim_ok = false;  // variant 13: this pixel's primary rays take their spheres from the pixel's list instead of walking the grid
-  if constexpr (VAR == 13 && PT_PRIMLIST) {
+  if constexpr (POOLED && PT_PRIMLIST) {
     // once per pixel and workgroup: the grid spheres the pixel's primary rays can return (pt_primlist.h)
     if (grid.valid && pass_spp >= PT_PRIMLIST_MIN_SPP && a.max_bounces >= 1) {
       int k = 0;
@@ -372,14 +431,14 @@ frame_top:
     // the nearest-hit search as helpers of the pooled sphere tests, which otherwise run ever emptier towards the end of every workgroup)
     for (;;) {
       const bool live = i < i_end;
-      if constexpr (VAR == 13 && PT_POOL_HELPERS) {
+      if constexpr (POOLED && PT_POOL_HELPERS) {
         if (__builtin_amdgcn_ballot_w64(live) == 0) break;
       } else {
         if (!live) break;
       }
       if (by_progress) {
         int iu;  // the first lane that still works
-        if constexpr (VAR == 13 && PT_POOL_HELPERS) iu = __builtin_amdgcn_readlane(i, __builtin_ctzll(__builtin_amdgcn_ballot_w64(live)));
+        if constexpr (POOLED && PT_POOL_HELPERS) iu = __builtin_amdgcn_readlane(i, __builtin_ctzll(__builtin_amdgcn_ballot_w64(live)));
         else iu = __builtin_amdgcn_readfirstlane(i);
         const int band = (iu >= q1 ? 1 : 0) + (iu >= q2 ? 1 : 0) + (iu >= q3 ? 1 : 0);
         if (band != last_band) {  // wave-uniform
@@ -400,15 +459,14 @@ frame_top:
       bool escaped = false;
       if (n < a.max_bounces) {
         // (variant 13: a path's last bounce -- never its first -- needs neither the hit distance nor a next ray: pt_trace.h, pt_grid.h)
-        const bool dead_end = VAR == 13 && PT_V13_DEAD_END && (n > 0) & (n == a.max_bounces - 1);
-        escaped = !bounce_once<RNG, (VAR == 11 ? 11 : VAR == 13 ? 13 : 6)>(L, sc, a.n_spheres, o, d, color, mask, rng, var, n, live,
-                                                                           live & prim_ok & (n == 0), dead_end);
+        const bool dead_end = POOLED && PT_V13_DEAD_END && (n > 0) & (n == a.max_bounces - 1);
+        escaped = !bounce_once<RNG, K.tracer>(L, sc, a.n_spheres, o, d, color, mask, rng, var, n, live, live & prim_ok & (n == 0), dead_end);
         if (live) n++;
       }
       if (live & (escaped | (n >= a.max_bounces))) {
         if (!escaped) {
           L.color = L.color + color;                 // :198
-          if (sc.lean && !(VAR == 13 && PT_V13_WELFORD_TABLE)) welford_update(var[0], luminance(color)); else welford_update(var[0], luminance(color), sc.rcpn);  // :200
+          if (sc.lean && !(POOLED && PT_V13_WELFORD_TABLE)) welford_update(var[0], luminance(color)); else welford_update(var[0], luminance(color), sc.rcpn);  // :200
         }
         i++;
         n = 0;
@@ -416,7 +474,7 @@ frame_top:
     }
     if (by_progress) __builtin_amdgcn_s_setprio(0);
   }
-  if constexpr (VAR == 12) {
+  if constexpr (kDecoupled) {
     // Variant 11 with the nearest-hit search and the rest of the bounce at DIFFERENT times per lane.  In variant 11 a wave
     // walks the grid until its slowest lane is done (a ray needs 7 test trips, the wave makes 21: a quarter of the lanes
     // work) and only then shades.  Here a lane keeps its walk (GridWalk) across iterations of this loop: the wave leaves the
@@ -450,7 +508,7 @@ frame_top:
             if (brute) hit = intersect_scene_screened_large(sc, a.n_spheres, o, d, make_ray_const(d), t, idx);
             else hit = grid_end(w, sc, grid, a.n_spheres, o, d, t, idx);
           }
-          const bool escaped = !bounce_shade<RNG, 11>(L, sc, o, d, color, mask, rng, var, n, hit, t, idx);
+          const bool escaped = !bounce_shade<RNG, K.tracer>(L, sc, o, d, color, mask, rng, var, n, hit, t, idx);
           n++;
           if (escaped | (n >= a.max_bounces)) {
             if (!escaped) {
@@ -479,7 +537,7 @@ frame_top:
       grid_trips<true>(w, grid, o, d, in_walk & !brute, i < a.spp, PT_GRID_PARK);
     }
   }
-  if constexpr (VAR >= 7 && !kRegen && VAR != 12) {
+  if constexpr (K.loop == PT_LOOP_PAIRS) {
     const int draws = (a.spp != 1 ? 2 : 0) + 2 * a.max_bounces;  // consumed by a path that never escapes
     for (; i + 2 <= a.spp; i += 2) {
       Rng<RNG> g[2] = {rng, rng};
@@ -498,14 +556,14 @@ frame_top:
         rng.begin_sample((uint32_t)i + 1u);
         F3 dir;
         primary_ray(rng, dir);
-        trace_ray<RNG, 6>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);
+        trace_ray<RNG, K.tracer>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);
       } else {
         accumulate_path(L, var, res[1]);
         rng = g[1];
       }
     }
   }
-  if constexpr (!kRegen && VAR != 12) {
+  if constexpr (!kRegen && !kDecoupled) {  // sample after sample (and the odd sample the pairs leave)
     // Issue priority by progress (long waves only).  A SIMD serves its waves oldest first: of four waves that start together
     // the favoured one finishes in half the time its fair share would take and the last one finishes its work alone, which a
     // lone wave cannot do at more than ~45 % of the SIMD's issue rate (a frame of 1024 workgroups x 4096 spp: first wave done
@@ -534,7 +592,7 @@ frame_top:
       rng.begin_sample((uint32_t)i);
       F3 dir;
       primary_ray(rng, dir);
-      trace_ray<RNG, (VAR >= 7 ? 6 : VAR), REFB>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);  // :231
+      trace_ray<RNG, K.tracer, REFB>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);  // :231
     }
     if (by_progress) __builtin_amdgcn_s_setprio(0);
   }
@@ -543,19 +601,19 @@ frame_top:
       if (active) {
         auto st = [&](int w, uint32_t v) { a.chunk_state[(size_t)w * a.tile_pixels + tp] = v; };
         auto stf = [&](int w, float v) { st(w, __float_as_uint(v)); };
-        stf(0, L.color.x); stf(1, L.color.y); stf(2, L.color.z);
-        stf(3, L.normal.x); stf(4, L.normal.y); stf(5, L.normal.z);
-        stf(6, L.albedo.x); stf(7, L.albedo.y); stf(8, L.albedo.z);
-        stf(9, L.depth);
-        st(10, (uint32_t)var[0].n);
-        st(11, (uint32_t)var[1].n);
+        stf(PT_REC_COLOR, L.color.x); stf(PT_REC_COLOR + 1, L.color.y); stf(PT_REC_COLOR + 2, L.color.z);
+        stf(PT_REC_NORMAL, L.normal.x); stf(PT_REC_NORMAL + 1, L.normal.y); stf(PT_REC_NORMAL + 2, L.normal.z);
+        stf(PT_REC_ALBEDO, L.albedo.x); stf(PT_REC_ALBEDO + 1, L.albedo.y); stf(PT_REC_ALBEDO + 2, L.albedo.z);
+        stf(PT_REC_DEPTH, L.depth);
+        st(PT_REC_N_COLOR, (uint32_t)var[0].n);
+        st(PT_REC_N_HIT, (uint32_t)var[1].n);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          stf(12 + 2 * k, var[k].mean);
-          stf(13 + 2 * k, var[k].M2);
+          stf(PT_REC_MEAN + 2 * k, var[k].mean);
+          stf(PT_REC_M2 + 2 * k, var[k].M2);
         }
         if constexpr (RNG == PT_RNG_XORWOW) {
-          st(20, rng.st.d); st(21, rng.st.v0); st(22, rng.st.v1); st(23, rng.st.v2); st(24, rng.st.v3); st(25, rng.st.v4);
+          st(PT_REC_RNG, rng.st.d); st(PT_REC_RNG + 1, rng.st.v0); st(PT_REC_RNG + 2, rng.st.v1); st(PT_REC_RNG + 3, rng.st.v2); st(PT_REC_RNG + 4, rng.st.v3); st(PT_REC_RNG + 5, rng.st.v4);
         }
       }
       chunk_publish(a, block_id, chunk);
@@ -587,7 +645,7 @@ frame_top:
   } else {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool wave_full = (__builtin_amdgcn_ballot_w64(active) == ~0ull) && ((reinterpret_cast<uintptr_t>(out_f) & 15u) == 0u) &&
-                         VAR != 11 && VAR != 12 && VAR != 13;  // variants 11-13: the LDS holds the grid until the last wave is done: plain stores there
+                         K.grid == PT_GRID_NONE;  // variants 11-13: the LDS holds the grid until the last wave is done: plain stores there
   if (wave_full) {
     float* wl = reinterpret_cast<float*>(lds_scene + a.scene_lds_f4) + wave * (64 * 14);
 #pragma unroll
@@ -615,19 +673,19 @@ frame_top:
       uint32_t* rec = args.session;
       auto st = [&](int w, uint32_t v) { rec[(size_t)w * a.tile_pixels + tp] = v; };
       auto stf = [&](int w, float v) { st(w, __float_as_uint(v)); };
-      stf(0, L.color.x); stf(1, L.color.y); stf(2, L.color.z);
-      stf(3, L.normal.x); stf(4, L.normal.y); stf(5, L.normal.z);
-      stf(6, L.albedo.x); stf(7, L.albedo.y); stf(8, L.albedo.z);
-      stf(9, L.depth);
-      st(10, (uint32_t)var[0].n);
-      st(11, (uint32_t)var[1].n);
+      stf(PT_REC_COLOR, L.color.x); stf(PT_REC_COLOR + 1, L.color.y); stf(PT_REC_COLOR + 2, L.color.z);
+      stf(PT_REC_NORMAL, L.normal.x); stf(PT_REC_NORMAL + 1, L.normal.y); stf(PT_REC_NORMAL + 2, L.normal.z);
+      stf(PT_REC_ALBEDO, L.albedo.x); stf(PT_REC_ALBEDO + 1, L.albedo.y); stf(PT_REC_ALBEDO + 2, L.albedo.z);
+      stf(PT_REC_DEPTH, L.depth);
+      st(PT_REC_N_COLOR, (uint32_t)var[0].n);
+      st(PT_REC_N_HIT, (uint32_t)var[1].n);
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        stf(12 + 2 * k, var[k].mean);
-        stf(13 + 2 * k, var[k].M2);
+        stf(PT_REC_MEAN + 2 * k, var[k].mean);
+        stf(PT_REC_M2 + 2 * k, var[k].M2);
       }
       if constexpr (RNG == PT_RNG_XORWOW) {
-        st(20, rng.st.d); st(21, rng.st.v0); st(22, rng.st.v1); st(23, rng.st.v2); st(24, rng.st.v3); st(25, rng.st.v4);
+        st(PT_REC_RNG, rng.st.d); st(PT_REC_RNG + 1, rng.st.v0); st(PT_REC_RNG + 2, rng.st.v1); st(PT_REC_RNG + 3, rng.st.v2); st(PT_REC_RNG + 4, rng.st.v3); st(PT_REC_RNG + 5, rng.st.v4);
       }
     }
   }
@@ -674,6 +732,8 @@ constexpr int kRecWords = 24;  // 4 feature blocks {v0,v1,v2,x} + flags + 6 stat
 template <int RNG, int kSplit, bool LEAN = false, int REFB = 0>
 __global__ void __launch_bounds__(PT_BLOCK_THREADS) pixel_kernel_split(PixelKernelArgs a) {
   constexpr bool REF = REFB != 0;
+  constexpr VariantInfo K = kVariants[split_row(kSplit)];  // this kernel's row (variant 8 or 9)
+  static_assert(K.lanes == kSplit && K.threads == PT_BLOCK_THREADS && (!REF || K.ref_builds) && (!LEAN || K.lean == PT_LEAN_BIG), "a pixel_kernel_split build is one its row announces");
   if constexpr (REF) {
     a.n_spheres = 9;
     a.max_bounces = REFB;
@@ -684,7 +744,7 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS) pixel_kernel_split(PixelKern
   }
   extern __shared__ float4 lds_scene[];
   SceneLds sc = stage_scene<false>(a.spheres, a.n_spheres, lds_scene, LEAN, mk3(a.eye[0], a.eye[1], a.eye[2]), a.spp);
-  sc.small_only = !LEAN && (kSplit == 4 || REF);  // variant 8 has a lean build for larger scenes, variant 9 has not (its REF builds see 9 spheres)
+  sc.small_only = !LEAN && (K.lean == PT_LEAN_BIG || REF);  // variant 8 has a lean build for larger scenes, variant 9 has not (its REF builds see 9 spheres)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* xl = reinterpret_cast<float*>(lds_scene + a.scene_lds_f4) + wave * (64 * kRecWords);
   const int gbase = lane & ~(kSplit - 1);
@@ -692,7 +752,7 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS) pixel_kernel_split(PixelKern
   // Sample chunking as in pixel_kernel (reference-configuration builds): workgroup blockIdx.x = chunk * n_blocks + block renders
   // the samples [chunk * per, (chunk + 1) * per) of its 256 / kSplit pixels and hands their state to the next chunk through
   // chunk_state (same 26-word layout: every lane stores the features it owns, lane 0 of a pixel the true generator state).
-  constexpr bool CHUNKS = REF;
+  constexpr bool CHUNKS = K.chunk_build(REF);
   uint32_t block_id = blockIdx.x, chunk = 0u, n_chunks = 1u;
   if constexpr (CHUNKS) {
     if (a.chunks > 1u) {
@@ -779,13 +839,13 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS) pixel_kernel_split(PixelKern
 #pragma unroll
           for (int q = 0; q < kOwn; q++) {
             const int f = s * kOwn + q;  // 0 colour, 1 normal, 2 albedo, 3 depth
-            sum0[q] = ldf(f < 3 ? 3 * f : 9);
-            sum1[q] = f < 3 ? ldf(3 * f + 1) : 0.0f;
-            sum2[q] = f < 3 ? ldf(3 * f + 2) : 0.0f;
-            w[q] = Welford{(int)ld(f == 0 ? 10 : 11), ldf(12 + 2 * f), ldf(13 + 2 * f)};
+            sum0[q] = ldf(f < 3 ? PT_REC_COLOR + 3 * f : PT_REC_DEPTH);
+            sum1[q] = f < 3 ? ldf(PT_REC_COLOR + 3 * f + 1) : 0.0f;
+            sum2[q] = f < 3 ? ldf(PT_REC_COLOR + 3 * f + 2) : 0.0f;
+            w[q] = Welford{(int)ld(f == 0 ? PT_REC_N_COLOR : PT_REC_N_HIT), ldf(PT_REC_MEAN + 2 * f), ldf(PT_REC_M2 + 2 * f)};
           }
           if constexpr (RNG == PT_RNG_XORWOW) {  // the pixel's true state after sample i_begin - 1; lane s starts s samples further on
-            rng.st = Xorwow{ld(20), ld(21), ld(22), ld(23), ld(24), ld(25)};
+            rng.st = Xorwow{ld(PT_REC_RNG), ld(PT_REC_RNG + 1), ld(PT_REC_RNG + 2), ld(PT_REC_RNG + 3), ld(PT_REC_RNG + 4), ld(PT_REC_RNG + 5)};
             final_state = rng.st;
             xorwow_skip(rng.st, s * D);
           }
@@ -943,17 +1003,17 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS) pixel_kernel_split(PixelKern
         for (int q = 0; q < kOwn; q++) {
           const int f = s * kOwn + q;
           if (f < 3) {
-            stf(3 * f, sum0[q]); stf(3 * f + 1, sum1[q]); stf(3 * f + 2, sum2[q]);
+            stf(PT_REC_COLOR + 3 * f, sum0[q]); stf(PT_REC_COLOR + 3 * f + 1, sum1[q]); stf(PT_REC_COLOR + 3 * f + 2, sum2[q]);
           } else {
-            stf(9, sum0[q]);
+            stf(PT_REC_DEPTH, sum0[q]);
           }
-          if (f < 2) st(10 + f, (uint32_t)w[q].n);  // the three first-hit accumulators count together: the normal's stands for them
-          stf(12 + 2 * f, w[q].mean);
-          stf(13 + 2 * f, w[q].M2);
+          if (f < 2) st(PT_REC_N_COLOR + f, (uint32_t)w[q].n);  // the three first-hit accumulators count together: the normal's stands for them (PT_REC_N_HIT)
+          stf(PT_REC_MEAN + 2 * f, w[q].mean);
+          stf(PT_REC_M2 + 2 * f, w[q].M2);
         }
         if constexpr (RNG == PT_RNG_XORWOW) {
           if (s == 0) {
-            st(20, final_state.d); st(21, final_state.v0); st(22, final_state.v1); st(23, final_state.v2); st(24, final_state.v3); st(25, final_state.v4);
+            st(PT_REC_RNG, final_state.d); st(PT_REC_RNG + 1, final_state.v0); st(PT_REC_RNG + 2, final_state.v1); st(PT_REC_RNG + 3, final_state.v2); st(PT_REC_RNG + 4, final_state.v3); st(PT_REC_RNG + 5, final_state.v4);
           }
         }
       }
@@ -1017,33 +1077,6 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS)
 // ---- launchers (host) ---------------------------------------------------------------------
 #include <utility>
 
-// The kernel variants, one row each (VariantInfo, pt_kernel.h; what the variants are: the list there).  A new variant or a new
-// build flavour is registered HERE: the selector, the launchers and pt_capi.hip follow the row.
-static constexpr int kNumVariants = 15;
-static constexpr int kT = PT_BLOCK_THREADS, kTG = PT_GRID_BLOCK_THREADS, kTW = PT_GRID_WIDE_THREADS;
-static constexpr VariantInfo kVariants[kNumVariants] = {
-    //        product lanes threads lean        LDS extra      grid            wide   ref    resume frames chunk family       can chunk
-    /*  0 */ {true,  1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    // 1-5, 7: measured negative results and stepping stones (DESIGN.md section 4)
-    /*  1 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  2 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  3 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PACKED, PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  4 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  5 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  6 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_WALLS,  PT_GRID_NONE,   false, true,  true,  true,  PT_CHUNK_ONE_LANE, true},
-    /*  7 */ {false, 1, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /*  8 */ {true,  4, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true},
-    /*  9 */ {true,  2, kT,  PT_LEAN_NEVER,  PT_LDS_PLAIN,  PT_GRID_NONE,   false, true,  false, false, PT_CHUNK_SPLIT,    true},
-    /* 10 */ {true,  1, kT,  PT_LEAN_BIG,    PT_LDS_PLAIN,  PT_GRID_NONE,   false, false, true,  false, PT_CHUNK_NONE,     false},
-    // 11 (the grid walk with every lane testing its own spheres) and 12: superseded by 13, kept for A/B
-    /* 11 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /* 12 */ {false, 1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_LANE,   false, false, false, false, PT_CHUNK_NONE,     false},
-    /* 13 */ {true,  1, kTG, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, false, false, true,  false, PT_CHUNK_GRID,     true},
-    // 14 cannot chunk: the host has never chunked it, although its kernel (variant 13's) could and its sample cap is the grid family's
-    /* 14 */ {true,  1, kTW, PT_LEAN_ALWAYS, PT_LDS_PLAIN,  PT_GRID_POOLED, true,  false, true,  false, PT_CHUNK_GRID,     false},
-};
-static constexpr VariantInfo kNoVariant = {false, 1, kT, PT_LEAN_NEVER, PT_LDS_PLAIN, PT_GRID_NONE, false, false, false, false, PT_CHUNK_NONE, false};
-
 const VariantInfo& pt_kernel_variant(int variant) { return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : kNoVariant; }
 int pt_kernel_num_variants(void) { return kNumVariants; }
 int pt_kernel_block_threads(int variant) { return pt_kernel_variant(variant).threads; }
@@ -1085,7 +1118,7 @@ template <bool FRAMES, bool RESUME, bool ADAPTIVE, int RNG, int VAR, bool LEAN, 
 static kernel_fn<FRAMES, RESUME, ADAPTIVE> kernel_build() {
   constexpr VariantInfo v = kVariants[VAR];
   if constexpr (v.split()) return pt::pixel_kernel_split<RNG, v.lanes, LEAN, REFB>;
-  else return pt::pixel_kernel<RNG, (VAR == 14 ? 13 : VAR), LEAN, REFB, FRAMES, v.wide, RESUME, ADAPTIVE>;  // variant 14 is variant 13's kernel with WIDE: there is no VAR = 14 build
+  else return pt::pixel_kernel<RNG, v.kernel, LEAN, REFB, FRAMES, v.wide, RESUME, ADAPTIVE>;  // (a wide row: its kernel's build with WIDE)
 }
 
 // Variant VAR's build of one flavour for a launch's LDS layout and reference configuration, or null.  Only the builds the row
@@ -1116,7 +1149,8 @@ static kernel_fn<FRAMES, RESUME, ADAPTIVE> select_kernel_of(int variant, bool le
   return (variant >= 0 && variant < kNumVariants) ? of[variant](lean, ref) : nullptr;
 }
 
-// variant 12's loop assumes every ray is searched for: without bounces it runs variant 11's kernel
+// variant 12's loop assumes every ray is searched for: without bounces it runs variant 11's kernel.  (A rule about a launch's
+// max_bounces, not a property of a build: the one place outside the table that names variants.)
 static inline int run_variant(int variant, int max_bounces) { return (variant == 12 && max_bounces < 1) ? 11 : variant; }
 
 template <bool FRAMES = false, bool RESUME = false, bool ADAPTIVE = false>
@@ -1197,8 +1231,7 @@ void pt_kernel_grid_layout(int n_spheres, int threads, uint64_t out[8]) {
 // does a launch with these arguments chain a pixel's samples through several workgroups (sample chunking)?
 bool pt_kernel_chunked(int variant, int n_spheres, int max_bounces, bool planar, int spp, uint32_t chunks) {
   const VariantInfo& v = pt_kernel_variant(variant);
-  // of a variant with reference-configuration builds only those hand a pixel's state from workgroup to workgroup (kChunkable)
-  const bool build_chunks = v.can_chunk && (!v.ref_builds || (!lds_lean(n_spheres, v) && ref_config(n_spheres, max_bounces, v, planar)));
+  const bool build_chunks = v.chunk_build(!lds_lean(n_spheres, v) && ref_config(n_spheres, max_bounces, v, planar));  // (what the kernel was compiled by)
   return build_chunks && chunks > 1u && chunks <= (uint32_t)PT_CHUNKS_MAX && spp >= 2 * (int)chunks &&
          (spp + (int)chunks - 1) / (int)chunks <= (v.chunk_family == PT_CHUNK_GRID ? PT_CHUNK_MAX_SAMPLES_GRID : PT_CHUNK_MAX_SAMPLES);
 }

@@ -9,6 +9,10 @@
 
 namespace pt {
 
+// LEVEL (here and in pt_intersect.h) is the tracer level, the `tracer` column of the variant table (VariantInfo, pt_kernel.h),
+// not a variant number: 0 literal, 1 lean FP64, 2 screened, 3 + packed FP32, 4 + cheap sqrt / rsqrt, 5 branch-free keys,
+// 6 straight-line speculation, 11 / 13 = 6 with the nearest-hit search through the uniform grid, per lane / pooled per wave.
+// The comparisons below (>= 4, >= 5, >= 6, == 11, == 13) DEFINE the levels.
 // One iteration of the bounce loop (src/pathtrace.cu:155-196) at depth n; false = the ray left the scene
 // (:157-161, the path's colour has been added to L.color and the path is over).
 // PRIMARY (only ever with n == 0): o is the eye the scene image was staged for, see SceneLds::eyeg
@@ -16,7 +20,7 @@ namespace pt {
 // the part of the iteration after intersectScene (:156): hit/t/idx are its results
 // `dead_end` (variant 13's regeneration loop; never with n == 0): the path ends after this iteration, so the next ray is not
 // formed -- the generator still makes its two draws (:131), which is all of :176-180 that outlives the iteration
-template <int RNG, int VAR>
+template <int RNG, int LEVEL>
 __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc, F3& o, F3& d, F3& color, F3& mask,
                                              Rng<RNG>& rng, Welford (&var)[4], int n, bool hit, float t, int idx, bool dead_end = false) {
   if (!hit) {  // :157-161
@@ -31,7 +35,7 @@ __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc,
   fetch_material(sc, idx, emis, scol, n == 0 ? &lum_col : nullptr);
   F3 normal = mk3(0.0f, 0.0f, 0.0f);
   float u_az, u_el;
-  if constexpr (VAR >= 6) {
+  if constexpr (LEVEL >= 6) {
     // whole geometric step speculatively with the cheap sequences, literal redo if any of them
     // met an input outside its verified domain (never observed in the Cornell box)
     rng.bounce(n, u_az, u_el);
@@ -48,11 +52,11 @@ __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc,
   } else {
     F3 pos = o + d * t;                                // :163
     normal = pos - mk3(g.x, g.y, g.z);                 // :164
-    if constexpr (VAR >= 4) normal = normalize_fast(normal); else normal = normalize(normal);
+    if constexpr (LEVEL >= 4) normal = normalize_fast(normal); else normal = normalize(normal);
     if (!(dot(normal, d) < 0.0f)) normal = normal * -1.0f;  // :166
     o = pos + normal * 0.05f;         // :178, PUSH_RAY_ORIGIN
     rng.bounce(n, u_az, u_el);
-    if constexpr (VAR >= 4)
+    if constexpr (LEVEL >= 4)
       d = normalize_fast(cosine_weighted_fast(normal, u_az, u_el));  // :180
     else
       d = normalize(cosine_weighted(normal, u_az, u_el));
@@ -67,7 +71,7 @@ __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc,
     L.normal = L.normal + normal;
     L.albedo = L.albedo + scol;
     L.depth += t;
-    if (VAR >= 6 && (!sc.lean || (VAR == 13 && PT_V13_WELFORD_TABLE))) {  // (the lean brute-force kernels keep the division; the grid kernel shares ONE count and the table)
+    if (LEVEL >= 6 && (!sc.lean || (LEVEL == 13 && PT_V13_WELFORD_TABLE))) {  // (the lean brute-force kernels keep the division; the grid kernel shares ONE count and the table)
       welford_update3(var[1], var[2], var[3], luminance(normal), lum_col, t, sc.rcpn);
     } else {
       welford_update(var[1], luminance(normal));
@@ -82,48 +86,48 @@ __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc,
 // the t handed to bounce_shade are dead, and the nearest-hit search may return any t (intersect_scene_screened_keys)
 // `live` (variant 13's regeneration loop only): false for a lane whose pixel is finished -- it goes through the nearest-hit search
 // as a helper of the wave's pooled tests and changes nothing of its own
-template <int RNG, int VAR, bool PRIMARY = false, bool LAST = false>
+template <int RNG, int LEVEL, bool PRIMARY = false, bool LAST = false>
 __device__ __forceinline__ bool bounce_once(TraceOutput& L, const SceneLds& sc, int nsph, F3& o, F3& d, F3& color, F3& mask,
                                             Rng<RNG>& rng, Welford (&var)[4], int n, bool live = true, bool prim = false,
                                             bool dead_end = false) {
   float t = 0.0f;
   int idx = 0;
   bool hit;
-  if constexpr (VAR == 11)
+  if constexpr (LEVEL == 11)
     hit = intersect_scene_v11(sc, nsph, o, d, t, idx);
-  else if constexpr (VAR == 13)
+  else if constexpr (LEVEL == 13)
     hit = intersect_scene_v13(sc, nsph, o, d, t, idx, live, prim, dead_end);  // prim: a primary ray of a pixel with a list (pt_primlist.h)
   else
-    hit = intersect_scene<VAR, PRIMARY, LAST>(sc, nsph, o, d, t, idx);
-  if (VAR == 13 && !live) return true;
-  return bounce_shade<RNG, VAR>(L, sc, o, d, color, mask, rng, var, n, hit, t, idx, dead_end);
+    hit = intersect_scene<LEVEL, PRIMARY, LAST>(sc, nsph, o, d, t, idx);
+  if (LEVEL == 13 && !live) return true;
+  return bounce_shade<RNG, LEVEL>(L, sc, o, d, color, mask, rng, var, n, hit, t, idx, dead_end);
 }
 
 // trace_ray: src/pathtrace.cu:150-201
 // UNROLL_MB: a bounce count known at compile time (the kernel builds for one scene size and bounce cap, pt_kernel.hip: the
 // reference's MAX_BOUNCES 5, and the 8 of the interactive configuration) for which the path is emitted straight-line; the
 // generic builds (0) unroll the reference's five only.
-template <int RNG, int VAR, int UNROLL_MB = 0>
+template <int RNG, int LEVEL, int UNROLL_MB = 0>
 __device__ __forceinline__ void trace_ray(TraceOutput& L, const SceneLds& sc, int nsph, F3 o, F3 d, Rng<RNG>& rng,
                                           Welford (&var)[4], int max_bounces) {
   F3 color = mk3(0.0f, 0.0f, 0.0f);
   F3 mask = mk3(1.0f, 1.0f, 1.0f);
 #if PT_UNROLL_BOUNCES
   constexpr int kMB = UNROLL_MB >= 2 ? UNROLL_MB : 5;
-  if (VAR >= 6 && max_bounces == kMB) {  // straight-line, no loop state, n folds to constants
-    if (!bounce_once<RNG, VAR, true>(L, sc, nsph, o, d, color, mask, rng, var, 0)) return;  // trace_ray starts at the eye
+  if (LEVEL >= 6 && max_bounces == kMB) {  // straight-line, no loop state, n folds to constants
+    if (!bounce_once<RNG, LEVEL, true>(L, sc, nsph, o, d, color, mask, rng, var, 0)) return;  // trace_ray starts at the eye
 #pragma unroll
     for (int n = 1; n < kMB - 1; n++)
-      if (!bounce_once<RNG, VAR>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
-    if (!bounce_once<RNG, VAR, false, true>(L, sc, nsph, o, d, color, mask, rng, var, kMB - 1)) return;  // the last: colour only
+      if (!bounce_once<RNG, LEVEL>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
+    if (!bounce_once<RNG, LEVEL, false, true>(L, sc, nsph, o, d, color, mask, rng, var, kMB - 1)) return;  // the last: colour only
   } else
 #endif
   {
     for (int n = 0; n < max_bounces; n++)
-      if (!bounce_once<RNG, VAR>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
+      if (!bounce_once<RNG, LEVEL>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
   }
   L.color = L.color + color;                    // :198
-  if (VAR >= 6 && !sc.lean) welford_update(var[0], luminance(color), sc.rcpn); else welford_update(var[0], luminance(color));  // :200
+  if (LEVEL >= 6 && !sc.lean) welford_update(var[0], luminance(color), sc.rcpn); else welford_update(var[0], luminance(color));  // :200
 }
 
 // ---- variant 7: two samples of a pixel in lockstep ---------------------------------------------

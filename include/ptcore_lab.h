@@ -91,7 +91,10 @@ int pt_debug_denoiser_conv_plan(pt_denoiser* d, int n_frames, int conv, int info
 /* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
  * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */
 int pt_debug_progressive_set_samples(pt_progressive* p, int64_t samples);
-/* A copy of the session's record: PT_CHUNK_WORDS (26) words per tile pixel, [word][pixel] (synchronous). */
+/* A copy of the session's record: PT_CHUNK_WORDS (26) words per tile pixel, [word][pixel] (synchronous).  Words (PT_REC_*,
+ * csrc/pt_kernel.h): 0-8 the sums of colour, normal and albedo (x y z each), 9 the depth sum, 10 / 11 the Welford counts (the
+ * colour's; the one the three first-hit accumulators share), 12-19 {mean, M2} of colour, normal, albedo, depth, 20-25 the
+ * XORWOW generator d, v0 .. v4 (unused by philox sessions). */
 int pt_debug_progressive_record(pt_progressive* p, uint32_t* host);
 /* Adaptive sessions after their first pass: the next pass renders exactly the pixels whose byte in host_mask (one per tile
  * pixel) is non-zero, without the rule.  The set may only shrink: a pixel the last pass did not render is PT_EINVAL. */
