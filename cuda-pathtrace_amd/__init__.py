@@ -155,6 +155,15 @@ ABI = {
     "pt_denoiser_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_denoiser_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pt_denoiser_denoise_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _fp]),
+    "pt_filter_opts_default": (None, [_vp]),
+    "pt_filter_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "pt_filter_destroy": (ctypes.c_int, [_vp]),
+    "pt_filter_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_filter_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_filter_enqueue": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "pt_filter_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _fp]),
+    "pt_filter_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "pt_filter_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _fp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -189,6 +198,8 @@ LAB_ABI = {
     "pt_debug_denoiser_memory": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "pt_debug_denoiser_last_enqueue": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_denoiser_conv_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "pt_debug_filter_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
+    "pt_debug_filter_tiled": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "pt_debug_progressive_record": (ctypes.c_int, [_vp, _vp]),
     "pt_debug_progressive_set_active": (ctypes.c_int, [_vp, _vp]),
@@ -917,3 +928,135 @@ def denoise_frames(frames, weights, out_of_place=False, denoiser=None, precision
             d_rgb.free()
         if denoiser is None:
             dn.destroy()
+
+
+class FilterOpts(ctypes.Structure):
+    """pt_filter_opts (include/ptcore.h)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_l", ctypes.c_float), ("sigma_n", ctypes.c_float), ("sigma_a", ctypes.c_float),
+                ("sigma_z", ctypes.c_float), ("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class FeatureFilter:
+    """ctypes view of pt_filter: the weights-free denoiser for width x height frames, a variance-guided edge-avoiding a-trous
+    filter on albedo-demodulated colour (DENOISER.md, "Feature-guided filter").  max_frames > 1 reserves the workspace for
+    batches of that many frames per group.  samples: the frame's count per pixel; d_counts: a device uint32 [H][W] count image
+    (Progressive.counts' layout) that replaces it."""
+
+    def __init__(self, width, height, max_frames=1, iterations=5, sigma_l=4.0, sigma_n=0.35, sigma_a=0.1, sigma_z=1.0):
+        self.handle = None
+        opts = FilterOpts(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_a=sigma_a, sigma_z=sigma_z, max_frames=max_frames)
+        h = _vp()
+        check(lib.pt_filter_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height = width, height
+        self.max_frames = max_frames
+        self.iterations = iterations
+
+    def reserve_frames(self, n):
+        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
+        check(lib.pt_filter_reserve_frames(self.handle, n))
+        self.max_frames = max(self.max_frames, n)
+
+    def memory(self):
+        """{"workspace": bytes of the state and guide images of all max_frames frames, "per_pixel": bytes per pixel and frame}."""
+        b = ctypes.c_uint64(0)
+        check(lib.pt_filter_workspace_bytes(self.handle, ctypes.byref(b)))
+        return {"workspace": int(b.value), "per_pixel": int(b.value) // (self.max_frames * self.width * self.height)}
+
+    def _strides(self, frame_stride_floats, rgb_stride_floats):
+        px = self.width * self.height
+        return (px * CHANNELS if frame_stride_floats is None else frame_stride_floats,
+                px * 3 if rgb_stride_floats is None else rgb_stride_floats)
+
+    def enqueue(self, d_frame, samples, d_rgb=None, d_counts=None, stream=None):
+        """Asynchronous; d_rgb None = in place on the [H][W][14] frame, else [H][W][3] into d_rgb (frame untouched)."""
+        check(lib.pt_filter_enqueue(self.handle, d_frame, d_rgb, samples, d_counts, stream))
+
+    def run(self, d_frame, samples, d_rgb=None, d_counts=None):
+        """Synchronous; returns device-event milliseconds."""
+        ms = ctypes.c_float(0)
+        check(lib.pt_filter_run(self.handle, d_frame, d_rgb, samples, d_counts, ctypes.byref(ms)))
+        return ms.value
+
+    def enqueue_frames(self, d_frames, n, samples, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None, stream=None):
+        """Asynchronous; n frames at d_frames + k * frame_stride_floats (default: packed [n][H][W][14]), in place or, with d_rgb,
+        [H][W][3] at d_rgb + k * rgb_stride_floats (default packed): bit for bit n single enqueues."""
+        fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
+        check(lib.pt_filter_enqueue_frames(self.handle, n, d_frames, fs, d_rgb, rs, samples, stream))
+
+    def run_frames(self, d_frames, n, samples, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None):
+        """Synchronous enqueue_frames; returns device-event milliseconds."""
+        fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
+        ms = ctypes.c_float(0)
+        check(lib.pt_filter_run_frames(self.handle, n, d_frames, fs, d_rgb, rs, samples, ctypes.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _lab(name):
+        if not IS_LAB:
+            raise RuntimeError(f"{name} is a diagnostic of libptcore_lab.so (include/ptcore_lab.h); the product library has none")
+        return getattr(lib, name)
+
+    def step(self, d_frame, samples, step, d_rgb=None, d_counts=None):
+        """Lab library only: the set-up and one iteration at `step`, fused with the re-modulation; synchronous."""
+        check(self._lab("pt_debug_filter_step")(self.handle, d_frame, d_rgb, samples, d_counts, step))
+
+    def tiled(self, on):
+        """Lab library only: steps 1 and 2 through the LDS tile (True) or with direct loads (False)."""
+        check(self._lab("pt_debug_filter_tiled")(self.handle, int(bool(on))))
+
+    def destroy(self):
+        if self.handle:
+            check(lib.pt_filter_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **opts):
+    """Convenience for tests: upload a host [H][W][14] frame, filter it on the GPU, download.  Returns the frame after the
+    in-place step, or (frame untouched, rgb [H][W][3]) with out_of_place=True.  counts: a host uint32 [H][W] count image.
+    opts: of the FeatureFilter made here (iterations, sigma_*)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    h, w = frame.shape[:2]
+    ff = filt or FeatureFilter(w, h, **opts)
+    d_frame = DeviceBuffer(frame.nbytes).upload(frame)
+    d_rgb = DeviceBuffer(h * w * 12) if out_of_place else None
+    d_counts = DeviceBuffer(h * w * 4).upload(np.ascontiguousarray(counts, dtype=np.uint32)) if counts is not None else None
+    try:
+        ff.run(d_frame.ptr, samples, d_rgb.ptr if d_rgb else None, d_counts.ptr if d_counts else None)
+        f = d_frame.download(np.float32, frame.shape)
+        return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
+    finally:
+        d_frame.free()
+        if d_rgb:
+            d_rgb.free()
+        if d_counts:
+            d_counts.free()
+        if filt is None:
+            ff.destroy()
+
+
+def filter_frames(frames, samples, out_of_place=False, filt=None, **opts):
+    """The batched twin of filter_frame: host frames [N][H][W][14] through ONE pt_filter_run_frames call (a filter reserved
+    for all N frames unless one is given).  Returns the frames after the in-place step, or (frames untouched, rgb
+    [N][H][W][3]) with out_of_place=True."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    n, h, w = frames.shape[:3]
+    ff = filt or FeatureFilter(w, h, max_frames=n, **opts)
+    d_frames = DeviceBuffer(frames.nbytes).upload(frames)
+    d_rgb = DeviceBuffer(n * h * w * 12) if out_of_place else None
+    try:
+        ff.run_frames(d_frames.ptr, n, samples, d_rgb=d_rgb.ptr if d_rgb else None)
+        f = d_frames.download(np.float32, frames.shape)
+        return (f, d_rgb.download(np.float32, (n, h, w, 3))) if out_of_place else f
+    finally:
+        d_frames.free()
+        if d_rgb:
+            d_rgb.free()
+        if filt is None:
+            ff.destroy()

@@ -14,7 +14,9 @@
 // interactive mode, per-frame times are summarised), --gpus N (the frame row-tiled over devices
 // --device .. --device+N-1 by one process: MultiRenderer / pt_mgpu_*, RCCL gather to the first device), --progressive N
 // (the still frame refined in N passes of -s samples each into one buffer: ProgressiveRenderer / pt_progressive_*; the
-// saved frame is bit for bit the one -s N*S writes, the one-pass variant of the interactive loop with the camera at rest).
+// saved frame is bit for bit the one -s N*S writes, the one-pass variant of the interactive loop with the camera at rest),
+// --filter (the weights-free denoiser, FeatureFilter / pt_filter_*: every frame of the headless loop and every progressive pass
+// is filtered in place after Render(), where -d would run the network; the saved EXR and bitmaps hold the filtered frame).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -30,6 +32,7 @@
 #include "Camera.h"
 #include "DenoiseNet.h"
 #include "Denoiser.h"
+#include "FeatureFilter.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
 #include "ProgressiveRenderer.h"
@@ -68,6 +71,9 @@ static void usage() {
                "                                standard error <= arg; ends early when no pixel is active\n"
                "  --adaptive-min arg            with --adaptive: no pixel stops before this many samples (default 16)\n"
                "  --adaptive-radius arg         with --adaptive: dilation radius 0..4 (default 1)\n"
+               "  --filter                      denoise without weights: variance-guided a-trous filter on every frame\n"
+               "  --filter-iterations arg       with --filter: a-trous iterations 1..8 (default 5)\n"
+               "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
             << std::endl;
 }
 
@@ -94,6 +100,10 @@ int main(int argc, const char** argv) {
   int adaptiveMin = 16, adaptiveRadius = 1;
   const float adaptiveFloor = 0.05f;
   bool adaptiveMinGiven = false, adaptiveRadiusGiven = false;
+  // --filter: the feature-guided filter (pt_filter_*) in place after every Render() / progressive pass
+  bool filtering = false, filterIterationsGiven = false, filterSigmaGiven = false;
+  int filterIterations = 5;
+  std::string filterSigma;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -129,6 +139,9 @@ int main(int argc, const char** argv) {
     else if (a == "--adaptive") { adaptiveTol = atof(value("--adaptive")); adaptiveGiven = true; }
     else if (a == "--adaptive-min") { adaptiveMin = atoi(value("--adaptive-min")); adaptiveMinGiven = true; }
     else if (a == "--adaptive-radius") { adaptiveRadius = atoi(value("--adaptive-radius")); adaptiveRadiusGiven = true; }
+    else if (a == "--filter") filtering = true;
+    else if (a == "--filter-iterations") { filterIterations = atoi(value("--filter-iterations")); filterIterationsGiven = true; }
+    else if (a == "--filter-sigma") { filterSigma = value("--filter-sigma"); filterSigmaGiven = true; }
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -183,6 +196,41 @@ int main(int argc, const char** argv) {
   if (denoising && batch) {
     std::cerr << "ERROR: -d cannot be combined with --batch: the denoiser runs after every frame of the loop" << std::endl;
     return 1;
+  }
+  pt_filter_opts filterOpts;
+  pt_filter_opts_default(&filterOpts);
+  if ((filterIterationsGiven || filterSigmaGiven) && !filtering) {  // (before any device is touched)
+    std::cerr << "ERROR: " << (filterIterationsGiven ? "--filter-iterations" : "--filter-sigma")
+              << " needs --filter: it sets an option of the feature-guided filter" << std::endl;
+    return 1;
+  }
+  if (filtering) {
+    if (denoising) {
+      std::cerr << "ERROR: --filter cannot be combined with -d: choose the filter or the network" << std::endl;
+      return 1;
+    }
+    if (batch) {
+      std::cerr << "ERROR: --filter cannot be combined with --batch: the filter runs after every frame of the loop" << std::endl;
+      return 1;
+    }
+    if (filterIterationsGiven && (filterIterations < 1 || filterIterations > 8)) {
+      std::cerr << "ERROR: --filter-iterations " << filterIterations << ": 1 .. 8" << std::endl;
+      return 1;
+    }
+    filterOpts.iterations = filterIterations;
+    if (filterSigmaGiven) {
+      float v[4];
+      char extra;
+      const int got = sscanf(filterSigma.c_str(), "%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &extra);
+      bool ok = got == 4;
+      for (int k = 0; ok && k < 4; k++) ok = v[k] > 0.0f && v[k] <= 3.4028234663852886e38f;
+      if (!ok) {
+        std::cerr << "ERROR: --filter-sigma '" << filterSigma << "': four finite numbers > 0 as l,n,a,z (luminance, normal, albedo, depth)"
+                  << std::endl;
+        return 1;
+      }
+      filterOpts.sigma_l = v[0], filterOpts.sigma_n = v[1], filterOpts.sigma_a = v[2], filterOpts.sigma_z = v[3];
+    }
   }
   if ((adaptiveGiven || adaptiveMinGiven || adaptiveRadiusGiven) && !progressiveGiven) {  // (before any device is touched)
     std::cerr << "ERROR: " << (adaptiveGiven ? "--adaptive" : adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius")
@@ -261,10 +309,13 @@ int main(int argc, const char** argv) {
   // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
   DenoiseNet* net =
       denoising ? new DenoiseNet(width, height, denoiseWeights, 1, denoisePrecision == "half" ? PT_DENOISE_F16 : PT_DENOISE_F32) : NULL;
-  float denoiseTime = 0.0f;
+  // --filter: likewise on the first device, after the gather
+  FeatureFilter* filter = filtering ? new FeatureFilter(width, height, filterOpts) : NULL;
+  float denoiseTime = 0.0f, filterTime = 0.0f;
   auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
     if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
+    if (filter) filterTime = filter->Filter(b, samplesPerPixel);
     return ms;
   };
   Camera camera(glm::vec3(cameraPos[0], cameraPos[1], cameraPos[2]), cameraView[0], cameraView[1]);  // main.cu:128 verbatim
@@ -341,8 +392,10 @@ int main(int argc, const char** argv) {
       }
       times.push_back(session.Refine(d_buffer, scene, camera, samplesPerPixel));
       if (net) denoiseTime = net->Denoise(d_buffer);
+      if (adaptiveGiven) session.Counts(d_counts);
+      // --filter: with the session's count so far; under --adaptive with every pixel's own count
+      if (filter) filterTime = filter->Filter(d_buffer, (int)session.Samples(), d_counts);
       if (adaptiveGiven) {
-        session.Counts(d_counts);
         gpuErrchk(pt_memcpy_d2h(counts.data(), d_counts, counts.size() * sizeof(unsigned int)));
         double spp = 0;
         for (unsigned int c : counts) spp += c;
@@ -364,6 +417,7 @@ int main(int argc, const char** argv) {
   }
   std::cout << "Render completed in " << renderTime << "ms (" << 1000.0f / renderTime << " fps)" << std::endl;
   if (net) std::cout << "Denoise completed in " << denoiseTime << "ms" << std::endl;
+  if (filter) std::cout << "Filter completed in " << filterTime << "ms" << std::endl;
   if (tiled) {
     std::cout << "Tile kernel times:";
     for (int g = 0; g < gpus; g++) std::cout << " " << tiled->TileKernelMs(g) << "ms";
@@ -401,6 +455,7 @@ int main(int argc, const char** argv) {
   if (!noBitmap) buffer.SaveBitmaps(outputName);
   buffer.FreeCPU();
   delete net;
+  delete filter;
   delete single;
   delete tiled;
   if (batch_frames) (void)pt_free(batch_frames);  // (d_buffer points into it)

@@ -350,6 +350,72 @@ int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, si
 int pt_denoiser_denoise_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
                                size_t rgb_stride_floats, float* ms_out);
 
+/* ---- feature-guided filter: the weights-free denoiser --------------------------------------- */
+/* No counterpart in the reference, whose only denoiser is the CNN above and which ships no weights for it.  The frame itself
+ * carries what a feature-guided filter needs (src/pathtrace.cu:240-254: mean colour, normal, albedo, depth and the sample
+ * variance of each), so pt_filter_* turns a 2 .. 16 spp frame into a usable picture without outside data: an edge-avoiding
+ * a-trous wavelet filter on albedo-demodulated colour, its luminance stop scaled by the pixel's own variance (the spatial
+ * stage of SVGF), its stops on normal, albedo and depth taken from the frame's channels.  TOLERANCED code like fast_math:
+ * DENOISER.md, "Feature-guided filter", states the definition and the measured distance from its float64 restatement
+ * (tests/filter_model.py).  Deterministic: no atomics, two runs give the same bits.
+ *   With EPS = 0.00316f (train.py:48-55), lum(c) = 0.2126 c.x + 0.7152 c.y + 0.0722 c.z and a = EPS + albedo per channel:
+ *   set-up    ill = colour / a;  n = the pixel's count (d_counts) or `samples`;  var = ch10 / n / lum(a)^2 when n >= 2, else
+ *             lum(ill)^2;  dz = 0.5 max(|z[y][x+1] - z[y][x-1]|, |z[y+1][x] - z[y-1][x]|), indices clamped.
+ *   iteration i = 0 .. iterations-1, step s = 2^i:  g = the 3 x 3 (1/4, 1/2, 1/4)^2 blur of var (replicated edges),
+ *             sd = sqrt(max(g, 0)), L = lum(ill); over the 25 taps q = p + s (i, j), i, j in -2 .. 2 that lie inside the frame,
+ *             h = k[i] k[j] with k = (1/16, 1/4, 3/8, 1/4, 1/16), d = s sqrt(i^2 + j^2):
+ *               e = |n_q - n_p|^2 / sigma_n^2 + |alb_q - alb_p|^2 / sigma_a^2
+ *                 + |z_q - z_p| / (sigma_z dz_p d + 1e-3 |z_p| + 1e-20) + |L_q - L_p| / (sigma_l sd_p + 0.01 |L_p| + 1e-4)
+ *               w = h exp(-e);   ill' = sum(w ill_q) / sum(w);   var' = sum(w^2 var_q) / sum(w)^2
+ *   result    ill (EPS + albedo): unclamped radiance.  In place it replaces channels 0-2 and channels 3-13 are not written; out
+ *             of place it goes to d_rgb ([height][width][3]) and the frame is left byte for byte untouched.
+ * Limits: the colour variance skips escaped paths (pathtrace.cu:157-161), so in open scenes channel 10 rests on fewer than n
+ * samples, which the filter ignores; and the variance transfer above is the definition, not an identity, for a coloured albedo.
+ * Workspace: 64 bytes per pixel and frame of a group (pt_filter_workspace_bytes). */
+typedef struct pt_filter_opts {
+  int32_t iterations;  /* 1 .. 8 (default 5): steps 1, 2, 4, ...                          */
+  float sigma_l;       /* luminance stop, in standard deviations (default 4.0)            */
+  float sigma_n;       /* normal stop (default 0.35)                                      */
+  float sigma_a;       /* albedo stop (default 0.1)                                       */
+  float sigma_z;       /* depth stop, in screen-space depth slopes (default 1.0)          */
+  int32_t max_frames;  /* frames per group, >= 1 (default 1)                              */
+  int32_t reserved[2]; /* must be 0                                                       */
+} pt_filter_opts;
+typedef struct pt_filter pt_filter; /* opaque: the options + the workspace of one frame size */
+void pt_filter_opts_default(pt_filter_opts* opts);
+/* opts may be NULL (= defaults).  Every option is validated BEFORE a device is touched: iterations outside 1 .. 8, a sigma that
+ * is not finite and > 0, max_frames < 1 (or beyond the limits of pt_filter_reserve_frames), a non-zero reserved word or a
+ * width / height outside 1 .. 4096 x 4096 pixels (a side at most 16384) is PT_EINVAL naming the argument.  Allocates the workspace on the current device. */
+int pt_filter_create(int width, int height, const pt_filter_opts* opts, pt_filter** out);
+int pt_filter_destroy(pt_filter* f);
+/* Grows the workspace for groups of up to max_frames frames; max_frames <= the current value is a no-op.  Limits: max_frames
+ * <= 65535 and max_frames x width x height <= 2^26 pixels (PT_EINVAL beyond).  It synchronises the device before freeing the
+ * old workspace; on failure (PT_EHIP) the old workspace stays in use. */
+int pt_filter_reserve_frames(pt_filter* f, int max_frames);
+int pt_filter_workspace_bytes(const pt_filter* f, uint64_t* bytes);
+/* Filters the device frame d_frame ([height][width][14]), asynchronous on hip_stream (NULL = default stream).  d_rgb == NULL:
+ * in place; d_rgb != NULL: out of place.  samples >= 1 is the frame's uniform count; with d_counts != NULL (uint32
+ * [height][width], what pt_progressive_counts writes) every pixel uses its own count and samples is ignored.  The iterations
+ * never read the caller's frame (the last one writes it), so in-place use is safe.  One filter's enqueues share its workspace:
+ * do not run two of them concurrently on different streams.  A null filter or frame, or samples < 1 without a count image, is
+ * PT_EINVAL and nothing is launched. */
+int pt_filter_enqueue(pt_filter* f, float* d_frame, float* d_rgb, int samples, const uint32_t* d_counts, void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around the
+ * filter, like pt_denoiser_denoise. */
+int pt_filter_run(pt_filter* f, float* d_frame, float* d_rgb, int samples, const uint32_t* d_counts, float* ms_out);
+/* Batches, with the contract and limits of pt_denoiser_enqueue_frames: bit for bit what
+ *   for k in 0 .. n-1: pt_filter_enqueue(f, d_frames + k * frame_stride, d_rgb ? d_rgb + k * rgb_stride : NULL, samples, NULL, s)
+ * does.  Frames go through in groups of up to max_frames, each group in the launches of ONE frame (1 + iterations).  Strides are
+ * in floats and may leave gaps (frame_stride >= width x height x 14, rgb_stride >= width x height x 3 when d_rgb is given), so
+ * the strided output of pt_renderer_enqueue_frames can be passed straight in.  There is no count image in the batch form.
+ * n_frames < 1, a stride too small, samples < 1, a null filter or null frames is PT_EINVAL naming the argument, and nothing is
+ * launched. */
+int pt_filter_enqueue_frames(pt_filter* f, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                             size_t rgb_stride_floats, int samples, void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = device-event milliseconds around all the groups. */
+int pt_filter_run_frames(pt_filter* f, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                         size_t rgb_stride_floats, int samples, float* ms_out);
+
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
  * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.

@@ -88,6 +88,13 @@ int pt_debug_denoiser_last_enqueue(pt_denoiser* d, int* groups, int* launches);
  * table that pt_debug_denoiser_conv_info reports. */
 int pt_debug_denoiser_conv_plan(pt_denoiser* d, int n_frames, int conv, int info[6]);
 
+/* Feature-guided filter (csrc/pt_filter.hip): the set-up and ONE iteration at `step` (1 .. 4096; the product runs 1, 2, 4, ...
+ * in turn), fused with the re-modulation like a last iteration; arguments as pt_filter_enqueue.  Synchronous. */
+int pt_debug_filter_step(pt_filter* f, float* d_frame, float* d_rgb, int samples, const uint32_t* d_counts, int step);
+/* on != 0: the iterations at steps 1 and 2 read an LDS tile (the workgroup's pixels and a clamped halo) instead of global
+ * memory; the same bits (DENOISER.md, "Speed", has the measurement that decided the product's choice). */
+int pt_debug_filter_tiled(pt_filter* f, int on);
+
 /* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
  * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */
 int pt_debug_progressive_set_samples(pt_progressive* p, int64_t samples);
