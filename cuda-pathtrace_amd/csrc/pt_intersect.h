@@ -286,39 +286,65 @@ __device__ __forceinline__ uint32_t screen_sphere_oc(F3 off, float c, int i, F3 
 // (a ray nearly parallel to a wall; an origin outside a wall; a scene without the structure, whose block makes K infinite), the
 // wave screens the three behind walls into the same ranking -- the two smallest of nine distinct keys do not depend on the order
 // they are ranked in, so that is today's ranking.  Everything after the ranking is unchanged.
+//
+// One pass per axis (EXACTNESS.md A.21).  The two walls of an axis have centres that differ along that axis only, bit for bit
+// (classify_walls refuses every other scene, and a refused scene's certificates are never used: K is infinite).  So the behind
+// wall's off = o - centre agrees with the faced wall's in the other two coordinates, and with it their squares and their
+// products with d: the pass forms the faced wall's nine terms from that wall's own geometry -- right for ANY sphere -- and for
+// the behind wall only the three terms of its own axis.  Each wall's two sums keep the reference's order,
+// (x*x + y*y) + z*z and (d.x*ox + d.y*oy) + d.z*oz (:75-76), on the same operand bits as before.
 __device__ __forceinline__ bool neg_finite(float x) { return __builtin_amdgcn_classf(x, 0x18); }  // -normal or -subnormal
+template <int AX>
+__device__ __forceinline__ F3 with_axis(F3 v, float x) {
+  return mk3(AX == 0 ? x : v.x, AX == 1 ? x : v.y, AX == 2 ? x : v.z);
+}
+// -> the faced wall's key; hb = the behind wall's h = b / 2 (:75), inb = the certificate's class compare on its c (:76)
+template <int AX>
+__device__ __forceinline__ uint32_t screen_wall_pair(const uint4 t, uint32_t m, F3 o, F3 d, const RayConst& rc, uint32_t imask,
+                                                     ScreenState& st, float& hb, bool& inb) {
+  // m: all ones where d[AX] is negative; such a ray faces the wall centred on the plus side (t.y, t.w), any other the one on
+  // the minus side (t.x, t.z)
+  const float4 gf = lds_read_f4(bitop3<0xE4>(t.y, t.x, m)), gb = lds_read_f4(bitop3<0xE4>(t.x, t.y, m));
+  const F3 off = mk3(o.x - gf.x, o.y - gf.y, o.z - gf.z);  // :73
+  const F3 sq = off * off, pr = d * off;
+  const float ob = AX == 0 ? o.x - gb.x : AX == 1 ? o.y - gb.y : o.z - gb.z;
+  const F3 sqb = with_axis<AX>(sq, ob * ob), prb = with_axis<AX>(pr, (AX == 0 ? d.x : AX == 1 ? d.y : d.z) * ob);
+  hb = (prb.x + prb.y) + prb.z;
+  inb = neg_finite(fmaf(gb.w, 5.9837103e-08f, ((sqb.x + sqb.y) + sqb.z) - gb.w));
+  return screen_sphere_oc(off, ((sq.x + sq.y) + sq.z) - gf.w, (int)bitop3<0xE4>(t.w, t.z, m), d, rc, imask, st);
+}
+// Nothing is scheduled across the boundary between two passes (sched_barrier): left alone, the scheduler interleaves the three
+// and the kernel no longer fits its 96 registers (+48 B of scratch, ten reloads per sample: profiles/r07/README.md).  WALLS: the
+// kernel build has a wall block.  In every other build this function is dead code, and a barrier in dead code still changed
+// the instruction streams of the 8-bounce XORWOW builds -- so those builds do not get to see one.
+template <bool WALLS>
 __device__ __forceinline__ void screen_walled(ScreenState& st, const uint4* W, F3 o, F3 d, const RayConst& rc, uint32_t imask,
                                               uint32_t lim_hi_bits) {
   auto umin = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
   auto umax = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
   const float4* Wg = reinterpret_cast<const float4*>(W);
   const uint4 oi = W[3];
-  // per axis: all ones where d[axis] is negative; such a ray faces the wall centred on the plus side (W[4 + k].y, .w), any
-  // other the one on the minus side (.x, .z)
   auto sel = [](uint32_t dbits) { return (uint32_t)((int32_t)dbits >> 31); };
-  auto faced = [&](int k, uint32_t m) {
-    const uint4 t = W[4 + k];
-    return screen_sphere(lds_read_f4(bitop3<0xE4>(t.y, t.x, m)), (int)bitop3<0xE4>(t.w, t.z, m), o, d, rc, imask, st);
-  };
   const uint32_t mx = sel(__float_as_uint(d.x)), my = sel(__float_as_uint(d.y)), mz = sel(__float_as_uint(d.z));
   const uint32_t a0 = screen_sphere(Wg[0], (int)oi.x, o, d, rc, imask, st), a1 = screen_sphere(Wg[1], (int)oi.y, o, d, rc, imask, st),
                  a2 = screen_sphere(Wg[2], (int)oi.z, o, d, rc, imask, st);
   const uint32_t l0 = umin(umin(a0, a1), a2), n0 = umed3(a0, a1, a2);
-  const uint32_t b0 = faced(0, mx), b1 = faced(1, my), b2 = faced(2, mz);
+  float h0, h1, h2;
+  bool in0, in1, in2;
+  if constexpr (WALLS) __builtin_amdgcn_sched_barrier(0);
+  const uint32_t b0 = screen_wall_pair<0>(W[4], mx, o, d, rc, imask, st, h0, in0);
+  if constexpr (WALLS) __builtin_amdgcn_sched_barrier(0);
+  const uint32_t b1 = screen_wall_pair<1>(W[5], my, o, d, rc, imask, st, h1, in1);
+  if constexpr (WALLS) __builtin_amdgcn_sched_barrier(0);
+  const uint32_t b2 = screen_wall_pair<2>(W[6], mz, o, d, rc, imask, st, h2, in2);
+  if constexpr (WALLS) __builtin_amdgcn_sched_barrier(0);
   const uint32_t l1 = umin(umin(b0, b1), b2), n1 = umed3(b0, b1, b2);
   st.k1 = umin(l0, l1);
   st.k2 = umin(umin(umax(l0, l1), n0), n1);
   // the certificates of the three behind walls
   const float K = __uint_as_float(st.k1 & ~imask) * __uint_as_float(oi.w);
-  auto certified = [&](int k, uint32_t m) {
-    const uint4 t = W[4 + k];
-    const float4 g = lds_read_f4(bitop3<0xE4>(t.x, t.y, m));
-    const F3 off = mk3(o.x - g.x, o.y - g.y, o.z - g.z);  // :73
-    const float h = dot(d, off);                          // b / 2 (:75)
-    const float c = dot(off, off) - g.w;                  // :76
-    return neg_finite(fmaf(2.0f, h, K)) & neg_finite(fmaf(g.w, 5.9837103e-08f, c));
-  };
-  const bool cert = (st.k1 < lim_hi_bits) & certified(0, mx) & certified(1, my) & certified(2, mz);
+  const bool cert = (st.k1 < lim_hi_bits) & (neg_finite(fmaf(2.0f, h0, K)) & in0) & (neg_finite(fmaf(2.0f, h1, K)) & in1) &
+                    (neg_finite(fmaf(2.0f, h2, K)) & in2);
   if (__builtin_expect(__builtin_amdgcn_ballot_w64(!cert) != 0, 0)) {
     auto behind = [&](int k, uint32_t m) {
       const uint4 t = W[4 + k];
@@ -337,7 +363,7 @@ __device__ unsigned long long g_screen_stats[8];
 // LAST: the caller uses only the hit/miss decision and the index (the last bounce of a path of known length: emission of the
 // sphere hit, nothing else -- t, the hit point and the next ray are dead).  The winner's FP64 exact step is then replaced by
 // its float part and two certainty tests, see below.
-template <bool NB, bool PRIMARY = false, bool LAST = false>
+template <bool NB, bool PRIMARY = false, bool LAST = false, bool WALLS = false>
 __device__ __forceinline__ bool intersect_scene_screened_keys(const SceneLds& sc, int n, F3 o, F3 d, const RayConst& rc,
                                                               float& t_hit, int& idx) {
   if (n <= 0) return false;
@@ -377,7 +403,7 @@ __device__ __forceinline__ bool intersect_scene_screened_keys(const SceneLds& sc
 #if PT_UNROLL_NINE
   if constexpr (!PRIMARY) {
     if (sc.walls && n == 9) {  // builds with a wall block (stage_walls): rank six spheres, certify three
-      screen_walled(st, sc.walls, o, d, rc, imask, lim_hi_bits);
+      screen_walled<WALLS>(st, sc.walls, o, d, rc, imask, lim_hi_bits);
       i = 9;
     }
   }
@@ -599,7 +625,7 @@ __device__ __forceinline__ bool intersect_scene_screened_large(const SceneLds& s
   return hit;
 }
 
-template <int LEVEL, bool PRIMARY = false, bool LAST = false>
+template <int LEVEL, bool PRIMARY = false, bool LAST = false, bool WALLS = false>  // WALLS: the build stages a wall block (stage_walls)
 __device__ __forceinline__ bool intersect_scene(const SceneLds& sc, int n, F3 o, F3 d, float& t_hit, int& idx) {
   // every ray but the primary one has a unit direction: its constants come from the workgroup's table (any other a: general
   // routine).  Not in the lean layouts: their kernels mix depths in a wave (path regeneration), so both routines would run.
@@ -609,7 +635,7 @@ __device__ __forceinline__ bool intersect_scene(const SceneLds& sc, int n, F3 o,
     // wall spheres hits all six).  In a many-sphere scene almost every test fails `det >= 0` for
     // the whole wave and the literal loop skips its FP64 part with one wave-uniform branch.
     if (!sc.lean && (sc.small_only || n <= PT_SCREEN_MAX_SPHERES))
-      return intersect_scene_screened_keys<(LEVEL >= 6), (PRIMARY && LEVEL >= 6), (LAST && LEVEL >= 6)>(sc, n, o, d, rc, t_hit, idx);
+      return intersect_scene_screened_keys<(LEVEL >= 6), (PRIMARY && LEVEL >= 6), (LAST && LEVEL >= 6), WALLS>(sc, n, o, d, rc, t_hit, idx);
     if constexpr (LEVEL >= 6) return intersect_scene_screened_large(sc, n, o, d, rc, t_hit, idx);
     return intersect_scene_loop<1>(sc, n, o, d, rc, t_hit, idx);
   }

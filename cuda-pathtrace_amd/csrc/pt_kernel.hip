@@ -233,7 +233,8 @@ pixel_kernel(typename KernelArgsOf<FRAMES, RESUME, ADAPTIVE>::type args) {  // (
   sc.small_only = !LEAN && K.lean == PT_LEAN_BIG;
   // the 5-bounce reference-configuration builds of variant 6 screen secondary rays against the faced wall of each axis only
   // (pt_walls.h; the 8-bounce interactive build keeps the nine-sphere screen: DESIGN.md section 8)
-  if constexpr (K.lds_extra == PT_LDS_WALLS && REFB == 5 && !LEAN) stage_walls(sc, a.spheres, a.n_spheres);
+  constexpr bool kWalls = K.lds_extra == PT_LDS_WALLS && REFB == 5 && !LEAN;
+  if constexpr (kWalls) stage_walls(sc, a.spheres, a.n_spheres);
   constexpr bool kRegen = K.loop == PT_LOOP_REGEN, kDecoupled = K.loop == PT_LOOP_DECOUPLED;
   GridLds grid;
   if constexpr (K.grid != PT_GRID_NONE) {  // the frame's grid, built by build_grid_kernel just before this launch
@@ -592,7 +593,7 @@ frame_top:
       rng.begin_sample((uint32_t)i);
       F3 dir;
       primary_ray(rng, dir);
-      trace_ray<RNG, K.tracer, REFB>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);  // :231
+      trace_ray<RNG, K.tracer, REFB, kWalls>(L, sc, a.n_spheres, eye, dir, rng, var, a.max_bounces);  // :231
     }
     if (by_progress) __builtin_amdgcn_s_setprio(0);
   }

@@ -86,7 +86,7 @@ __device__ __forceinline__ bool bounce_shade(TraceOutput& L, const SceneLds& sc,
 // the t handed to bounce_shade are dead, and the nearest-hit search may return any t (intersect_scene_screened_keys)
 // `live` (variant 13's regeneration loop only): false for a lane whose pixel is finished -- it goes through the nearest-hit search
 // as a helper of the wave's pooled tests and changes nothing of its own
-template <int RNG, int LEVEL, bool PRIMARY = false, bool LAST = false>
+template <int RNG, int LEVEL, bool PRIMARY = false, bool LAST = false, bool WALLS = false>
 __device__ __forceinline__ bool bounce_once(TraceOutput& L, const SceneLds& sc, int nsph, F3& o, F3& d, F3& color, F3& mask,
                                             Rng<RNG>& rng, Welford (&var)[4], int n, bool live = true, bool prim = false,
                                             bool dead_end = false) {
@@ -98,7 +98,7 @@ __device__ __forceinline__ bool bounce_once(TraceOutput& L, const SceneLds& sc, 
   else if constexpr (LEVEL == 13)
     hit = intersect_scene_v13(sc, nsph, o, d, t, idx, live, prim, dead_end);  // prim: a primary ray of a pixel with a list (pt_primlist.h)
   else
-    hit = intersect_scene<LEVEL, PRIMARY, LAST>(sc, nsph, o, d, t, idx);
+    hit = intersect_scene<LEVEL, PRIMARY, LAST, WALLS>(sc, nsph, o, d, t, idx);
   if (LEVEL == 13 && !live) return true;
   return bounce_shade<RNG, LEVEL>(L, sc, o, d, color, mask, rng, var, n, hit, t, idx, dead_end);
 }
@@ -107,7 +107,7 @@ __device__ __forceinline__ bool bounce_once(TraceOutput& L, const SceneLds& sc, 
 // UNROLL_MB: a bounce count known at compile time (the kernel builds for one scene size and bounce cap, pt_kernel.hip: the
 // reference's MAX_BOUNCES 5, and the 8 of the interactive configuration) for which the path is emitted straight-line; the
 // generic builds (0) unroll the reference's five only.
-template <int RNG, int LEVEL, int UNROLL_MB = 0>
+template <int RNG, int LEVEL, int UNROLL_MB = 0, bool WALLS = false>  // WALLS: the kernel build stages a wall block (stage_walls)
 __device__ __forceinline__ void trace_ray(TraceOutput& L, const SceneLds& sc, int nsph, F3 o, F3 d, Rng<RNG>& rng,
                                           Welford (&var)[4], int max_bounces) {
   F3 color = mk3(0.0f, 0.0f, 0.0f);
@@ -118,13 +118,13 @@ __device__ __forceinline__ void trace_ray(TraceOutput& L, const SceneLds& sc, in
     if (!bounce_once<RNG, LEVEL, true>(L, sc, nsph, o, d, color, mask, rng, var, 0)) return;  // trace_ray starts at the eye
 #pragma unroll
     for (int n = 1; n < kMB - 1; n++)
-      if (!bounce_once<RNG, LEVEL>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
-    if (!bounce_once<RNG, LEVEL, false, true>(L, sc, nsph, o, d, color, mask, rng, var, kMB - 1)) return;  // the last: colour only
+      if (!bounce_once<RNG, LEVEL, false, false, WALLS>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
+    if (!bounce_once<RNG, LEVEL, false, true, WALLS>(L, sc, nsph, o, d, color, mask, rng, var, kMB - 1)) return;  // the last: colour only
   } else
 #endif
   {
     for (int n = 0; n < max_bounces; n++)
-      if (!bounce_once<RNG, LEVEL>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
+      if (!bounce_once<RNG, LEVEL, false, false, WALLS>(L, sc, nsph, o, d, color, mask, rng, var, n)) return;
   }
   L.color = L.color + color;                    // :198
   if (LEVEL >= 6 && !sc.lean) welford_update(var[0], luminance(color), sc.rcpn); else welford_update(var[0], luminance(color));  // :200

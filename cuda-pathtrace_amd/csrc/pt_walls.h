@@ -6,6 +6,8 @@
 // The secondary-bounce screen (intersect_scene_screened_keys, EXACTNESS.md A.18) ranks the faced wall of each axis and certifies
 // the other one instead of screening it.  The certificate is sound for ANY sphere, so this classification only decides how often
 // it passes: a scene without the structure gets a layout that never certifies (ok = false) and every sphere is screened.
+// The screen also takes the behind wall's two off-axis offsets from the faced wall of the pair (screen_walled, EXACTNESS.md
+// A.21), so "the structure" includes that the two centres of a pair carry the same bits off their axis.
 #pragma once
 #include <math.h>
 #include "../../include/ptcore.h"
@@ -79,6 +81,11 @@ __host__ __device__ inline WallLayout classify_walls(const pt_sphere* s, int n) 
     // the two walls' insides overlap along the axis: the plus wall's near surface lies below the minus wall's
     const pt_sphere &a = s[pl[k]], &b = s[mi[k]];
     if (!((double)a.pos[k] - (double)a.radius < (double)b.pos[k] + (double)b.radius)) return none;
+    // the two centres differ along their axis ONLY: the screen forms o - centre, its square and its product with d for the
+    // other two coordinates once per pair (screen_walled, EXACTNESS.md A.21), which is the same float only for the same BITS
+    // (+0 and -0 are equal values and give o - c different signs of zero)
+    for (int j = 0; j < 3; j++)
+      if (j != k && __builtin_bit_cast(unsigned, a.pos[j]) != __builtin_bit_cast(unsigned, b.pos[j])) return none;
   }
   for (int k = 0; k < 3; k++) {
     w.obj[k] = objs[k];
