@@ -188,6 +188,7 @@ LAB_ABI = {
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "pt_debug_policy_ms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pt_debug_policy_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "pt_debug_renderer_batch_launches": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "pt_debug_denoiser_layer_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                     ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_activation": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t]),
@@ -521,6 +522,12 @@ class Renderer:
     def set_rng_state(self, st):
         st = np.ascontiguousarray(st, dtype=np.uint32)
         check(lib.pt_renderer_set_rng_state(self.handle, st.ctypes.data, st.size))
+
+    def batch_launches(self):  # lab library only (pt_debug_renderer_batch_launches)
+        """Launches of the frames kernel that enqueue_frames has made on this renderer (single enqueues do not count)."""
+        n = ctypes.c_uint32(0)
+        check(lib.pt_debug_renderer_batch_launches(self.handle, ctypes.byref(n)))
+        return n.value
 
     def kernel_info(self, n_spheres):
         ki = KernelInfo()

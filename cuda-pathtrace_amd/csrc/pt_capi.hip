@@ -68,6 +68,7 @@ struct pt_renderer {
   hipEvent_t ev_err = nullptr;
   bool err_pending = false;       // a chunked launch's error word is on its way to h_err
   uint32_t debug = 0;             // PT_DEBUG_* (lab library only, env PT_LAB_DEBUG)
+  uint32_t batch_launches = 0;    // successful pt_launch_frames_kernel calls (the lab library reports it: pt_debug_renderer_batch_launches)
   // The renderer owns single-instance device scratch (generator state, d_accel, d_fail): launches of one
   // renderer must execute in submission order even when the caller alternates streams.
   hipEvent_t ev_last = nullptr;   // recorded after every launch on the stream it went to
@@ -591,6 +592,9 @@ int pt_renderer_enqueue(pt_renderer* r, float* d_out, const pt_sphere* d_spheres
 // A batch of frames with known cameras (include/ptcore.h).  Where a frames kernel exists -- the reference's scene in the
 // reference configuration, i.e. the interactive shape -- the batch goes out as launches of up to PT_FRAMES_MAX frames each;
 // everywhere else, and whenever two frames would share a buffer, it is the loop of single-frame enqueues it stands for.
+// So is the batch of an XORWOW renderer that does not persist its state: each of its single frames starts from the seeded
+// stream (pixel_kernel, xorwow_init), while the frames kernel seeds once and keeps the generator in registers across its frames.
+// (The counter-based generator's key depends only on the frame counter: batched with or without persist_rng.)
 int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_t out_stride_floats, float* d_vertices,
                                size_t vtx_stride_floats, const pt_sphere* d_spheres, int n_spheres, const float* bases,
                                const float* eyes, void* hip_stream) {
@@ -602,6 +606,7 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
   const int variant = effective_variant(r, n_spheres);
   const bool batched = n_frames >= 2 && r->tile_pixels > 0 && variant != PT_VARIANT_FAST &&
                        pt_kernel_has_frames(variant, n_spheres, r->opts.max_bounces, r->opts.layout == PT_LAYOUT_PLANAR) &&
+                       (r->opts.rng_mode != PT_RNG_XORWOW || r->d_state != nullptr) &&
                        out_stride_floats >= tile_floats && (d_vertices ? vtx_stride_floats >= vtx_floats : saved_vertices == nullptr);
   int rc = PT_OK;
   for (int f0 = 0; f0 < n_frames && rc == PT_OK;) {
@@ -633,6 +638,7 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
     {
       const hipError_t e = pt_launch_frames_kernel(fa, r->opts.rng_mode, variant, (hipStream_t)hip_stream);
       if (e != hipSuccess) { rc = pt_fail(PT_EHIP, "pt_renderer_enqueue_frames: %s", hipGetErrorString(e)); break; }
+      r->batch_launches++;
     }
     rc = mark_last(r, (hipStream_t)hip_stream);
     r->frame += (uint32_t)m;
@@ -641,6 +647,15 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
   r->d_vertices = saved_vertices;
   return rc;
 }
+
+#if PT_BUILD_EXPERIMENTS
+// lab library: how many launches of the frames kernel this renderer has made (include/ptcore_lab.h)
+int pt_debug_renderer_batch_launches(pt_renderer* r, uint32_t* launches) {
+  if (!r || !launches) return pt_fail(PT_EINVAL, "pt_debug_renderer_batch_launches: NULL argument");
+  *launches = r->batch_launches;
+  return PT_OK;
+}
+#endif
 
 int pt_renderer_render(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, int n_spheres, const float basis[12],
                        const float eye[3], float* ms_out) {

@@ -168,7 +168,9 @@ int pt_renderer_enqueue(pt_renderer* r, float* d_out, const pt_sphere* d_spheres
  * 8 bounces, interleaved layout: the interactive shape, whose single frame is one round of waves -- all ramp and tail) the frames
  * go out as ONE launch per 32: a workgroup keeps its pixels for the whole batch and loops over the frames, the generator staying
  * in its registers from frame to frame (the counter-based one is re-keyed per frame) -- no state traffic, one ramp and one tail
- * per batch.  Elsewhere it IS the loop of single enqueues.
+ * per batch.  Elsewhere it IS the loop of single enqueues -- also for an XORWOW renderer created with persist_rng = 0, whose
+ * every frame starts from the seeded stream (a generator kept in registers would carry on instead); the counter-based
+ * generator is keyed by the frame counter alone and is batched with or without persist_rng.
  * d_vertices != NULL: frame f also writes its display vertices to d_vertices + f * vtx_stride_floats (pt_renderer_set_display
  * for the batch).  Frames that would share a buffer (out_stride_floats below one tile, a set_display buffer without
  * d_vertices) are rendered one by one.  bases / eyes are host arrays, read before the call returns. */

@@ -59,6 +59,10 @@ int pt_debug_grid_image(const pt_sphere* d_spheres, int n_spheres, const float* 
 int pt_debug_policy_ms(int rng_mode, int variant, double waves_per_simd, int spp, int bounces, double* ms);
 /* the variant the library's own cost-model policy picks (6, 8 or 9) for a tile of `waves_per_simd` one-lane waves per SIMD */
 int pt_debug_policy_choice(int rng_mode, double waves_per_simd, int spp, int bounces, int with9, int chunked, int* variant);
+/* *launches = the launches of the frames kernel (one per group of up to 32 frames) that pt_renderer_enqueue_frames has made on
+ * this renderer since it was created; frames that went out as single enqueues do not count.  The tests of the batch kernel
+ * use it to see that the kernel they check is the one that ran. */
+int pt_debug_renderer_batch_launches(pt_renderer* r, uint32_t* launches);
 
 /* Denoiser diagnostics (csrc/pt_denoise.hip).  Layers = the activation buffers of the workspace, in execution order:
  * 0 "input" (the pre-processed frame, NHWC, 16 channels of which 14-15 are zero), "block<b>.t1" / ".res" / ".out", "lat6",

@@ -188,7 +188,8 @@ def test_straight_from_the_renderer(pt, gpu, sd, single_dn):
     bases, eyes = poses(pt, n, w, h)
     scene = pt.scene_cornell()
     d_scene, ns = pt.upload_scene(scene)
-    r = pt.Renderer(w, h, spp)
+    r = pt.Renderer(w, h, spp, variant=6)  # (the variant with a frames kernel, whatever the policy would pick)
+    assert r.kernel_info(9)["variant"] == 6
     r1 = pt.Renderer(w, h, spp)
     d = pt.DeviceBuffer(n * fs * 4)
     one = pt.DeviceBuffer(px * 56)

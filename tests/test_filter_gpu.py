@@ -204,7 +204,8 @@ def test_straight_from_the_renderer(pt, gpu):
         bases.append(pt.camera_basis(eye, yaw=-90.0 + 0.9 * k, pitch=-0.4 * k, width=w, height=h))
         eyes.append(eye)
     stride = w * h * 14 + 64
-    r = pt.Renderer(w, h, spp)
+    r = pt.Renderer(w, h, spp, variant=6)  # (the variant with a frames kernel: the policy gives so small a tile to variant 8)
+    assert r.kernel_info(9)["variant"] == 6
     ff = pt.FeatureFilter(w, h, max_frames=2)
     d_scene, ns = pt.upload_scene(pt.scene_cornell())
     d_out, d_rgb = pt.DeviceBuffer(n * stride * 4), pt.DeviceBuffer(n * w * h * 12)
