@@ -164,6 +164,16 @@ ABI = {
     "pt_filter_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _fp]),
     "pt_filter_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
     "pt_filter_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _fp]),
+    "pt_temporal_opts_default": (None, [_vp]),
+    "pt_temporal_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "pt_temporal_destroy": (ctypes.c_int, [_vp]),
+    "pt_temporal_reset": (ctypes.c_int, [_vp]),
+    "pt_temporal_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_temporal_camera": (ctypes.c_int, [_fp, _fp]),
+    "pt_temporal_enqueue": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _vp]),
+    "pt_temporal_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _fp]),
+    "pt_temporal_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _vp]),
+    "pt_temporal_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _fp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -1067,3 +1077,107 @@ def filter_frames(frames, samples, out_of_place=False, filt=None, **opts):
             d_rgb.free()
         if filt is None:
             ff.destroy()
+
+
+class TemporalOpts(ctypes.Structure):
+    """pt_temporal_opts (include/ptcore.h)."""
+    _fields_ = [("history_cap", ctypes.c_float), ("depth_tol", ctypes.c_float), ("normal_tol", ctypes.c_float),
+                ("albedo_tol", ctypes.c_float), ("min_weight", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+def temporal_camera(basis):
+    """pt_temporal_camera: the float32 inverse [3][3] of [B0 | B1-B0 | B2-B0] that carries a world offset from the eye to
+    t (1, sy, v); host only.  Raises PtError for a degenerate or non-parallelogram basis."""
+    _, b = _f32(basis, 12)
+    out = np.zeros(9, dtype=np.float32)
+    check(lib.pt_temporal_camera(b, out.ctypes.data_as(_fp)))
+    return out.reshape(3, 3)
+
+
+class Temporal:
+    """ctypes view of pt_temporal: the temporal accumulator for width x height frames (DENOISER.md, "Temporal accumulation").
+    Every call works in place on a device [H][W][14] frame of `samples` samples per pixel rendered with (basis, eye): channels
+    0-2 and 10 become those of all the samples accumulated at the pixel's world position; d_counts, a device uint32 [H][W]
+    image, receives the accumulated counts (FeatureFilter's d_counts)."""
+
+    def __init__(self, width, height, history_cap=256.0, depth_tol=0.02, normal_tol=0.9, albedo_tol=0.01, min_weight=0.25):
+        self.handle = None
+        opts = TemporalOpts(history_cap=history_cap, depth_tol=depth_tol, normal_tol=normal_tol, albedo_tol=albedo_tol, min_weight=min_weight)
+        h = _vp()
+        check(lib.pt_temporal_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height = width, height
+
+    def memory(self):
+        """{"workspace": bytes of the two history images, "per_pixel": bytes per pixel}."""
+        b = ctypes.c_uint64(0)
+        check(lib.pt_temporal_workspace_bytes(self.handle, ctypes.byref(b)))
+        return {"workspace": int(b.value), "per_pixel": int(b.value) // (self.width * self.height)}
+
+    def reset(self):
+        """Forget the history: the next frame passes through."""
+        check(lib.pt_temporal_reset(self.handle))
+
+    def enqueue(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None, stream=None):
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        check(lib.pt_temporal_enqueue(self.handle, d_frame, samples, b, e, d_counts, stream))
+
+    def run(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None):
+        """Synchronous; returns device-event milliseconds."""
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        ms = ctypes.c_float(0)
+        check(lib.pt_temporal_run(self.handle, d_frame, samples, b, e, d_counts, ctypes.byref(ms)))
+        return ms.value
+
+    def _cameras(self, bases, eyes, frame_stride_floats):
+        bases = np.ascontiguousarray(bases, dtype=np.float32).reshape(-1, 12)
+        eyes = np.ascontiguousarray(eyes, dtype=np.float32).reshape(-1, 3)
+        assert len(bases) == len(eyes)
+        fs = self.width * self.height * CHANNELS if frame_stride_floats is None else frame_stride_floats
+        return bases, eyes, fs
+
+    def enqueue_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None, stream=None):
+        """Asynchronous; the n = len(bases) frames at d_frames + k * frame_stride_floats (default: packed) in order, bit for
+        bit n single enqueues; d_counts receives the last frame's counts."""
+        bases, eyes, fs = self._cameras(bases, eyes, frame_stride_floats)
+        check(lib.pt_temporal_enqueue_frames(self.handle, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
+                                             samples, d_counts, stream))
+
+    def run_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None):
+        """Synchronous enqueue_frames; returns device-event milliseconds."""
+        bases, eyes, fs = self._cameras(bases, eyes, frame_stride_floats)
+        ms = ctypes.c_float(0)
+        check(lib.pt_temporal_run_frames(self.handle, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
+                                         samples, d_counts, ctypes.byref(ms)))
+        return ms.value
+
+    def destroy(self):
+        if self.handle:
+            check(lib.pt_temporal_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def accumulate_frames(frames, samples, bases, eyes, temporal=None, **opts):
+    """Convenience for tests, like filter_frames: host frames [N][H][W][14] of one fly-through through ONE
+    pt_temporal_run_frames call of a fresh session (or `temporal`, whose history then goes in).  Returns (the frames after the
+    stage, the uint32 [H][W] counts of the last frame).  opts: of the Temporal made here."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    n, h, w = frames.shape[:3]
+    ta = temporal or Temporal(w, h, **opts)
+    d_frames, d_counts = DeviceBuffer(frames.nbytes).upload(frames), DeviceBuffer(h * w * 4)
+    try:
+        ta.run_frames(d_frames.ptr, samples, bases, eyes, d_counts=d_counts.ptr)
+        return d_frames.download(np.float32, frames.shape), d_counts.download(np.uint32, (h, w))
+    finally:
+        d_frames.free()
+        d_counts.free()
+        if temporal is None:
+            ta.destroy()

@@ -16,7 +16,9 @@
 // (the still frame refined in N passes of -s samples each into one buffer: ProgressiveRenderer / pt_progressive_*; the
 // saved frame is bit for bit the one -s N*S writes, the one-pass variant of the interactive loop with the camera at rest),
 // --filter (the weights-free denoiser, FeatureFilter / pt_filter_*: every frame of the headless loop and every progressive pass
-// is filtered in place after Render(), where -d would run the network; the saved EXR and bitmaps hold the filtered frame).
+// is filtered in place after Render(), where -d would run the network; the saved EXR and bitmaps hold the filtered frame),
+// --temporal (with --frames / --poses: TemporalAccumulator / pt_temporal_* accumulates every frame of the headless loop in place
+// after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +40,7 @@
 #include "ProgressiveRenderer.h"
 #include "Renderer.h"
 #include "Scene.h"
+#include "TemporalAccumulator.h"
 
 static void usage() {
   std::cout << "cuda-pathtrace" << std::endl
@@ -74,6 +77,8 @@ static void usage() {
                "  --filter                      denoise without weights: variance-guided a-trous filter on every frame\n"
                "  --filter-iterations arg       with --filter: a-trous iterations 1..8 (default 5)\n"
                "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
+               "  --temporal                    with --frames / --poses: reproject and accumulate every frame over the last ones\n"
+               "  --temporal-cap arg            with --temporal: cap of the accumulated history in samples, >= 1 (default 256)\n"
             << std::endl;
 }
 
@@ -104,6 +109,9 @@ int main(int argc, const char** argv) {
   bool filtering = false, filterIterationsGiven = false, filterSigmaGiven = false;
   int filterIterations = 5;
   std::string filterSigma;
+  // --temporal: the temporal accumulator (pt_temporal_*) in place after every Render() of the frame loop
+  bool temporal = false, temporalCapGiven = false;
+  double temporalCap = 256.0;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -142,6 +150,8 @@ int main(int argc, const char** argv) {
     else if (a == "--filter") filtering = true;
     else if (a == "--filter-iterations") { filterIterations = atoi(value("--filter-iterations")); filterIterationsGiven = true; }
     else if (a == "--filter-sigma") { filterSigma = value("--filter-sigma"); filterSigmaGiven = true; }
+    else if (a == "--temporal") temporal = true;
+    else if (a == "--temporal-cap") { temporalCap = atof(value("--temporal-cap")); temporalCapGiven = true; }
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -232,6 +242,31 @@ int main(int argc, const char** argv) {
       filterOpts.sigma_l = v[0], filterOpts.sigma_n = v[1], filterOpts.sigma_a = v[2], filterOpts.sigma_z = v[3];
     }
   }
+  pt_temporal_opts temporalOpts;
+  pt_temporal_opts_default(&temporalOpts);
+  if (temporalCapGiven && !temporal) {  // (before any device is touched)
+    std::cerr << "ERROR: --temporal-cap needs --temporal: it caps the accumulator's history" << std::endl;
+    return 1;
+  }
+  if (temporal) {
+    if (progressiveGiven) {
+      std::cerr << "ERROR: --temporal cannot be combined with --progressive: a still frame has the progressive session" << std::endl;
+      return 1;
+    }
+    if (batch) {
+      std::cerr << "ERROR: --temporal cannot be combined with --batch: the accumulator runs after every frame of the loop" << std::endl;
+      return 1;
+    }
+    if (!framesGiven && posesFile.empty()) {
+      std::cerr << "ERROR: --temporal needs --frames or --poses: it accumulates the frames of the headless loop" << std::endl;
+      return 1;
+    }
+    if (temporalCapGiven && (!(temporalCap >= 1.0) || !(temporalCap <= 3.4028234663852886e38))) {
+      std::cerr << "ERROR: --temporal-cap " << temporalCap << ": a finite number of samples >= 1" << std::endl;
+      return 1;
+    }
+    temporalOpts.history_cap = (float)temporalCap;
+  }
   if ((adaptiveGiven || adaptiveMinGiven || adaptiveRadiusGiven) && !progressiveGiven) {  // (before any device is touched)
     std::cerr << "ERROR: " << (adaptiveGiven ? "--adaptive" : adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius")
               << " needs --progressive: adaptive sampling refines a progressive session" << std::endl;
@@ -311,11 +346,16 @@ int main(int argc, const char** argv) {
       denoising ? new DenoiseNet(width, height, denoiseWeights, 1, denoisePrecision == "half" ? PT_DENOISE_F16 : PT_DENOISE_F32) : NULL;
   // --filter: likewise on the first device, after the gather
   FeatureFilter* filter = filtering ? new FeatureFilter(width, height, filterOpts) : NULL;
-  float denoiseTime = 0.0f, filterTime = 0.0f;
+  // --temporal: likewise; with --filter its per-pixel counts replace the filter's uniform count
+  TemporalAccumulator* accumulator = temporal ? new TemporalAccumulator(width, height, temporalOpts) : NULL;
+  unsigned int* d_temporalCounts = NULL;
+  if (accumulator && filter) gpuErrchk(pt_malloc((void**)&d_temporalCounts, (size_t)width * height * sizeof(unsigned int)));
+  float denoiseTime = 0.0f, filterTime = 0.0f, temporalTime = 0.0f;
   auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
+    if (accumulator) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, d_temporalCounts);
     if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
-    if (filter) filterTime = filter->Filter(b, samplesPerPixel);
+    if (filter) filterTime = filter->Filter(b, samplesPerPixel, d_temporalCounts);
     return ms;
   };
   Camera camera(glm::vec3(cameraPos[0], cameraPos[1], cameraPos[2]), cameraView[0], cameraView[1]);  // main.cu:128 verbatim
@@ -416,6 +456,7 @@ int main(int argc, const char** argv) {
     for (int f = 0; f < frames; f++) renderTime = render(d_buffer, scene, camera);
   }
   std::cout << "Render completed in " << renderTime << "ms (" << 1000.0f / renderTime << " fps)" << std::endl;
+  if (accumulator) std::cout << "Temporal accumulation completed in " << temporalTime << "ms" << std::endl;
   if (net) std::cout << "Denoise completed in " << denoiseTime << "ms" << std::endl;
   if (filter) std::cout << "Filter completed in " << filterTime << "ms" << std::endl;
   if (tiled) {
@@ -456,6 +497,8 @@ int main(int argc, const char** argv) {
   buffer.FreeCPU();
   delete net;
   delete filter;
+  delete accumulator;
+  if (d_temporalCounts) (void)pt_free(d_temporalCounts);
   delete single;
   delete tiled;
   if (batch_frames) (void)pt_free(batch_frames);  // (d_buffer points into it)

@@ -418,6 +418,70 @@ int pt_filter_enqueue_frames(pt_filter* f, int n_frames, float* d_frames, size_t
 int pt_filter_run_frames(pt_filter* f, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
                          size_t rgb_stride_floats, int samples, float* ms_out);
 
+/* ---- temporal accumulation: reproject and blend the frames of a fly-through ------------------ */
+/* The temporal stage of SVGF in front of the filter above; no counterpart in the reference.  A session belongs to one frame
+ * size and carries, from call to call, what the earlier frames accumulated: two history images used ping-pong, each three
+ * float4 per pixel {colour, s2}, {normal, z}, {albedo, count} (96 bytes of workspace per pixel, pt_temporal_workspace_bytes), and
+ * the previous call's camera.  A call works IN PLACE on a device frame [height][width][14] of uniform sample count n: it
+ * rewrites channels 0-2 (colour) and 10 (the colour's per-sample variance) and leaves channels 3-9 and 11-13 untouched byte for
+ * byte; the optional count image (uint32 [height][width]) receives every pixel's accumulated count and goes straight into
+ * pt_filter_enqueue.  EXACT code: DENOISER.md, "Temporal accumulation", states the definition operation by operation and the
+ * kernel equals its float32 restatement (tests/temporal_model.py) bit for bit.  Deterministic: two runs give the same bits.
+ *   host      P = inverse of M = [B0 | B1-B0 | B2-B0] (columns, B0..B3 the corners of basis), by cofactors in double, rounded
+ *             to float (pt_temporal_camera).  A primary direction is d = M (1, sy, v)^T, so P (X - eye) = t (1, sy, v)^T.
+ *   pixel     (row r, column c) with depth z = ch9:  X = eye + d z for the unjittered d of the pixel (sy = c / height, v = 1 -
+ *             r / width);  (alpha, beta, gamma) = P' (X - eye') with the PREVIOUS camera;  cc = (beta / alpha) height, rr = (1 -
+ *             gamma / alpha) width;  the four bilinear taps around (rr, cc) of the history, a tap valid when it lies inside the
+ *             frame, holds a count > 0 and |z' - alpha| <= depth_tol alpha, n' . n >= normal_tol, |alb' - alb|^2 <= albedo_tol;
+ *             with Ws = the valid taps' weight >= min_weight the history is (hC, hs2, hN) = the taps' weighted means, hN capped
+ *             at history_cap; otherwise, and where z <= 0 or alpha <= 0 or (rr, cc) is outside, the pixel restarts (hN = 0).
+ *   blend     tot = hN + n;  colour = hC + (n / tot) (C - hC);  ch10 = the exact two-group merge of the sample variances:
+ *             (hs2 max(hN - 1, 0) + ch10 (n - 1) + (lum(C) - lum(hC))^2 hN n / tot) / (tot - 1);  count = floor(tot + 0.5).
+ * The first call of a session and the first after pt_temporal_reset pass the frame through (its own bits, count n).
+ * Limits: silhouette pixels carry mixed depths and normals and mostly restart; sky pixels (z <= 0) never accumulate; the scene
+ * must not change between calls without a reset.  One session's calls share its workspace and are ordered by the stream: do
+ * not run two of them concurrently on different streams. */
+typedef struct pt_temporal_opts {
+  float history_cap;  /* the accumulated count never exceeds this many samples, >= 1 (default 256)            */
+  float depth_tol;    /* relative depth stop, finite and > 0 (default 0.02)                                   */
+  float normal_tol;   /* smallest n' . n of a valid tap, -1 .. 1 (default 0.9)                                */
+  float albedo_tol;   /* largest squared albedo distance of a valid tap, finite and > 0 (default 0.01)        */
+  float min_weight;   /* smallest bilinear weight of the valid taps that keeps the history, (0, 1] (default 0.25) */
+  int32_t reserved;   /* must be 0                                                                            */
+} pt_temporal_opts;
+typedef struct pt_temporal pt_temporal; /* opaque: the options, the history and the previous camera of one frame size */
+void pt_temporal_opts_default(pt_temporal_opts* opts);
+/* opts may be NULL (= defaults).  Every option and size is validated BEFORE a device is touched (the size limits are
+ * pt_filter_create's); a bad value is PT_EINVAL naming the argument.  Allocates the workspace on the current device. */
+int pt_temporal_create(int width, int height, const pt_temporal_opts* opts, pt_temporal** out);
+int pt_temporal_destroy(pt_temporal* t);
+/* Forgets the history: the next frame passes through.  Call it when the scene changes. */
+int pt_temporal_reset(pt_temporal* t);
+int pt_temporal_workspace_bytes(const pt_temporal* t, uint64_t* bytes);
+/* The host step alone (no device): P_out = the row-major inverse above.  PT_EINVAL for a determinant that is zero or not
+ * finite, and for a basis whose B1 + B2 - B0 - B3 exceeds 1e-3 |B0| in any component (the mapping assumes the parallelogram
+ * that pt_camera_basis produces). */
+int pt_temporal_camera(const float basis[12], float P_out[9]);
+/* Accumulates the device frame d_frame of `samples` >= 1 samples per pixel, rendered with (basis, eye), asynchronous on
+ * hip_stream (NULL = default stream).  d_counts may be NULL.  A null accumulator, frame, basis or eye, samples < 1, a basis
+ * pt_temporal_camera refuses or a non-finite eye is PT_EINVAL naming the argument; nothing is launched and the session keeps
+ * its state. */
+int pt_temporal_enqueue(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], uint32_t* d_counts,
+                        void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around it. */
+int pt_temporal_run(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], uint32_t* d_counts,
+                    float* ms_out);
+/* n frames in order, bit for bit what
+ *   for k in 0 .. n-1: pt_temporal_enqueue(t, d_frames + k * frame_stride, samples, bases + 12 k, eyes + 3 k, NULL, s)
+ * does (frame k reads what frame k-1 wrote, so it is n launches); d_counts receives the counts of the LAST frame.  Strides are in
+ * floats and may leave gaps (frame_stride >= width x height x 14), so the output of pt_renderer_enqueue_frames passes straight
+ * in.  n_frames < 1, a stride too small, and everything pt_temporal_enqueue refuses, for any frame, is PT_EINVAL and nothing is
+ * launched. */
+int pt_temporal_enqueue_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                               const float* eyes, int samples, uint32_t* d_counts, void* hip_stream);
+int pt_temporal_run_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                           const float* eyes, int samples, uint32_t* d_counts, float* ms_out);
+
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
  * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.
