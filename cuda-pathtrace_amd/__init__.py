@@ -199,6 +199,7 @@ LAB_ABI = {
     "pt_debug_policy_ms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pt_debug_policy_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_renderer_batch_launches": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "pt_debug_fast_nearest": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _vp, _vp]),
     "pt_debug_denoiser_layer_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                     ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_activation": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t]),
@@ -384,6 +385,21 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+def fast_nearest(spheres, rays, specialised=False, last=False, mask=0xFFFFFFFF):
+    """Lab library: the fast mode's nearest<> on rays [n][6] = {o, d} (pt_debug_fast_nearest).  Returns (t float32 [n], index
+    int32 [n], -1 for a miss)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = len(rays)
+    d_scene, ns = upload_scene(spheres)
+    d_rays, d_t, d_idx = DeviceBuffer(max(rays.nbytes, 4)).upload(rays), DeviceBuffer(max(4 * n, 4)), DeviceBuffer(max(4 * n, 4))
+    try:
+        check(lib.pt_debug_fast_nearest(d_scene.ptr, ns, d_rays.ptr, n, 1 if specialised else 0, 1 if last else 0, mask, d_t.ptr, d_idx.ptr))
+        return d_t.download(np.float32, (n,)), d_idx.download(np.int32, (n,))
+    finally:
+        for b in (d_scene, d_rays, d_t, d_idx):
+            b.free()
 
 
 def policy_ms(rng_mode, variant, waves_per_simd, spp, bounces=5):

@@ -57,10 +57,19 @@ __device__ __forceinline__ float sphere_t(F3 o, F3 d, float a, float inv_a, cons
   const float s = __builtin_amdgcn_sqrtf(disc);                                      // NaN when there is no real root
   const float nq = copysign_neg_b3(s, h, absmask) - h;  // -(h + copysign(s, h)): no cancellation (absmask in a VGPR: pt_device.h)
   const float t_big = nq * inv_a;                       // the root of larger magnitude
-  const float t_small = c * __builtin_amdgcn_rcpf(nq);  // the other one: their product is c / a
+  float t_small = c * __builtin_amdgcn_rcpf(nq);        // the other one: their product is c / a
   // The reference returns the smaller root if both are positive, else the positive one, else a non-positive number its caller
   // rejects (:82-88,99): as bit patterns that is one unsigned minimum -- positive floats order like their bits, and a set sign
-  // bit (or a NaN: no real root) lies above all of them (pt_intersect.h, screen_sphere_oc).
+  // bit (or a NaN: no real root) lies above all of them (pt_intersect.h, screen_sphere_oc).  One pattern breaks that order: an
+  // origin exactly ON the sphere (c == +0) heading inward (h < 0) has t_small = +0, bits 0, below every positive float, while the
+  // reference's "tNear > 0" rejects it and returns the far root.  So the smallest denormal is subtracted first: a zero of either
+  // sign becomes -2^-149 and loses like any non-positive root, and every t from 2^-124 up is returned bit for bit (2^-149 is less
+  // than half an ulp there; FP32 denormals are on in every build of this file, and tests/test_fast_rays_gpu.py fails if they
+  // ever are not).  One full-rate v_add_f32; NOT contracted into the product, where it would turn exact ties the other way.
+  {
+#pragma clang fp contract(off)
+    t_small = t_small - __uint_as_float(1u);
+  }
   const uint32_t tb = __float_as_uint(t_big), ts = __float_as_uint(t_small);
   return __uint_as_float(tb < ts ? tb : ts);
 }
@@ -340,3 +349,50 @@ hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStre
   hipLaunchKernelGGL(fn, dim3(grid), dim3(PT_BLOCK_THREADS), lds, stream, b);
   return hipGetLastError();
 }
+
+#if PT_BUILD_EXPERIMENTS
+// LAB LIBRARY ONLY (include/ptcore_lab.h, pt_debug_fast_nearest): nearest<> on a list of rays.  No frame shows what the LAST
+// shortcut and the masked ctz loop return per ray -- only bounce 4 of the <9,5> build uses the one, only spp >= 8 reaches the
+// other -- so the tests call them here: the scene staged exactly as pixel_kernel_fast stages it, one ray per thread.
+#include "pt_internal.h"
+#include "../../include/ptcore_lab.h"
+
+namespace pt {
+namespace fast {
+
+template <int NS, bool LAST>
+__global__ void __launch_bounds__(PT_BLOCK_THREADS) nearest_probe_kernel(const pt_sphere* spheres, int n, const float* rays, uint32_t n_rays,
+                                                                         uint32_t mask, float* t_out, int32_t* idx_out) {
+  if constexpr (NS > 0) n = NS;
+  extern __shared__ float4 lds_scene[];
+  SceneLds sc = stage_scene<false>(spheres, n, lds_scene, NS == 0 && n > PT_FAST_LDS_SPHERES, mk3(0.0f, 0.0f, 0.0f), 0, false);
+  const uint32_t i = blockIdx.x * PT_BLOCK_THREADS + threadIdx.x;
+  if (i >= n_rays) return;  // the tail, after the staging barrier
+  const float* r = rays + (size_t)i * 6;
+  float t = 0.0f;
+  int idx = 0;
+  const bool hit = nearest<NS, LAST>(sc, n, mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]), t, idx, mask);
+  t_out[i] = t;
+  idx_out[i] = hit ? idx : -1;
+}
+
+}  // namespace fast
+}  // namespace pt
+
+extern "C" int pt_debug_fast_nearest(const pt_sphere* d_spheres, int n_spheres, const float* d_rays, uint32_t n_rays, int specialised,
+                                     int last, uint32_t mask, float* d_t, int32_t* d_idx) {
+  if (!d_spheres || n_spheres < 1 || (specialised && n_spheres != 9) || (n_rays && (!d_rays || !d_t || !d_idx)))
+    return pt_fail(PT_EINVAL, "pt_debug_fast_nearest: bad arguments");
+  if (!n_rays) return PT_OK;
+  typedef void (*probe_fn)(const pt_sphere*, int, const float*, uint32_t, uint32_t, float*, int32_t*);
+  const probe_fn fn = specialised ? (last ? pt::fast::nearest_probe_kernel<9, true> : pt::fast::nearest_probe_kernel<9, false>)
+                                  : (last ? pt::fast::nearest_probe_kernel<0, true> : pt::fast::nearest_probe_kernel<0, false>);
+  const unsigned grid = (unsigned)(((uint64_t)n_rays + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(PT_BLOCK_THREADS), pt_fast_kernel_lds_bytes(n_spheres), 0, d_spheres, n_spheres, d_rays, n_rays,
+                     mask, d_t, d_idx);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_debug_fast_nearest: %s", hipGetErrorString(e));
+  return PT_OK;
+}
+#endif  // PT_BUILD_EXPERIMENTS

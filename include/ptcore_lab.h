@@ -64,6 +64,16 @@ int pt_debug_policy_choice(int rng_mode, double waves_per_simd, int spp, int bou
  * use it to see that the kernel they check is the one that ran. */
 int pt_debug_renderer_batch_launches(pt_renderer* r, uint32_t* launches);
 
+/* The fast mode's scene intersection on a list of rays (csrc/pt_fast.hip, nearest<>): what no frame shows per ray -- the LAST
+ * shortcut (the key alone decides; only the last bounce of the 9-sphere, 5-bounce build uses it) and the masked loop of the
+ * specialised build (only primary rays at spp >= 8 reach it).  d_rays holds n_rays rays of 6 floats {o, d}.  specialised != 0
+ * requires n_spheres == 9 and runs nearest<9, .>, else nearest<0, .>; last = 0 or 1; mask = the spheres to rank (bit i = sphere
+ * i; the generic build ranks all of them whatever it says).  The scene is staged as the frame kernel stages it (LDS up to 64
+ * spheres, read in place above), one ray per thread of 256-thread workgroups.  Per ray: d_t = the t nearest<> reports (with
+ * last: the ranked key, index bits cleared), d_idx = the sphere, -1 for a miss.  Synchronous. */
+int pt_debug_fast_nearest(const pt_sphere* d_spheres, int n_spheres, const float* d_rays, uint32_t n_rays, int specialised, int last,
+                          uint32_t mask, float* d_t, int32_t* d_idx);
+
 /* Denoiser diagnostics (csrc/pt_denoise.hip).  Layers = the activation buffers of the workspace, in execution order:
  * 0 "input" (the pre-processed frame, NHWC, 16 channels of which 14-15 are zero), "block<b>.t1" / ".res" / ".out", "lat6",
  * "back<k+1><k>", "rep<k>".  shape = {rows, cols, channels}; *n_layers = their number (also for an invalid `layer`). */
