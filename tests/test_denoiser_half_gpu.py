@@ -167,8 +167,13 @@ def test_half_end_to_end_error_is_the_models(pt, gpu, dw, w, h, seed, capsys):
 def test_half_per_layer_rounding_within_the_bound(pt, lab, gpu, dw, sd, capsys):
     """Every layer, from the half input of that layer, against float64 on that same (already rounded) input and the rounded
     weights: |hip - ref| <= 4e-6 S + 4 ulp32(ref) + 1 ulp16(ref) -- the fp32 mode's bound plus the one rounding of the store
-    (the head stores fp32: no ulp16 term).  Saturated elements are compared with +-65504."""
-    w, h = 256, 256
+    (the head stores fp32: no ulp16 term).  Saturated elements are compared with +-65504.  At 256 x 256 and at 37 x 29 (every
+    M ragged, maps down to 1 x 1), the same bound."""
+    for w, h in ((256, 256), (37, 29)):
+        _half_per_layer_rounding(pt, lab, dw, sd, capsys, w, h)
+
+
+def _half_per_layer_rounding(pt, lab, dw, sd, capsys, w, h):
     frame = cornell(pt, w, h)
     sdh = {k: (np.clip(v, -HALF_MAX, HALF_MAX).astype(np.float16).astype(np.float32) if v.ndim == 4 else v) for k, v in sd.items()}
     dn = lab.Denoiser(w, h, sd, precision="half")
@@ -196,7 +201,7 @@ def test_half_per_layer_rounding_within_the_bound(pt, lab, gpu, dw, sd, capsys):
     finally:
         dn.destroy()
     with capsys.disabled():
-        print("\nhalf per-layer worst (|err| - 4 ulp32 - 1 ulp16) / S:", " ".join(f"{k}={v:.2e}" for k, v in worst.items()))
+        print(f"\n{w}x{h} half per-layer worst (|err| - 4 ulp32 - 1 ulp16) / S:", " ".join(f"{k}={v:.2e}" for k, v in worst.items()))
         print("overall worst ratio: %.3e (bound 4e-6)" % max(worst.values()))
 
 
