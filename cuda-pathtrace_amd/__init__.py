@@ -199,6 +199,10 @@ LAB_ABI = {
     "pt_debug_policy_ms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pt_debug_policy_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_renderer_batch_launches": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "pt_debug_kernel_builds": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32)]),
+    "pt_debug_variant_row": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32)]),
+    "pt_debug_launch_census": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "pt_debug_launch_census_reset": (ctypes.c_int, []),
     "pt_debug_fast_nearest": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _vp, _vp]),
     "pt_debug_denoiser_layer_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                     ctypes.c_char_p, ctypes.c_size_t]),
@@ -415,6 +419,55 @@ def policy_choice(rng_mode, waves_per_simd, spp, bounces=5, with9=True):
     v = ctypes.c_int(0)
     check(lib.pt_debug_policy_choice(rng_mode, waves_per_simd, spp, bounces, 1 if with9 else 0, 1 if spp >= 512 else 0, ctypes.byref(v)))
     return v.value
+
+
+BUILD_FIELDS = ("flavour", "rng", "kernel", "wide", "lean", "ref", "lanes", "row")
+FLAVOUR_PLAIN, FLAVOUR_FRAMES, FLAVOUR_RESUME, FLAVOUR_ADAPTIVE, FLAVOUR_FAST = range(5)
+ROW_FIELDS = ("product", "lanes", "threads", "lean", "grid", "wide", "ref_builds", "resume", "frames", "can_chunk", "kernel", "chunk_family")
+CENSUS_CHUNKED, CENSUS_REPAIR, CENSUS_PLANAR, CENSUS_VERTICES, CENSUS_RNG_STATE, CENSUS_FOOTPRINT, CENSUS_FIRST_PASS, CENSUS_PRIO = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def kernel_builds():
+    """Lab library: every distinct kernel function the selectors can return (pt_debug_kernel_builds), one dict of BUILD_FIELDS
+    each, in the order launch_census() reports them.  Needs no device."""
+    n = ctypes.c_int(0)
+    check(lib.pt_debug_kernel_builds(0, ctypes.byref(n), None))
+    out = []
+    for i in range(n.value):
+        info = (ctypes.c_int32 * len(BUILD_FIELDS))()
+        check(lib.pt_debug_kernel_builds(i, None, info))
+        out.append(dict(zip(BUILD_FIELDS, (int(x) for x in info))))
+    return out
+
+
+def variant_rows():
+    """Lab library: the rows of the kernel-variant table (pt_debug_variant_row), one dict of ROW_FIELDS each.  Needs no device."""
+    n = ctypes.c_int(0)
+    check(lib.pt_debug_variant_row(0, ctypes.byref(n), None))
+    out = []
+    for i in range(n.value):
+        info = (ctypes.c_int32 * len(ROW_FIELDS))()
+        check(lib.pt_debug_variant_row(i, None, info))
+        out.append(dict(zip(ROW_FIELDS, (int(x) for x in info))))
+    return out
+
+
+def launch_census():
+    """Lab library: [(launches, modes)] per build of kernel_builds() since the last launch_census_reset(), plus a last entry for
+    launches of functions that are in no build (pt_debug_launch_census; modes = OR of CENSUS_*)."""
+    n = ctypes.c_int(0)
+    check(lib.pt_debug_kernel_builds(0, ctypes.byref(n), None))
+    out = []
+    for i in list(range(n.value)) + [-1]:
+        launches, modes = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib.pt_debug_launch_census(i, ctypes.byref(launches), ctypes.byref(modes)))
+        out.append((launches.value, modes.value))
+    return out
+
+
+def launch_census_reset():
+    check(lib.pt_debug_launch_census_reset())
 
 
 def grid_header(spheres):

@@ -347,7 +347,9 @@ hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStre
   }
   const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(PT_BLOCK_THREADS), lds, stream, b);
-  return hipGetLastError();
+  // (census: the footprint analysis is in the <9, 5> build, from 8 samples -- pixel_kernel_fast, prim_mask)
+  return PT_LAUNCHED(fn, (b.planar != 0u ? PT_CENSUS_MODE_PLANAR : 0u) | (b.vertices ? PT_CENSUS_MODE_VERTICES : 0u) | (b.rng_state ? PT_CENSUS_MODE_RNG_STATE : 0u) |
+                             (a.n_spheres == 9 && a.max_bounces == 5 && a.spp >= 8 ? PT_CENSUS_MODE_FOOTPRINT : 0u));
 }
 
 #if PT_BUILD_EXPERIMENTS

@@ -305,3 +305,15 @@ hipError_t pt_launch_setup_random(uint32_t* state, int width, int row_begin, uin
 const void* pt_fast_kernel_symbol(int rng_mode, int n_spheres, int max_bounces);
 size_t pt_fast_kernel_lds_bytes(int n_spheres);
 hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStream_t stream);
+
+// The launch census (lab library only; include/ptcore_lab.h, pt_debug_launch_census): every launcher of a pixel kernel ends in
+// PT_LAUNCHED(fn, modes) -- the launch's status, and in the lab library a count under the function it handed to
+// hipLaunchKernelGGL when that status is hipSuccess, with what the launch was (PT_CENSUS_MODE_*).  The product library's
+// launchers are what they were: `modes` is not even evaluated there.
+#if PT_BUILD_EXPERIMENTS
+#include "../../include/ptcore_lab.h"
+hipError_t pt_census_launched(const void* fn, uint32_t modes);  // pt_kernel.hip
+#define PT_LAUNCHED(fn, modes) pt_census_launched((const void*)(fn), (modes))
+#else
+#define PT_LAUNCHED(fn, modes) hipGetLastError()
+#endif

@@ -1265,6 +1265,16 @@ static hipError_t prepare_launch(const void* fn, const VariantInfo& v, PixelKern
   return hipSuccess;
 }
 
+#if PT_BUILD_EXPERIMENTS
+// what a launch was, for the census: from the arguments the kernel got.  `ref`: a reference-configuration build (the ones with the
+// footprint analysis), `samples`: the count that build compares with PT_FOOTPRINT_MIN_SPP (pixel_kernel: pass_spp; split: a.spp)
+static inline uint32_t census_modes(const PixelKernelArgs& b, bool ref, int samples) {
+  return (b.chunks > 1u ? PT_CENSUS_MODE_CHUNKED : 0u) | (b.repair != 0u ? PT_CENSUS_MODE_REPAIR : 0u) | (b.planar != 0u ? PT_CENSUS_MODE_PLANAR : 0u) |
+         (b.vertices ? PT_CENSUS_MODE_VERTICES : 0u) | (b.rng_state ? PT_CENSUS_MODE_RNG_STATE : 0u) |
+         (ref && samples >= PT_FOOTPRINT_MIN_SPP ? PT_CENSUS_MODE_FOOTPRINT : 0u) | (b.prio != 0u ? PT_CENSUS_MODE_PRIO : 0u);
+}
+#endif
+
 hipError_t pt_launch_pixel_kernel(const PixelKernelArgs& a, int rng_mode, int variant, hipStream_t stream) {
   variant = run_variant(variant, a.max_bounces);
   const auto fn = select_kernel<>(rng_mode, variant, a.n_spheres, a.max_bounces, a.planar != 0u);
@@ -1283,7 +1293,7 @@ hipError_t pt_launch_pixel_kernel(const PixelKernelArgs& a, int rng_mode, int va
     grid *= a.chunks;
   }
   hipLaunchKernelGGL(fn, dim3(grid), dim3(s.block), s.lds, stream, b);
-  return hipGetLastError();
+  return PT_LAUNCHED(fn, census_modes(b, ref_config(a.n_spheres, a.max_bounces, pt_kernel_variant(variant), a.planar != 0u) != 0, a.spp));
 }
 
 bool pt_kernel_has_frames(int variant, int n_spheres, int max_bounces, bool planar) {
@@ -1303,7 +1313,7 @@ hipError_t pt_launch_frames_kernel(const FramesKernelArgs& fa, int rng_mode, int
   const hipError_t e = prepare_launch((const void*)fn, pt_kernel_variant(variant), b.base, a.spp, stream, &s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(rng_mode == PT_RNG_PHILOX ? s.blocks * fa.frames : s.blocks), dim3(s.block), s.lds, stream, b);
-  return hipGetLastError();
+  return PT_LAUNCHED(fn, census_modes(b.base, true, a.spp));  // (a batch has reference-configuration builds only)
 }
 
 hipError_t pt_launch_setup_random(uint32_t* state, int width, int row_begin, uint32_t tile_pixels, uint64_t seed,
@@ -1332,7 +1342,8 @@ static hipError_t launch_pass(const Args& ra, int rng_mode, int variant, hipStre
   const hipError_t e = prepare_launch((const void*)fn, pt_kernel_variant(variant), b.base, a.spp - ra.sample_begin, stream, &s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(s.blocks), dim3(s.block), s.lds, stream, b);
-  return hipGetLastError();
+  return PT_LAUNCHED(fn, census_modes(b.base, ref_config(a.n_spheres, a.max_bounces, pt_kernel_variant(variant), a.planar != 0u) != 0, a.spp - ra.sample_begin) |
+                             (ra.sample_begin == 0 ? (uint32_t)PT_CENSUS_MODE_FIRST_PASS : 0u));
 }
 
 hipError_t pt_launch_resume_kernel(const ResumeKernelArgs& ra, int rng_mode, int variant, hipStream_t stream) {
@@ -1343,3 +1354,119 @@ hipError_t pt_launch_adaptive_kernel(const AdaptiveKernelArgs& aa, int rng_mode,
   if (!aa.list || !aa.list_len) return hipErrorInvalidValue;
   return launch_pass<true>(aa, rng_mode, variant, stream);
 }
+
+#if PT_BUILD_EXPERIMENTS
+// ---- lab library: the builds behind the selectors and the launch census (include/ptcore_lab.h) ------------------------------
+// Every distinct function select_kernel<> and the fast mode's selector can return, found by walking the selectors themselves
+// over (flavour, generator, row, LDS layout, reference configuration): what a row announces but the selector does not hand out
+// is not here, and the tests compare this list with the rows (tests/test_kernel_census_host.py).
+#include <atomic>
+#include <mutex>
+
+#include "pt_internal.h"
+#include "../../include/ptcore_lab.h"
+
+namespace {
+struct CensusBuild {
+  const void* fn;
+  int32_t info[PT_BUILD_INFO_WORDS];  // flavour, generator, kernel row, wide, lean, reference bounces, lanes per pixel, first row that selects it
+};
+constexpr int kCensusMax = 256;
+CensusBuild g_builds[kCensusMax];
+int g_n_builds = 0;
+std::atomic<uint32_t> g_launches[kCensusMax], g_modes[kCensusMax];
+std::atomic<uint32_t> g_unknown_launches{0u};  // launches of a function the walk did not find (none, or the walk is wrong)
+std::once_flag g_census_once;
+
+template <bool FRAMES, bool RESUME, bool ADAPTIVE>
+const void* build_of(int rng, int row, bool lean, int ref) {
+  const std::make_integer_sequence<int, kNumVariants> all;
+  return rng == PT_RNG_PHILOX ? (const void*)select_kernel_of<FRAMES, RESUME, ADAPTIVE, PT_RNG_PHILOX>(row, lean, ref, all)
+                              : (const void*)select_kernel_of<FRAMES, RESUME, ADAPTIVE, PT_RNG_XORWOW>(row, lean, ref, all);
+}
+
+void census_add(const void* fn, int flavour, int rng, int kernel, int wide, int lean, int ref, int lanes, int row) {
+  if (!fn) return;
+  for (int i = 0; i < g_n_builds; i++)
+    if (g_builds[i].fn == fn) return;  // (equal pointers: one build)
+  if (g_n_builds >= kCensusMax) return;
+  g_builds[g_n_builds++] = CensusBuild{fn, {flavour, rng, kernel, wide, lean, ref, lanes, row}};
+}
+
+void census_enumerate() {
+  static const int refs[3] = {0, 5, 8};
+  for (int flavour = 0; flavour < 4; flavour++)
+    for (int rng = 0; rng < 2; rng++)
+      for (int row = 0; row < kNumVariants; row++)
+        for (int lean = 0; lean < 2; lean++)
+          for (int ref : refs) {
+            const VariantInfo& v = kVariants[row];
+            const void* fn = flavour == 0 ? build_of<false, false, false>(rng, row, lean != 0, ref)
+                           : flavour == 1 ? build_of<true, false, false>(rng, row, lean != 0, ref)
+                           : flavour == 2 ? build_of<false, true, false>(rng, row, lean != 0, ref)
+                                          : build_of<false, true, true>(rng, row, lean != 0, ref);
+            census_add(fn, flavour, rng, v.kernel, v.wide ? 1 : 0, lean, ref, v.lanes, row);
+          }
+  for (int rng = 0; rng < 2; rng++) {  // the fast mode (pt_fast.hip): the reference's configuration as constants, and the generic build
+    census_add(pt_fast_kernel_symbol(rng, 9, 5), 4, rng, PT_VARIANT_FAST, 0, 0, 5, 1, PT_VARIANT_FAST);
+    census_add(pt_fast_kernel_symbol(rng, 1, 1), 4, rng, PT_VARIANT_FAST, 0, 0, 0, 1, PT_VARIANT_FAST);
+  }
+}
+}  // namespace
+
+hipError_t pt_census_launched(const void* fn, uint32_t modes) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  std::call_once(g_census_once, census_enumerate);
+  for (int i = 0; i < g_n_builds; i++)
+    if (g_builds[i].fn == fn) {
+      g_launches[i].fetch_add(1u, std::memory_order_relaxed);
+      g_modes[i].fetch_or(modes, std::memory_order_relaxed);
+      return e;
+    }
+  g_unknown_launches.fetch_add(1u, std::memory_order_relaxed);
+  return e;
+}
+
+extern "C" int pt_debug_kernel_builds(int index, int* n_builds, int32_t info[PT_BUILD_INFO_WORDS]) {
+  std::call_once(g_census_once, census_enumerate);
+  if (n_builds) *n_builds = g_n_builds;
+  if (!info) return PT_OK;  // (only the count)
+  if (index < 0 || index >= g_n_builds) return pt_fail(PT_EINVAL, "pt_debug_kernel_builds: index %d of %d builds", index, g_n_builds);
+  for (int k = 0; k < PT_BUILD_INFO_WORDS; k++) info[k] = g_builds[index].info[k];
+  return PT_OK;
+}
+
+extern "C" int pt_debug_variant_row(int row, int* n_rows, int32_t info[PT_ROW_INFO_WORDS]) {
+  if (n_rows) *n_rows = kNumVariants;
+  if (!info) return PT_OK;
+  if (row < 0 || row >= kNumVariants) return pt_fail(PT_EINVAL, "pt_debug_variant_row: row %d of %d", row, kNumVariants);
+  const VariantInfo& v = kVariants[row];
+  const int32_t words[PT_ROW_INFO_WORDS] = {v.product, v.lanes, v.threads, v.lean, v.grid, v.wide, v.ref_builds, v.resume, v.frames, v.can_chunk, v.kernel, v.chunk_family};
+  for (int k = 0; k < PT_ROW_INFO_WORDS; k++) info[k] = words[k];
+  return PT_OK;
+}
+
+extern "C" int pt_debug_launch_census(int index, uint32_t* launches, uint32_t* modes) {
+  std::call_once(g_census_once, census_enumerate);
+  if (!launches || !modes) return pt_fail(PT_EINVAL, "pt_debug_launch_census: NULL argument");
+  if (index == -1) {  // launches of functions that are not in the list of builds
+    *launches = g_unknown_launches.load(std::memory_order_relaxed);
+    *modes = 0u;
+    return PT_OK;
+  }
+  if (index < 0 || index >= g_n_builds) return pt_fail(PT_EINVAL, "pt_debug_launch_census: index %d of %d builds", index, g_n_builds);
+  *launches = g_launches[index].load(std::memory_order_relaxed);
+  *modes = g_modes[index].load(std::memory_order_relaxed);
+  return PT_OK;
+}
+
+extern "C" int pt_debug_launch_census_reset(void) {
+  for (int i = 0; i < kCensusMax; i++) {
+    g_launches[i].store(0u, std::memory_order_relaxed);
+    g_modes[i].store(0u, std::memory_order_relaxed);
+  }
+  g_unknown_launches.store(0u, std::memory_order_relaxed);
+  return PT_OK;
+}
+#endif  // PT_BUILD_EXPERIMENTS

@@ -64,6 +64,34 @@ int pt_debug_policy_choice(int rng_mode, double waves_per_simd, int spp, int bou
  * use it to see that the kernel they check is the one that ran. */
 int pt_debug_renderer_batch_launches(pt_renderer* r, uint32_t* launches);
 
+/* The builds behind the kernel selectors: every distinct kernel function that the pixel-kernel selector (csrc/pt_kernel.hip,
+ * select_kernel) and the fast mode's (csrc/pt_fast.hip) can return in this library, found by walking the selectors themselves.
+ * *n_builds = their number (info may be NULL); info = {flavour (0 plain, 1 frames, 2 resume, 3 adaptive, 4 fast), generator
+ * (PT_RNG_*), kernel row (100 for the fast mode; a wide row reports the row whose kernel it runs), wide, lean LDS layout,
+ * reference bounces (0 generic, 5, 8), lanes per pixel, the first table row that selects it}.  Host only: needs no device. */
+#define PT_BUILD_INFO_WORDS 8
+int pt_debug_kernel_builds(int index, int* n_builds, int32_t info[PT_BUILD_INFO_WORDS]);
+/* Row `row` of the kernel-variant table (csrc/pt_kernel.h, VariantInfo): info = {product, lanes, threads, lean (0 never, 1 above
+ * 10 spheres, 2 always), grid, wide, ref_builds, resume, frames, can_chunk, kernel, chunk_family}; *n_rows = rows.  Host only. */
+#define PT_ROW_INFO_WORDS 12
+int pt_debug_variant_row(int row, int* n_rows, int32_t info[PT_ROW_INFO_WORDS]);
+/* The launch census.  Every launcher of a pixel kernel counts each launch that succeeded under the function it launched:
+ * *launches = launches of build `index` (the index of pt_debug_kernel_builds) since the last reset, by any renderer and thread
+ * of the process; *modes = the OR over those launches of what each was (PT_CENSUS_* below).  index -1: launches of functions
+ * that are not in the list (there should be none).  The tests use it to see that the build they compare is the one that ran. */
+enum {
+  PT_CENSUS_MODE_CHUNKED = 1,     /* the samples were chained through chunks > 1 workgroups                                */
+  PT_CENSUS_MODE_REPAIR = 2,      /* a repair launch after a broken chunk chain                                            */
+  PT_CENSUS_MODE_PLANAR = 4,      /* channel-first output                                                                  */
+  PT_CENSUS_MODE_VERTICES = 8,    /* the fused display vertices were written                                               */
+  PT_CENSUS_MODE_RNG_STATE = 16,  /* a persisted generator state was read and written (else: seeded in the kernel)         */
+  PT_CENSUS_MODE_FOOTPRINT = 32,  /* the build has the pixel-footprint analysis and the launch's sample count reached it   */
+  PT_CENSUS_MODE_FIRST_PASS = 64, /* resume and adaptive builds: the pass started from zero samples                        */
+  PT_CENSUS_MODE_PRIO = 128       /* issue priority by progress was on                                                     */
+};
+int pt_debug_launch_census(int index, uint32_t* launches, uint32_t* modes);
+int pt_debug_launch_census_reset(void);
+
 /* The fast mode's scene intersection on a list of rays (csrc/pt_fast.hip, nearest<>): what no frame shows per ray -- the LAST
  * shortcut (the key alone decides; only the last bounce of the 9-sphere, 5-bounce build uses it) and the masked loop of the
  * specialised build (only primary rays at spp >= 8 reach it).  d_rays holds n_rays rays of 6 floats {o, d}.  specialised != 0
