@@ -85,11 +85,15 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
         const bool valid = ok & inside & (t2.w > 0.0f) & (fabsf(t1.w - al) <= dtol) &
                            ((t1.x * nx + t1.y * ny) + t1.z * nz >= p.normal_tol) &
                            ((dax * dax + day * day) + daz * daz <= p.albedo_tol);
+        // an invalid tap contributes 0 to every sum: its values are selected away with its weight (0 * NaN is NaN, and a
+        // history pixel that fails a stop may hold anything)
         const float w = valid ? wgt : 0.0f;
+        const float tx = valid ? t0.x : 0.0f, ty = valid ? t0.y : 0.0f, tz = valid ? t0.z : 0.0f;
+        const float ts = valid ? t0.w : 0.0f, tn = valid ? t2.w : 0.0f;
         ws = ws + w;
-        sx = sx + w * t0.x, sy2 = sy2 + w * t0.y, sz = sz + w * t0.z;
-        ss = ss + w * t0.w;
-        sn = sn + w * t2.w;
+        sx = sx + w * tx, sy2 = sy2 + w * ty, sz = sz + w * tz;
+        ss = ss + w * ts;
+        sn = sn + w * tn;
       }
     }
     const bool keep = ws >= p.min_weight;

@@ -98,11 +98,14 @@ class TemporalModel:
                 dA = t2[..., :3] - A
                 valid = (ok & inside & (t2[..., 3] > 0) & (np.abs(t1[..., 3] - al) <= dtol)
                          & (_dot3(t1[..., :3], N) >= self.normal_tol) & (_dot3(dA, dA) <= self.albedo_tol))
+                # an invalid tap contributes 0 to every sum: its values are selected away with its weight (0 * NaN is NaN)
                 w = np.where(valid, w, f32(0.0)).astype(f32)
+                t0 = np.where(valid[..., None], t0, f32(0.0)).astype(f32)
+                tn = np.where(valid, t2[..., 3], f32(0.0)).astype(f32)
                 Ws = Ws + w
                 sC = sC + w[..., None] * t0[..., :3]
                 ss2 = ss2 + w * t0[..., 3]
-                sN = sN + w * t2[..., 3]
+                sN = sN + w * tn
         keep = Ws >= self.min_weight
         hC = np.where(keep[..., None], sC / Ws[..., None], f32(0.0)).astype(f32)
         hs2 = np.where(keep, ss2 / Ws, f32(0.0)).astype(f32)
@@ -143,6 +146,13 @@ def accumulate_sequence(frames, n, bases, eyes, **opts):
     m = TemporalModel(frames.shape[2], frames.shape[1], **opts)
     outs, counts = zip(*(m.accumulate(f, n, b, e) for f, b, e in zip(frames, bases, eyes)))
     return np.stack(outs), np.stack(counts)
+
+
+def run_calls(width, height, calls, **opts):
+    """calls [(frame, samples, basis, eye)] through one session: ([frame after the stage], [counts])."""
+    m = TemporalModel(width, height, **opts)
+    outs, counts = zip(*(m.accumulate(f, n, b, e) for f, n, b, e in calls))
+    return list(outs), list(counts)
 
 
 # static camera, 4 x 4 spp against 16 spp: the worst |d| / (|ref| + 1e-3) measured with the committed model on the oracle's frames

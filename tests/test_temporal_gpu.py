@@ -96,6 +96,8 @@ def assert_bit_parity(got, got_counts, want, want_counts, what):
 
 @pytest.mark.parametrize("size", [(64, 64), (37, 29), (64, 3), (3, 64), (1, 1)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_bit_parity_with_the_model_on_a_fly_through(pt, gpu, size):
+    """Share of the pixels of frames 1 .. 5 that find history, measured with the model on these frames: 0.801 .. 0.809 at
+    64 x 64 (band 0.5 .. 0.95) and 0.521 .. 0.599 at 37 x 29 (the same margins below and above: 0.22 .. 0.75)."""
     w, h = size
     frames, bases, eyes, want, want_counts = sequence(pt, w, h)
     assert (frames[..., 9] > 0).any()
@@ -104,6 +106,12 @@ def test_bit_parity_with_the_model_on_a_fly_through(pt, gpu, size):
             share = float((want_counts[k] > N).mean())
             print(f"frame {k}: {share:.3f} of the pixels with history")
             assert 0.5 <= share <= 0.95, (k, share)
+        assert want_counts.max() == N * FRAMES
+    if size == (37, 29):  # the same on the frame that is not square (measured 0.52 .. 0.60; the margins of the 64 x 64 band)
+        for k in range(1, FRAMES):
+            share = float((want_counts[k] > N).mean())
+            print(f"37 x 29 frame {k}: {share:.3f} of the pixels with history")
+            assert 0.22 <= share <= 0.75, (k, share)
         assert want_counts.max() == N * FRAMES
     got, got_counts = run_singles(pt, frames, bases, eyes)
     assert_bit_parity(got, got_counts, want, want_counts, size)
