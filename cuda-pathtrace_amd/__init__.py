@@ -73,6 +73,8 @@ class AdaptiveOpts(ctypes.Structure):  # pt_adaptive_opts
     ]
 
 
+REC_WORDS = 26  # PT_CHUNK_WORDS (csrc/pt_kernel.h): words per tile pixel of a session's record
+
 # Progressive.set_adaptive's defaults (profiles/adaptive/README.md: how they were chosen)
 ADAPTIVE_FLOOR, ADAPTIVE_MIN_SAMPLES, ADAPTIVE_RADIUS = 0.05, 16, 1
 
@@ -219,6 +221,9 @@ LAB_ABI = {
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "pt_debug_progressive_record": (ctypes.c_int, [_vp, _vp]),
     "pt_debug_progressive_set_active": (ctypes.c_int, [_vp, _vp]),
+    "pt_debug_adaptive_select": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(AdaptiveOpts), _vp, _vp, _vp, _vp, _vp]),
+    "pt_debug_adaptive_finalize": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp]),
 }
 
 FN_INV_SQRT_LITERAL, FN_INV_SQRT_FAST, FN_SQRT_LITERAL, FN_SQRT_FAST, FN_SIN, FN_COS, FN_UNIFORM = range(7)
@@ -706,7 +711,7 @@ class Progressive:
 
     def record(self):  # lab library only (pt_debug_progressive_record): [26][tile pixels] uint32
         n = self.renderer.rows * self.renderer.width
-        a = np.zeros((26, n), dtype=np.uint32)
+        a = np.zeros((REC_WORDS, n), dtype=np.uint32)
         check(lib.pt_debug_progressive_record(self.handle, a.ctypes.data))
         return a
 
@@ -724,6 +729,34 @@ class Progressive:
             self.destroy()
         except Exception:
             pass
+
+
+def debug_adaptive_select(rec, width, n, n_end, mode, peek, tolerance, floor, min_samples, radius, mask, counts, lst, words):
+    """Lab library only (pt_debug_adaptive_select): the selection kernels of an adaptive pass on host arrays.  rec [26][pixels]
+    uint32; mask uint8, counts and lst uint32 of `pixels` entries, words uint32 of 2.  Nothing is changed in place: returns
+    (mask, counts, list, words, block prefix) as the call left them."""
+    rec = np.ascontiguousarray(rec, dtype=np.uint32)
+    tp = rec.shape[1]
+    assert rec.shape[0] == REC_WORDS
+    out = [np.array(a, dtype=t, copy=True).reshape(-1) for a, t in ((mask, np.uint8), (counts, np.uint32), (lst, np.uint32), (words, np.uint32))]
+    assert [a.size for a in out] == [tp, tp, tp, 2]
+    sums = np.zeros((tp + 255) // 256, dtype=np.uint32)
+    o = AdaptiveOpts(float(tolerance), float(floor), int(min_samples), int(radius))
+    check(lib.pt_debug_adaptive_select(rec.ctypes.data, tp, int(width), int(n), int(n_end), int(mode), int(bool(peek)), ctypes.byref(o),
+                                       out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, sums.ctypes.data))
+    return out[0], out[1], out[2], out[3], sums
+
+
+def debug_adaptive_finalize(rec, counts, planar):
+    """Lab library only (pt_debug_adaptive_finalize): the frame of rec [26][pixels] at counts [pixels], float32 [pixels][14] or,
+    planar, [14][pixels]."""
+    rec = np.ascontiguousarray(rec, dtype=np.uint32)
+    tp = rec.shape[1]
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert rec.shape[0] == REC_WORDS and counts.size == tp
+    out = np.zeros((14, tp) if planar else (tp, 14), dtype=np.float32)
+    check(lib.pt_debug_adaptive_finalize(rec.ctypes.data, counts.ctypes.data, tp, int(bool(planar)), out.ctypes.data))
+    return out
 
 
 class MultiRenderer:

@@ -965,10 +965,7 @@ int pt_progressive_set_adaptive(pt_progressive* p, const pt_adaptive_opts* opts)
     PT_HIP(hipMemset(p->ast.words, 0, 4 * sizeof(uint32_t)));
   }
   p->opts = *opts;
-  p->rule.tolerance = (double)opts->tolerance;
-  p->rule.floor = (double)opts->floor;
-  p->rule.min_samples = opts->min_samples;
-  p->rule.radius = opts->radius;
+  p->rule = pt_adaptive_rule(*opts);
   p->forced = false;
   return PT_OK;
 }

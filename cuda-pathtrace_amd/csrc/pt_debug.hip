@@ -179,3 +179,96 @@ extern "C" int pt_debug_grid_image(const pt_sphere* d_spheres, int n_spheres, co
   PT_HIPD(e);
   return PT_OK;
 }
+
+#if PT_BUILD_EXPERIMENTS
+// ---- the adaptive selection and finalize kernels on states the caller builds (include/ptcore_lab.h) ----------------------------
+// Host code only: the launchers are pt_adaptive.hip's own.  Every device array is an allocation of its own, filled with a sentinel
+// before the caller's data goes over its front, and followed by 64 guard words; a guard that changed is reported by name.
+namespace {
+
+constexpr size_t kGuardBytes = 256;  // 64 words (the mask: 256 bytes)
+constexpr int kSentinel = 0xA5;
+
+struct GuardedArray {
+  const char* name = "";
+  uint8_t* d = nullptr;
+  size_t bytes = 0;
+  ~GuardedArray() {
+    if (d) (void)hipFree(d);
+  }
+  hipError_t create(const char* nm, const void* host, size_t n) {
+    name = nm;
+    bytes = n;
+    hipError_t e = hipMalloc((void**)&d, n + kGuardBytes);
+    if (e == hipSuccess) e = hipMemset(d, kSentinel, n + kGuardBytes);
+    if (e == hipSuccess && host && n) e = hipMemcpy(d, host, n, hipMemcpyHostToDevice);
+    return e;
+  }
+  // the array back to the host (host may be NULL) and the guard read: *broken = the first array whose guard changed
+  hipError_t finish(void* host, const char** broken) {
+    uint8_t g[kGuardBytes];
+    hipError_t e = (host && bytes) ? hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(g, d + bytes, kGuardBytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (size_t i = 0; i < kGuardBytes; i++)
+      if (g[i] != (uint8_t)kSentinel && !*broken) *broken = name;
+    return hipSuccess;
+  }
+};
+
+}  // namespace
+
+extern "C" int pt_debug_adaptive_select(const uint32_t* rec, uint32_t tile_pixels, int width, int n, int n_end, int mode, int peek,
+                                        const pt_adaptive_opts* opts, uint8_t* mask, uint32_t* counts, uint32_t* list,
+                                        uint32_t words[2], uint32_t* block_sums) {
+  if (!rec || !opts || !mask || !counts || !list || !words || !tile_pixels)
+    return pt_fail(PT_EINVAL, "pt_debug_adaptive_select: NULL argument or an empty tile");
+  if (opts->radius < 0 || opts->radius > PT_ADAPTIVE_MAX_RADIUS)
+    return pt_fail(PT_EINVAL, "pt_debug_adaptive_select: radius %d (0..%d)", opts->radius, PT_ADAPTIVE_MAX_RADIUS);
+  const size_t tp = tile_pixels, n_blocks = (tp + PT_ADAPTIVE_BLOCK - 1) / PT_ADAPTIVE_BLOCK;
+  GuardedArray g_rec, g_mask, g_counts, g_list, g_words, g_sums;
+  PT_HIPD(g_rec.create("rec", rec, (size_t)PT_CHUNK_WORDS * tp * sizeof(uint32_t)));
+  PT_HIPD(g_mask.create("mask", mask, tp));
+  PT_HIPD(g_counts.create("counts", counts, tp * sizeof(uint32_t)));
+  PT_HIPD(g_list.create("list", list, tp * sizeof(uint32_t)));
+  PT_HIPD(g_words.create("words", words, 2 * sizeof(uint32_t)));
+  PT_HIPD(g_sums.create("block_sums", nullptr, n_blocks * sizeof(uint32_t)));
+  AdaptiveState s{};
+  s.counts = (uint32_t*)g_counts.d;
+  s.list = (uint32_t*)g_list.d;
+  s.mask = g_mask.d;
+  s.block_sums = (uint32_t*)g_sums.d;
+  s.words = (uint32_t*)g_words.d;
+  const AdaptiveRule rule = pt_adaptive_rule(*opts);
+  const hipError_t e = pt_launch_adaptive_select(s, rule, (const uint32_t*)g_rec.d, tile_pixels, width, n, n_end, mode, peek != 0, nullptr);
+  if (e == hipErrorInvalidValue) return pt_fail(PT_EINVAL, "pt_debug_adaptive_select: the launcher refused the arguments");
+  PT_HIPD(e);
+  PT_HIPD(hipDeviceSynchronize());
+  const char* broken = nullptr;
+  PT_HIPD(g_rec.finish(nullptr, &broken));
+  PT_HIPD(g_mask.finish(mask, &broken));
+  PT_HIPD(g_counts.finish(counts, &broken));
+  PT_HIPD(g_list.finish(list, &broken));
+  PT_HIPD(g_words.finish(words, &broken));
+  PT_HIPD(g_sums.finish(block_sums, &broken));
+  if (broken) return pt_fail(PT_EHIP, "pt_debug_adaptive_select: the guard words behind %s were written", broken);
+  return PT_OK;
+}
+
+extern "C" int pt_debug_adaptive_finalize(const uint32_t* rec, const uint32_t* counts, uint32_t tile_pixels, int planar, float* out) {
+  if (!rec || !counts || !out || !tile_pixels) return pt_fail(PT_EINVAL, "pt_debug_adaptive_finalize: NULL argument or an empty tile");
+  const size_t tp = tile_pixels;
+  GuardedArray g_rec, g_counts, g_out;
+  PT_HIPD(g_rec.create("rec", rec, (size_t)PT_CHUNK_WORDS * tp * sizeof(uint32_t)));
+  PT_HIPD(g_counts.create("counts", counts, tp * sizeof(uint32_t)));
+  PT_HIPD(g_out.create("out", nullptr, tp * 14 * sizeof(float)));
+  PT_HIPD(pt_launch_adaptive_finalize((const uint32_t*)g_rec.d, (const uint32_t*)g_counts.d, (float*)g_out.d, tile_pixels, planar != 0, nullptr));
+  PT_HIPD(hipDeviceSynchronize());
+  const char* broken = nullptr;
+  PT_HIPD(g_rec.finish(nullptr, &broken));
+  PT_HIPD(g_counts.finish(nullptr, &broken));
+  PT_HIPD(g_out.finish(out, &broken));
+  if (broken) return pt_fail(PT_EHIP, "pt_debug_adaptive_finalize: the guard words behind %s were written", broken);
+  return PT_OK;
+}
+#endif

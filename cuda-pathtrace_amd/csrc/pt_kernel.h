@@ -283,12 +283,17 @@ struct AdaptiveRule {
   int32_t min_samples;         // the rule is evaluated from this count on
   int32_t radius;              // dilation window (2 radius + 1)^2, clipped to the tile
 };
+// the rule of a session's options: the ONE conversion (pt_progressive_set_adaptive and the lab library's pt_debug_adaptive_select)
+inline AdaptiveRule pt_adaptive_rule(const pt_adaptive_opts& o) {
+  return AdaptiveRule{(double)o.tolerance, (double)o.floor, o.min_samples, o.radius};
+}
 #define PT_ADAPTIVE_BLOCK 256
 #define PT_ADAPTIVE_MAX_RADIUS 4
 // Decide the pass's active set and list.  n = samples every active pixel holds now, n_end = after the pass.  mode: 0 = evaluate
 // the rule (when n >= min_samples) on the pixels of mask bit 0, 1 = take mask bit 0 as it is (a forced set), 2 = every pixel
 // (a session's first pass).  Active pixels' counts become n_end.  peek: only the decision and its size (words[0]); the list,
-// the counts, mask bit 0 and the maximum count stay as they are.
+// the counts, mask bit 0 and the maximum count stay as they are (mode 2 sets mask bit 0 of every pixel even so: that is the
+// mode's set; no session peeks before its first pass).  Mask bits above bit 0 are scratch: every call rewrites them.
 hipError_t pt_launch_adaptive_select(const AdaptiveState& s, const AdaptiveRule& rule, const uint32_t* rec, uint32_t tile_pixels,
                                      int width, int n, int n_end, int mode, bool peek, hipStream_t stream);
 // The frame of every tile pixel at its own count from the record, in the renderer's layout (frame_values, pt_scene_lds.h)

@@ -532,7 +532,9 @@ int pt_progressive_destroy(pt_progressive* p);
  *    c0..c2), the pixel is CONVERGED when (a) no sample hit anything (depth 0), or (b) every one of its n samples scored
  *    (the colour variance skips escaped paths, pathtrace.cu:157-161) and
  *        (double)c10 <= ((double)tol * (double)tol * (double)n) * (m * m),  m = max((double)lum, (double)floor),
- *    evaluated left to right in double.  Because of the "every sample scored" condition, a pixel where some path escapes
+ *    evaluated left to right in double, with max as C's (double)lum > (double)floor ? lum : floor.  Two consequences for
+ *    values that are not numbers: a NaN luminance takes the floor (the comparison is false), and a NaN variance never
+ *    converges (it compares false against every threshold).  Because of the "every sample scored" condition, a pixel where some path escapes
  *    keeps sampling: adaptivity mostly helps closed scenes.
  *  - Dilation: a pixel stays active if it was active and an active, unconverged pixel lies in the (2 radius + 1)^2 window
  *    around it, clipped to the renderer's tile.

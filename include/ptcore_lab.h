@@ -148,6 +148,22 @@ int pt_debug_progressive_record(pt_progressive* p, uint32_t* host);
 /* Adaptive sessions after their first pass: the next pass renders exactly the pixels whose byte in host_mask (one per tile
  * pixel) is non-zero, without the rule.  The set may only shrink: a pixel the last pass did not render is PT_EINVAL. */
 int pt_debug_progressive_set_active(pt_progressive* p, const uint8_t* host_mask);
+/* The selection in front of an adaptive pass (csrc/pt_adaptive.hip: classify, decide, scan, scatter) on a state the caller builds,
+ * without a session or a renderer.  All pointers are HOST pointers; synchronous.  rec = [PT_CHUNK_WORDS (26)][tile_pixels] words
+ * laid out like a session's record; mask, counts, list = tile_pixels entries each, words = {list length, maximum count}.  These
+ * four go up to the device before the launch and come back afterwards whatever `peek` says, so a caller sees what a call left
+ * alone and can chain calls by passing the output back in.  block_sums (may be NULL) receives the exclusive prefix of the
+ * active pixels per 256-pixel block.  n = the count every active pixel holds, n_end > n = the count after the pass; mode 0 =
+ * the rule on the pixels of mask bit 0, 1 = mask bit 0 as it is, 2 = every pixel; the rule is made from opts exactly as
+ * pt_progressive_set_adaptive makes it (opts itself is not validated beyond the radius).  Every device array is an allocation
+ * of its own, filled with a sentinel before the upload and followed by 64 guard words (the mask: 256 bytes): a guard that
+ * changed is PT_EHIP with the array's name in the message. */
+int pt_debug_adaptive_select(const uint32_t* rec, uint32_t tile_pixels, int width, int n, int n_end, int mode, int peek,
+                             const pt_adaptive_opts* opts, uint8_t* mask, uint32_t* counts, uint32_t* list, uint32_t words[2],
+                             uint32_t* block_sums);
+/* The frame after an adaptive pass (adaptive_finalize_kernel): out = tile_pixels x 14 floats, [pixel][channel] or, planar != 0,
+ * [channel][pixel], each pixel at counts[pixel] from rec.  Host pointers, synchronous, guarded like the call above. */
+int pt_debug_adaptive_finalize(const uint32_t* rec, const uint32_t* counts, uint32_t tile_pixels, int planar, float* out);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,13 @@ def test_decision_model_for_each_radius(lab, oracle, gpu, radius):
     run_adaptive(lab, oracle, 96, 64, lab.scene_cornell(), [4, 2, 2, 3, 3], 5, 0, "cornell", q=0.5, radius=radius, min_samples=4)
 
 
+def test_scan_past_one_wave_in_a_session(lab, oracle, gpu):
+    """131 x 127 = 16637 pixels = 65 blocks of 256: the scan's second wave on the product's own one-allocation state, and a real
+    pass over the list it made (tests/test_adaptive_exact_gpu.py holds the list itself, up to 2052 blocks)."""
+    counts, _ = run_adaptive(lab, oracle, 131, 127, lab.scene_cornell(), [4, 4, 4], 5, 0, "cornell", radius=2)
+    assert len(np.unique(counts)) >= 2
+
+
 @pytest.mark.parametrize("rng", [0, 1], ids=["xorwow", "philox"])
 def test_every_variant_explicitly_and_automatically(lab, oracle, gpu, rng):
     """Random closed scenes of 40 and 300 spheres, 64 x 48: variants 6, 10, 13, 14 and the automatic choice."""

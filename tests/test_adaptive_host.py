@@ -129,3 +129,22 @@ def test_next_active_is_monotone_and_waits_for_min_samples():
         assert not (nxt & ~active).any()
     assert (next_active(active, f, full, full, n, 10.0, 0.05, n + 1, 1) == active).all()
     assert not next_active(active, f, full, full, n, 10.0, 0.05, n, 1).any()
+
+
+def test_nan_luminance_takes_the_floor_and_nan_variance_never_converges():
+    """The header's max is C's lum > floor ? lum : floor: a NaN luminance compares false and takes the floor; a NaN variance
+    compares false against any threshold (include/ptcore.h, EXACTNESS.md A.20)."""
+    n = 8
+    full = np.full((1, 4), n)
+    f = _frame(1, 4)
+    f[0, 0, 0:3] = np.nan                      # NaN colour, variance 0: converged at the floor's threshold
+    f[0, 1, 1] = np.nan                        # one NaN channel is a NaN luminance too
+    f[0, 1, 10] = np.float32(0.5 * 0.5 * n * 2.0 * 2.0)      # exactly T(floor = 2): converged
+    f[0, 2, 0:3] = np.nan
+    f[0, 2, 10] = np.nextafter(np.float32(0.5 * 0.5 * n * 2.0 * 2.0), np.float32(np.inf))  # one float above T(floor): not
+    f[0, 3, 10] = np.nan                       # NaN variance: never, whatever the tolerance
+    assert converged(f, full, full, n, 0.5, 2.0).tolist() == [[True, True, False, False]]
+    assert not converged(f, full, full, n, 1e30, 2.0)[0, 3]
+    # and the sets: the NaN-variance pixel stays active, the NaN-colour pixel with variance 0 stops
+    nxt = next_active(np.ones((1, 4), bool), f, full, full, n, 0.5, 2.0, 2, 0)
+    assert nxt.tolist() == [[False, False, True, True]]
