@@ -176,6 +176,18 @@ ABI = {
     "pt_temporal_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _fp]),
     "pt_temporal_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _vp]),
     "pt_temporal_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _fp]),
+    "pt_tonemap_opts_default": (None, [_vp]),
+    "pt_tonemap_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "pt_tonemap_destroy": (ctypes.c_int, [_vp]),
+    "pt_tonemap_reset": (ctypes.c_int, [_vp]),
+    "pt_tonemap_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_tonemap_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_tonemap_srgb_table": (ctypes.c_int, [_fp]),
+    "pt_tonemap_enqueue": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
+    "pt_tonemap_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _fp]),
+    "pt_tonemap_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp]),
+    "pt_tonemap_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _fp]),
+    "pt_tonemap_exposure": (ctypes.c_int, [_vp, _fp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -1283,3 +1295,120 @@ def accumulate_frames(frames, samples, bases, eyes, temporal=None, **opts):
         d_counts.free()
         if temporal is None:
             ta.destroy()
+
+
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+ENCODE_SRGB, ENCODE_LINEAR = 0, 1
+TONEMAP_CURVES = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
+TONEMAP_ENCODES = {"srgb": ENCODE_SRGB, "linear": ENCODE_LINEAR}
+
+
+class TonemapOpts(ctypes.Structure):
+    """pt_tonemap_opts (include/ptcore.h)."""
+    _fields_ = [("curve", ctypes.c_int32), ("encode", ctypes.c_int32), ("exposure", ctypes.c_float), ("key", ctypes.c_float),
+                ("white", ctypes.c_float), ("adapt", ctypes.c_float), ("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+def tonemap_srgb_table():
+    """pt_tonemap_srgb_table: the 255 float32 thresholds of the sRGB codes 1 .. 255; host only."""
+    out = np.zeros(255, dtype=np.float32)
+    check(lib.pt_tonemap_srgb_table(out.ctypes.data_as(_fp)))
+    return out
+
+
+class Tonemap:
+    """ctypes view of pt_tonemap: the tone-mapping session for width x height images (DENOISER.md, "Tone mapping").  A call reads
+    a device image of linear radiance [H][W][pixel_stride] (14: a frame, 3: a filter's or denoiser's d_rgb; never written) and
+    writes device RGBA8 uint32 [H][W].  curve: "clamp" | "reinhard" | "aces"; encode: "srgb" | "linear"; exposure: "auto"
+    (metered on the device and adapted from frame to frame at rate `adapt`) or a number > 0."""
+
+    def __init__(self, width, height, curve="aces", encode="srgb", exposure="auto", key=0.18, white=4.0, adapt=1.0, max_frames=1):
+        self.handle = None
+        if curve not in TONEMAP_CURVES:
+            raise ValueError(f"curve {curve!r}: one of {sorted(TONEMAP_CURVES)}")
+        if encode not in TONEMAP_ENCODES:
+            raise ValueError(f"encode {encode!r}: one of {sorted(TONEMAP_ENCODES)}")
+        if exposure != "auto" and float(exposure) == 0.0:
+            raise ValueError("exposure 0: 'auto' or a number > 0")
+        opts = TonemapOpts(curve=TONEMAP_CURVES[curve], encode=TONEMAP_ENCODES[encode], exposure=0.0 if exposure == "auto" else float(exposure),
+                           key=key, white=white, adapt=adapt, max_frames=max_frames)
+        h = _vp()
+        check(lib.pt_tonemap_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height = width, height
+        self.max_frames = max_frames
+
+    def reserve_frames(self, n):
+        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
+        check(lib.pt_tonemap_reserve_frames(self.handle, n))
+        self.max_frames = max(self.max_frames, n)
+
+    def memory(self):
+        """{"workspace": bytes of the table, the state and the partial sums of all max_frames frames}."""
+        b = ctypes.c_uint64(0)
+        check(lib.pt_tonemap_workspace_bytes(self.handle, ctypes.byref(b)))
+        return {"workspace": int(b.value)}
+
+    def reset(self):
+        """Forget the exposure: the next frame's exposure is its own target."""
+        check(lib.pt_tonemap_reset(self.handle))
+
+    def exposure(self):
+        """Synchronous: the exposure of the last frame (float32)."""
+        e = ctypes.c_float(0)
+        check(lib.pt_tonemap_exposure(self.handle, ctypes.byref(e)))
+        return np.float32(e.value)
+
+    def enqueue(self, d_src, d_rgba8, pixel_stride=CHANNELS, stream=None):
+        check(lib.pt_tonemap_enqueue(self.handle, d_src, pixel_stride, d_rgba8, stream))
+
+    def run(self, d_src, d_rgba8, pixel_stride=CHANNELS):
+        """Synchronous; returns device-event milliseconds."""
+        ms = ctypes.c_float(0)
+        check(lib.pt_tonemap_run(self.handle, d_src, pixel_stride, d_rgba8, ctypes.byref(ms)))
+        return ms.value
+
+    def _strides(self, pixel_stride, src_stride_floats, dst_stride_pixels):
+        px = self.width * self.height
+        return (px * pixel_stride if src_stride_floats is None else src_stride_floats, px if dst_stride_pixels is None else dst_stride_pixels)
+
+    def enqueue_frames(self, d_src, n, d_rgba8, pixel_stride=CHANNELS, src_stride_floats=None, dst_stride_pixels=None, stream=None):
+        """Asynchronous; n images at d_src + k * src_stride_floats (default: packed) to d_rgba8 + k * dst_stride_pixels, in order:
+        bit for bit n single enqueues, the adaptation included."""
+        ss, ds = self._strides(pixel_stride, src_stride_floats, dst_stride_pixels)
+        check(lib.pt_tonemap_enqueue_frames(self.handle, n, d_src, ss, pixel_stride, d_rgba8, ds, stream))
+
+    def run_frames(self, d_src, n, d_rgba8, pixel_stride=CHANNELS, src_stride_floats=None, dst_stride_pixels=None):
+        """Synchronous enqueue_frames; returns device-event milliseconds."""
+        ss, ds = self._strides(pixel_stride, src_stride_floats, dst_stride_pixels)
+        ms = ctypes.c_float(0)
+        check(lib.pt_tonemap_run_frames(self.handle, n, d_src, ss, pixel_stride, d_rgba8, ds, ctypes.byref(ms)))
+        return ms.value
+
+    def destroy(self):
+        if self.handle:
+            check(lib.pt_tonemap_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def tonemap_frame(frame_or_rgb, tonemap=None, **opts):
+    """Convenience for tests: upload a host [H][W][C] image (C = 14: a frame, 3: an rgb image, anything in 3 .. 64), tone-map it
+    on the GPU, download.  Returns uint8 [H][W][4].  opts: of the Tonemap made here (curve, encode, exposure, ...)."""
+    img = np.ascontiguousarray(frame_or_rgb, dtype=np.float32)
+    h, w, c = img.shape
+    tm = tonemap or Tonemap(w, h, **opts)
+    d_src, d_out = DeviceBuffer(img.nbytes).upload(img), DeviceBuffer(h * w * 4)
+    try:
+        tm.run(d_src.ptr, d_out.ptr, pixel_stride=c)
+        return d_out.download(np.uint8, (h, w, 4))
+    finally:
+        d_src.free()
+        d_out.free()
+        if tonemap is None:
+            tm.destroy()

@@ -18,7 +18,10 @@
 // --filter (the weights-free denoiser, FeatureFilter / pt_filter_*: every frame of the headless loop and every progressive pass
 // is filtered in place after Render(), where -d would run the network; the saved EXR and bitmaps hold the filtered frame),
 // --temporal (with --frames / --poses: TemporalAccumulator / pt_temporal_* accumulates every frame of the headless loop in place
-// after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts).
+// after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts),
+// --tonemap CURVE (ToneMapper / pt_tonemap_*: every frame of the headless loop and every progressive pass goes through the
+// session after --temporal, --filter and -d, so that --tonemap-adapt acts as eye adaptation; the last frame's sRGB picture is
+// written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,6 +44,7 @@
 #include "Renderer.h"
 #include "Scene.h"
 #include "TemporalAccumulator.h"
+#include "ToneMapper.h"
 
 static void usage() {
   std::cout << "cuda-pathtrace" << std::endl
@@ -79,6 +83,12 @@ static void usage() {
                "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
                "  --temporal                    with --frames / --poses: reproject and accumulate every frame over the last ones\n"
                "  --temporal-cap arg            with --temporal: cap of the accumulated history in samples, >= 1 (default 256)\n"
+               "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
+               "  --exposure arg                with --tonemap: auto (default, metered on the device) or a number > 0\n"
+               "  --tonemap-key arg             with --tonemap: luminance the metered mean is mapped to (default 0.18)\n"
+               "  --tonemap-white arg           with --tonemap reinhard: luminance that maps to white (default 4)\n"
+               "  --tonemap-adapt arg           with --tonemap: share of the way to the metered exposure per frame, (0, 1] (default 1)\n"
+               "  --tonemap-encode arg          with --tonemap: srgb (default) | linear\n"
             << std::endl;
 }
 
@@ -112,6 +122,12 @@ int main(int argc, const char** argv) {
   // --temporal: the temporal accumulator (pt_temporal_*) in place after every Render() of the frame loop
   bool temporal = false, temporalCapGiven = false;
   double temporalCap = 256.0;
+  // --tonemap CURVE: the tone-mapping session (pt_tonemap_*) after every other stage of a frame
+  std::string tonemapCurve, tonemapExposure, tonemapEncode;
+  bool tonemapGiven = false;
+  const char* tonemapOption = NULL;  // the first --exposure / --tonemap-* option seen
+  double tonemapKey = 0.18, tonemapWhite = 4.0, tonemapAdapt = 1.0;
+  bool tonemapKeyGiven = false, tonemapWhiteGiven = false, tonemapAdaptGiven = false;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -152,6 +168,12 @@ int main(int argc, const char** argv) {
     else if (a == "--filter-sigma") { filterSigma = value("--filter-sigma"); filterSigmaGiven = true; }
     else if (a == "--temporal") temporal = true;
     else if (a == "--temporal-cap") { temporalCap = atof(value("--temporal-cap")); temporalCapGiven = true; }
+    else if (a == "--tonemap") { tonemapCurve = value("--tonemap"); tonemapGiven = true; }
+    else if (a == "--exposure") { tonemapExposure = value("--exposure"); if (!tonemapOption) tonemapOption = "--exposure"; }
+    else if (a == "--tonemap-key") { tonemapKey = atof(value("--tonemap-key")); tonemapKeyGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-key"; }
+    else if (a == "--tonemap-white") { tonemapWhite = atof(value("--tonemap-white")); tonemapWhiteGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-white"; }
+    else if (a == "--tonemap-adapt") { tonemapAdapt = atof(value("--tonemap-adapt")); tonemapAdaptGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-adapt"; }
+    else if (a == "--tonemap-encode") { tonemapEncode = value("--tonemap-encode"); if (!tonemapOption) tonemapOption = "--tonemap-encode"; }
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -267,6 +289,55 @@ int main(int argc, const char** argv) {
     }
     temporalOpts.history_cap = (float)temporalCap;
   }
+  pt_tonemap_opts tonemapOpts;
+  pt_tonemap_opts_default(&tonemapOpts);
+  if (tonemapOption && !tonemapGiven) {  // (before any device is touched)
+    std::cerr << "ERROR: " << tonemapOption << " needs --tonemap: it sets an option of the tone mapper" << std::endl;
+    return 1;
+  }
+  if (tonemapGiven) {
+    if (batch) {
+      std::cerr << "ERROR: --tonemap cannot be combined with --batch: the tone mapper runs after every frame of the loop" << std::endl;
+      return 1;
+    }
+    if (tonemapCurve == "clamp") tonemapOpts.curve = PT_TONEMAP_CLAMP;
+    else if (tonemapCurve == "reinhard") tonemapOpts.curve = PT_TONEMAP_REINHARD;
+    else if (tonemapCurve == "aces") tonemapOpts.curve = PT_TONEMAP_ACES;
+    else {
+      std::cerr << "ERROR: --tonemap '" << tonemapCurve << "': clamp, reinhard or aces" << std::endl;
+      return 1;
+    }
+    if (!tonemapEncode.empty()) {
+      if (tonemapEncode == "srgb") tonemapOpts.encode = PT_ENCODE_SRGB;
+      else if (tonemapEncode == "linear") tonemapOpts.encode = PT_ENCODE_LINEAR;
+      else {
+        std::cerr << "ERROR: --tonemap-encode '" << tonemapEncode << "': srgb or linear" << std::endl;
+        return 1;
+      }
+    }
+    if (!tonemapExposure.empty() && tonemapExposure != "auto") {
+      char* end = NULL;
+      const double e = strtod(tonemapExposure.c_str(), &end);
+      if (end == tonemapExposure.c_str() || *end != '\0' || !(e > 0.0) || !(e <= 3.4028234663852886e38) || (float)e == 0.0f) {
+        std::cerr << "ERROR: --exposure '" << tonemapExposure << "': auto or a finite number > 0" << std::endl;
+        return 1;
+      }
+      tonemapOpts.exposure = (float)e;
+    }
+    if (tonemapKeyGiven && (!(tonemapKey > 0.0) || !(tonemapKey <= 3.4028234663852886e38) || (float)tonemapKey == 0.0f)) {
+      std::cerr << "ERROR: --tonemap-key " << tonemapKey << ": a finite luminance > 0" << std::endl;
+      return 1;
+    }
+    if (tonemapWhiteGiven && !(tonemapWhite >= 1e-18 && tonemapWhite <= 1e18)) {
+      std::cerr << "ERROR: --tonemap-white " << tonemapWhite << ": a luminance in 1e-18 .. 1e18" << std::endl;
+      return 1;
+    }
+    if (tonemapAdaptGiven && !(tonemapAdapt > 0.0 && tonemapAdapt <= 1.0 && (float)tonemapAdapt > 0.0f)) {
+      std::cerr << "ERROR: --tonemap-adapt " << tonemapAdapt << ": a rate in (0, 1]" << std::endl;
+      return 1;
+    }
+    tonemapOpts.key = (float)tonemapKey, tonemapOpts.white = (float)tonemapWhite, tonemapOpts.adapt = (float)tonemapAdapt;
+  }
   if ((adaptiveGiven || adaptiveMinGiven || adaptiveRadiusGiven) && !progressiveGiven) {  // (before any device is touched)
     std::cerr << "ERROR: " << (adaptiveGiven ? "--adaptive" : adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius")
               << " needs --progressive: adaptive sampling refines a progressive session" << std::endl;
@@ -350,12 +421,15 @@ int main(int argc, const char** argv) {
   TemporalAccumulator* accumulator = temporal ? new TemporalAccumulator(width, height, temporalOpts) : NULL;
   unsigned int* d_temporalCounts = NULL;
   if (accumulator && filter) gpuErrchk(pt_malloc((void**)&d_temporalCounts, (size_t)width * height * sizeof(unsigned int)));
-  float denoiseTime = 0.0f, filterTime = 0.0f, temporalTime = 0.0f;
+  // --tonemap: likewise; it reads the frame the other stages left and writes its own RGBA8 image
+  ToneMapper* mapper = tonemapGiven ? new ToneMapper(width, height, tonemapOpts) : NULL;
+  float denoiseTime = 0.0f, filterTime = 0.0f, temporalTime = 0.0f, tonemapTime = 0.0f;
   auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
     if (accumulator) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, d_temporalCounts);
     if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
     if (filter) filterTime = filter->Filter(b, samplesPerPixel, d_temporalCounts);
+    if (mapper) tonemapTime = mapper->Map(b);
     return ms;
   };
   Camera camera(glm::vec3(cameraPos[0], cameraPos[1], cameraPos[2]), cameraView[0], cameraView[1]);  // main.cu:128 verbatim
@@ -435,6 +509,7 @@ int main(int argc, const char** argv) {
       if (adaptiveGiven) session.Counts(d_counts);
       // --filter: with the session's count so far; under --adaptive with every pixel's own count
       if (filter) filterTime = filter->Filter(d_buffer, (int)session.Samples(), d_counts);
+      if (mapper) tonemapTime = mapper->Map(d_buffer);
       if (adaptiveGiven) {
         gpuErrchk(pt_memcpy_d2h(counts.data(), d_counts, counts.size() * sizeof(unsigned int)));
         double spp = 0;
@@ -459,6 +534,7 @@ int main(int argc, const char** argv) {
   if (accumulator) std::cout << "Temporal accumulation completed in " << temporalTime << "ms" << std::endl;
   if (net) std::cout << "Denoise completed in " << denoiseTime << "ms" << std::endl;
   if (filter) std::cout << "Filter completed in " << filterTime << "ms" << std::endl;
+  if (mapper) std::cout << "Tone mapping completed in " << tonemapTime << "ms (exposure " << mapper->Exposure() << ")" << std::endl;
   if (tiled) {
     std::cout << "Tile kernel times:";
     for (int g = 0; g < gpus; g++) std::cout << " " << tiled->TileKernelMs(g) << "ms";
@@ -488,6 +564,10 @@ int main(int argc, const char** argv) {
     }
     fclose(f);
   }
+  if (mapper && !mapper->SavePPM(outputName + "_tm.ppm")) {
+    std::cerr << "ERROR: cannot write " << outputName << "_tm.ppm" << std::endl;
+    return 1;
+  }
   // save results (main.cu:186-192)
   OutputBuffer buffer(width, height);
   buffer.AllocateCPU();
@@ -498,6 +578,7 @@ int main(int argc, const char** argv) {
   delete net;
   delete filter;
   delete accumulator;
+  delete mapper;
   if (d_temporalCounts) (void)pt_free(d_temporalCounts);
   delete single;
   delete tiled;

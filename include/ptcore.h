@@ -482,6 +482,89 @@ int pt_temporal_enqueue_frames(pt_temporal* t, int n_frames, float* d_frames, si
 int pt_temporal_run_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
                            const float* eyes, int samples, uint32_t* d_counts, float* ms_out);
 
+/* ---- tone mapping: metered exposure, a filmic curve and sRGB bytes ---------------------------- */
+/* The stage between a frame of linear radiance and a picture; no counterpart in the reference, whose display path is the clamp
+ * of pt_display_pack.  A session belongs to one frame size and keeps ONE float on the device, the exposure e, so no call
+ * synchronises with the host.  EXACT code: every operation below is a float32 add, multiply, divide or compare (no
+ * contraction), an integer sum or a table lookup, and the kernels equal the float32 restatement (tests/tonemap_model.py) bit
+ * for bit; the reductions are sums of integers, so their order cannot change a bit.  DENOISER.md, "Tone mapping", says the same.
+ *   input     device floats [height][width][pixel_stride], pixel_stride in 3 .. 64, colour c in the first three floats of a
+ *             pixel: stride 14 is a frame, stride 3 the d_rgb of pt_filter_* / pt_denoiser_*.  The input is never written.
+ *   output    device uint32 [height][width], r | g << 8 | b << 16 | 255 << 24.
+ *   lum(c)    (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z, left to right in float32.
+ *   1 meter   (only with exposure = 0, "auto")  a pixel is metered when the bit pattern of L = lum(c) lies in [bits(2^-20),
+ *             0x7F7FFFFF], that is L is finite and >= 2^-20: NaN, inf, zero, negative and black sky pixels do not count.
+ *             S = the sum of the metered pixels' bit patterns as uint64, K = their number;  m = S / K as an integer division;
+ *             Lavg = the float whose bits are (uint32)m;  target = key / Lavg, a float32 divide.  With K = 0 target is the
+ *             previous exposure, or 1 with no history.  (Averaging bit patterns averages a piecewise-linear log2, so Lavg is
+ *             a geometric mean: log2 Lavg lies within 0.0861 of the true mean log2, +-6 % in exposure, for a sum that is exact
+ *             in any order.  2^26 pixels x 2^31 stays below 2^64.)
+ *   2 adapt   first frame, first after pt_tonemap_reset, or adapt = 1:  e = target, the same bits;  otherwise d = target - e;
+ *             e = e + adapt d, two float32 roundings.  With a fixed exposure e is the option and neither meter nor adapt runs.
+ *   3 map     per channel  x = c e;  x = x > 0 ? x : 0 (NaN becomes 0);  x = x < 65504 ? x : 65504;
+ *             PT_TONEMAP_CLAMP     y = x
+ *             PT_TONEMAP_REINHARD  Lx = lum(x);  s = (1 + Lx / (white white)) / (1 + Lx);  y = x s   (on luminance: hue is kept)
+ *             PT_TONEMAP_ACES      y = (x (2.51f x + 0.03f)) / (x (2.43f x + 0.59f) + 0.14f)         (Narkowicz's rational fit)
+ *             then y = y < 1 ? y : 1 (NaN becomes 1).
+ *   4 encode  PT_ENCODE_SRGB    code = the number of k in 1 .. 255 with T[k] <= y, where T[k] is the float32 nearest to
+ *                               u <= 0.04045 ? u / 12.92 : pow((u + 0.055) / 1.055, 2.4) formed in double at u = (k - 0.5) / 255:
+ *                               the correctly rounded 8-bit sRGB code.  The table is built once on the host, kept in LDS and
+ *                               searched in eight steps; there is no powf on the device.
+ *             PT_ENCODE_LINEAR  (unsigned char)((double)y * 255.0), the display packer's own line.
+ * With PT_TONEMAP_CLAMP, exposure 1 and PT_ENCODE_LINEAR the three colour bytes are exactly those of pt_display_pack.  There is
+ * no dithering.  Launches: a fixed exposure is ONE launch per call; auto is three (meter: per-workgroup partial (S, K) into the
+ * workspace; adapt: one workgroup adds them and carries e; map).  No float atomics, no memset, no host synchronisation.
+ * Workspace: 1040 bytes (table, state) + per frame of a group 16 bytes per 256 pixels + 4 (pt_tonemap_workspace_bytes).  One
+ * session's calls share its workspace and state and are ordered by the stream: do not run two of them concurrently. */
+#define PT_TONEMAP_CLAMP 0
+#define PT_TONEMAP_REINHARD 1
+#define PT_TONEMAP_ACES 2
+#define PT_ENCODE_SRGB 0
+#define PT_ENCODE_LINEAR 1
+typedef struct pt_tonemap_opts {
+  int32_t curve;       /* PT_TONEMAP_CLAMP, _REINHARD or _ACES (default ACES)                                    */
+  int32_t encode;      /* PT_ENCODE_SRGB (default) or PT_ENCODE_LINEAR                                           */
+  float exposure;      /* 0 = auto (default): metered and adapted on the device; else finite and > 0: fixed      */
+  float key;           /* auto: the luminance the geometric mean is mapped to, finite and > 0 (default 0.18)     */
+  float white;         /* Reinhard: the luminance that maps to 1, 1e-18 .. 1e18 (default 4)                      */
+  float adapt;         /* auto: share of the way to the target taken per frame, (0, 1] (default 1 = at once)     */
+  int32_t max_frames;  /* frames per group, >= 1 (default 1)                                                     */
+  int32_t reserved[2]; /* must be 0                                                                              */
+} pt_tonemap_opts;
+typedef struct pt_tonemap pt_tonemap; /* opaque: the options, the table, the exposure and the partials of one frame size */
+void pt_tonemap_opts_default(pt_tonemap_opts* opts);
+/* opts may be NULL (= defaults).  Every option and size is validated BEFORE a device is touched (the size limits are
+ * pt_filter_create's, max_frames' those of pt_filter_reserve_frames); a bad value is PT_EINVAL naming the argument.  Allocates
+ * the workspace on the current device. */
+int pt_tonemap_create(int width, int height, const pt_tonemap_opts* opts, pt_tonemap** out);
+int pt_tonemap_destroy(pt_tonemap* t);
+/* Forgets the exposure: the next frame's exposure is its own target. */
+int pt_tonemap_reset(pt_tonemap* t);
+int pt_tonemap_workspace_bytes(const pt_tonemap* t, uint64_t* bytes);
+/* Grows the workspace for groups of up to max_frames frames, with pt_filter_reserve_frames' limits and rules; the exposure is kept. */
+int pt_tonemap_reserve_frames(pt_tonemap* t, int max_frames);
+/* Host only: out[k - 1] = T[k] of the encode step, k = 1 .. 255. */
+int pt_tonemap_srgb_table(float out[255]);
+/* Maps the device image d_src to d_rgba8, asynchronous on hip_stream (NULL = default stream).  A null session, source or
+ * destination, or a pixel_stride outside 3 .. 64, is PT_EINVAL naming the argument; nothing is launched and the session keeps
+ * its state. */
+int pt_tonemap_enqueue(pt_tonemap* t, const float* d_src, int pixel_stride, uint32_t* d_rgba8, void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around it. */
+int pt_tonemap_run(pt_tonemap* t, const float* d_src, int pixel_stride, uint32_t* d_rgba8, float* ms_out);
+/* n frames in order, bit for bit what
+ *   for k in 0 .. n-1: pt_tonemap_enqueue(t, d_src + k * src_stride_floats, pixel_stride, d_rgba8 + k * dst_stride_pixels, s)
+ * does, the adaptation carried from frame to frame included.  A group of up to max_frames frames goes out in three launches
+ * (one with a fixed exposure): meter all its frames, one workgroup adapts them in order, map all its frames.  Strides may leave
+ * gaps (src_stride_floats >= width x height x pixel_stride, dst_stride_pixels >= width x height).  n_frames < 1, a stride too
+ * small, and everything pt_tonemap_enqueue refuses is PT_EINVAL and nothing is launched. */
+int pt_tonemap_enqueue_frames(pt_tonemap* t, int n_frames, const float* d_src, size_t src_stride_floats, int pixel_stride,
+                              uint32_t* d_rgba8, size_t dst_stride_pixels, void* hip_stream);
+int pt_tonemap_run_frames(pt_tonemap* t, int n_frames, const float* d_src, size_t src_stride_floats, int pixel_stride,
+                          uint32_t* d_rgba8, size_t dst_stride_pixels, float* ms_out);
+/* Synchronous (it waits for the device): *out = the e of the last frame; the option with a fixed exposure; 1 before the first
+ * frame and after a reset. */
+int pt_tonemap_exposure(pt_tonemap* t, float* out);
+
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
  * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.
