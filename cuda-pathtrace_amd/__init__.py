@@ -11,6 +11,7 @@ The directory name has a hyphen (it is fixed by the project layout), so import i
 `load_package()` in __graft_entry__.py / tests/conftest.py, which registers it as
 `cuda_pathtrace_amd`.
 """
+import contextlib
 import ctypes
 import os
 
@@ -408,6 +409,72 @@ class DeviceBuffer:
             pass
 
 
+class _Session:
+    """What every ctypes view of a native session shares: the handle, its destroy symbol (`_destroy`, looked up in the loaded
+    library), destroy / __del__, and the timed call."""
+    handle = None  # (also when __init__ raised before the create)
+    _destroy = None
+
+    def destroy(self):
+        if self.handle:
+            check(getattr(lib, self._destroy)(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _timed(self, fn, *args):
+        """fn(handle, *args, &ms): a synchronous entry point whose last argument receives the milliseconds; returns them."""
+        ms = ctypes.c_float(0)
+        check(fn(self.handle, *args, ctypes.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _lab(name):
+        if not IS_LAB:
+            raise RuntimeError(f"{name} is a diagnostic of libptcore_lab.so (include/ptcore_lab.h); the product library has none")
+        return getattr(lib, name)
+
+
+class _BatchedStage(_Session):
+    """A post-process session whose workspace holds groups of max_frames frames (`_reserve`: its reserve symbol)."""
+    _reserve = None
+
+    def reserve_frames(self, n):
+        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
+        check(getattr(lib, self._reserve)(self.handle, n))
+        self.max_frames = max(self.max_frames, n)
+
+    def _strides(self, in_stride, out_stride, in_per_pixel=CHANNELS, out_per_pixel=3):
+        """The strides between frames, packed where None: a [H][W][14] frame in, a [H][W][3] image out unless said otherwise."""
+        px = self.width * self.height
+        return px * in_per_pixel if in_stride is None else in_stride, px * out_per_pixel if out_stride is None else out_stride
+
+
+@contextlib.contextmanager
+def _on_device(*specs, owned=None):
+    """The device side of the test conveniences: one DeviceBuffer per spec -- a host array (uploaded), a byte count, or None (no
+    buffer: None) -- all freed on exit, also after an exception; `owned`, a session made for the call, is destroyed with them."""
+    bufs = []
+    try:
+        for spec in specs:
+            bufs.append(None if spec is None else DeviceBuffer(spec) if isinstance(spec, int) else DeviceBuffer(spec.nbytes).upload(spec))
+        yield bufs
+    finally:
+        for b in bufs:
+            if b:
+                b.free()
+        if owned is not None:
+            owned.destroy()
+
+
+def _ptr(buf):
+    return buf.ptr if buf else None
+
+
 def fast_nearest(spheres, rays, specialised=False, last=False, mask=0xFFFFFFFF):
     """Lab library: the fast mode's nearest<> on rays [n][6] = {o, d} (pt_debug_fast_nearest).  Returns (t float32 [n], index
     int32 [n], -1 for a miss)."""
@@ -544,8 +611,9 @@ def upload_scene(spheres):
     return DeviceBuffer(max(spheres.nbytes, 4)).upload(spheres), len(spheres)
 
 
-class Renderer:
+class Renderer(_Session):
     """ctypes view of pt_renderer (the reference's class Renderer, include/Renderer.h)."""
+    _destroy = "pt_renderer_destroy"
 
     def __init__(self, width, height, spp, threads_per_block=8, *, max_bounces=5, rng_mode=RNG_XORWOW, seed=0,
                  row_begin=0, row_end=0, persist_rng=True, variant=None, layout=LAYOUT_INTERLEAVED, fast_math=False, chunks=0):
@@ -576,9 +644,7 @@ class Renderer:
         """Synchronous Render(); returns kernel milliseconds (Renderer.h:55-76)."""
         _, b = _f32(basis, 12)
         _, e = _f32(eye, 3)
-        ms = ctypes.c_float(0)
-        check(lib.pt_renderer_render(self.handle, d_out, d_spheres, n_spheres, b, e, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_renderer_render, d_out, d_spheres, n_spheres, b, e)
 
     def enqueue(self, d_out, d_spheres, n_spheres, basis, eye=DEFAULT_EYE, stream=None):
         _, b = _f32(basis, 12)
@@ -630,21 +696,11 @@ class Renderer:
         check(lib.pt_renderer_kernel_info(self.handle, n_spheres, ctypes.byref(ki)))
         return {f: getattr(ki, f) for f, _ in KernelInfo._fields_ if not f.startswith("reserved")}
 
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_renderer_destroy(self.handle))
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Progressive:
+class Progressive(_Session):
     """ctypes view of pt_progressive: one still frame of `renderer` refined pass by pass (include/ptcore.h).  After a pass that
     leaves the session at n >= 2 samples the frame equals the first Render() of a fresh renderer at n spp, bit for bit."""
+    _destroy = "pt_progressive_destroy"
 
     def __init__(self, renderer):
         h = _vp()
@@ -662,9 +718,7 @@ class Progressive:
         """Synchronous pass; returns device-event milliseconds."""
         _, b = _f32(basis, 12)
         _, e = _f32(eye, 3)
-        ms = ctypes.c_float(0)
-        check(lib.pt_progressive_render(self.handle, spp, d_out, d_spheres, n_spheres, b, e, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_progressive_render, spp, d_out, d_spheres, n_spheres, b, e)
 
     def samples(self):
         n = ctypes.c_int64(0)
@@ -731,17 +785,6 @@ class Progressive:
         m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
         check(lib.pt_debug_progressive_set_active(self.handle, m.ctypes.data))
 
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_progressive_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def debug_adaptive_select(rec, width, n, n_end, mode, peek, tolerance, floor, min_samples, radius, mask, counts, lst, words):
     """Lab library only (pt_debug_adaptive_select): the selection kernels of an adaptive pass on host arrays.  rec [26][pixels]
@@ -771,9 +814,10 @@ def debug_adaptive_finalize(rec, counts, planar):
     return out
 
 
-class MultiRenderer:
+class MultiRenderer(_Session):
     """ctypes view of pt_mgpu: one frame row-tiled over several devices of this process (one host thread per
     device inside the library, RCCL or peer-copy exchange to devices[0])."""
+    _destroy = "pt_mgpu_destroy"
 
     def __init__(self, devices, width, height, spp, threads_per_block=8, *, max_bounces=5, rng_mode=RNG_XORWOW, seed=0,
                  persist_rng=True, variant=None, gather=None, force_exchange=None, timeout_ms=None, fast_math=False, bands=None):
@@ -804,9 +848,7 @@ class MultiRenderer:
         """Synchronous; returns end-to-end wall milliseconds (render + exchange)."""
         _, b = _f32(basis, 12)
         _, e = _f32(eye, 3)
-        ms = ctypes.c_float(0)
-        check(lib.pt_mgpu_render(self.handle, d_out, d_spheres, n_spheres, b, e, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_mgpu_render, d_out, d_spheres, n_spheres, b, e)
 
     def tile(self, rank):
         dev, rb, re_, ms = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_float(0)
@@ -823,17 +865,6 @@ class MultiRenderer:
         buf = ctypes.create_string_buffer(128)
         check(lib.pt_mgpu_backend(self.handle, buf, 128))
         return buf.value.decode()
-
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_mgpu_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, **opts):
@@ -890,14 +921,14 @@ def denoise_precision(precision):
     return _DENOISE_PRECISIONS[precision]
 
 
-class Denoiser:
+class Denoiser(_BatchedStage):
     """ctypes view of pt_denoiser: the reference's DenoiseCNN step (train.py:test, main.cu:146-152) for width x height frames.
     weights: a PTDN file path, its bytes, or a reference-keyed state_dict.  max_frames > 1 reserves the workspace for batches
     of that many frames per group (pt_denoiser_reserve_frames).  precision: "float32" (the default, exact to fp32 rounding)
     or "half" (fp16 operands and storage, fp32 accumulation: the toleranced mode of DENOISER.md, "Half precision")."""
+    _destroy, _reserve = "pt_denoiser_destroy", "pt_denoiser_reserve_frames"
 
     def __init__(self, width, height, weights, max_frames=1, precision="float32"):
-        self.handle = None
         opts = DenoiserOpts(precision=denoise_precision(precision), max_frames=max_frames)
         blob = denoiser_weights_bytes(weights)
         h = _vp()
@@ -913,16 +944,6 @@ class Denoiser:
         check(lib.pt_denoiser_precision(self.handle, ctypes.byref(v)))
         return {n: k for k, n in _DENOISE_PRECISIONS.items()}[v.value]
 
-    def reserve_frames(self, n):
-        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
-        check(lib.pt_denoiser_reserve_frames(self.handle, n))
-        self.max_frames = max(self.max_frames, n)
-
-    def _strides(self, frame_stride_floats, rgb_stride_floats):
-        px = self.width * self.height
-        return (px * CHANNELS if frame_stride_floats is None else frame_stride_floats,
-                px * 3 if rgb_stride_floats is None else rgb_stride_floats)
-
     def enqueue_frames(self, d_frames, n, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None, stream=None):
         """Asynchronous; n frames at d_frames + f * frame_stride_floats (default: packed [n][H][W][14]), in place or, with d_rgb,
         [H][W][3] at d_rgb + f * rgb_stride_floats (default packed): bit for bit n single enqueues."""
@@ -932,9 +953,7 @@ class Denoiser:
     def denoise_frames(self, d_frames, n, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None):
         """Synchronous enqueue_frames; returns device-event milliseconds."""
         fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
-        ms = ctypes.c_float(0)
-        check(lib.pt_denoiser_denoise_frames(self.handle, n, d_frames, fs, d_rgb, rs, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_denoiser_denoise_frames, n, d_frames, fs, d_rgb, rs)
 
     def enqueue(self, d_frame, d_rgb=None, stream=None):
         """Asynchronous; d_rgb None = in place on the [H][W][14] frame, else [H][W][3] into d_rgb (frame untouched)."""
@@ -942,9 +961,7 @@ class Denoiser:
 
     def denoise(self, d_frame, d_rgb=None):
         """Synchronous; returns device-event milliseconds."""
-        ms = ctypes.c_float(0)
-        check(lib.pt_denoiser_denoise(self.handle, d_frame, d_rgb, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_denoiser_denoise, d_frame, d_rgb)
 
     # lab library only (pt_debug_denoiser_*)
     def layers(self):
@@ -1008,17 +1025,6 @@ class Denoiser:
             out.append(dict(zip(keys, list(info))))
         return out
 
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_denoiser_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def denoise_frame(frame, weights, out_of_place=False, denoiser=None, precision="float32"):
     """Convenience for tests: upload a host [H][W][14] frame, denoise it on the GPU, download.  Returns the frame after the
@@ -1026,18 +1032,10 @@ def denoise_frame(frame, weights, out_of_place=False, denoiser=None, precision="
     frame = np.ascontiguousarray(frame, dtype=np.float32)
     h, w = frame.shape[:2]
     dn = denoiser or Denoiser(w, h, weights, precision=precision)
-    d_frame = DeviceBuffer(frame.nbytes).upload(frame)
-    d_rgb = DeviceBuffer(h * w * 12) if out_of_place else None
-    try:
-        dn.denoise(d_frame.ptr, d_rgb.ptr if d_rgb else None)
+    with _on_device(frame, h * w * 12 if out_of_place else None, owned=None if denoiser else dn) as (d_frame, d_rgb):
+        dn.denoise(d_frame.ptr, _ptr(d_rgb))
         f = d_frame.download(np.float32, frame.shape)
         return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
-    finally:
-        d_frame.free()
-        if d_rgb:
-            d_rgb.free()
-        if denoiser is None:
-            dn.destroy()
 
 
 def denoise_frames(frames, weights, out_of_place=False, denoiser=None, precision="float32"):
@@ -1047,18 +1045,10 @@ def denoise_frames(frames, weights, out_of_place=False, denoiser=None, precision
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
     dn = denoiser or Denoiser(w, h, weights, max_frames=n, precision=precision)
-    d_frames = DeviceBuffer(frames.nbytes).upload(frames)
-    d_rgb = DeviceBuffer(n * h * w * 12) if out_of_place else None
-    try:
-        dn.denoise_frames(d_frames.ptr, n, d_rgb=d_rgb.ptr if d_rgb else None)
+    with _on_device(frames, n * h * w * 12 if out_of_place else None, owned=None if denoiser else dn) as (d_frames, d_rgb):
+        dn.denoise_frames(d_frames.ptr, n, d_rgb=_ptr(d_rgb))
         f = d_frames.download(np.float32, frames.shape)
         return (f, d_rgb.download(np.float32, (n, h, w, 3))) if out_of_place else f
-    finally:
-        d_frames.free()
-        if d_rgb:
-            d_rgb.free()
-        if denoiser is None:
-            dn.destroy()
 
 
 class FilterOpts(ctypes.Structure):
@@ -1067,14 +1057,14 @@ class FilterOpts(ctypes.Structure):
                 ("sigma_z", ctypes.c_float), ("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
-class FeatureFilter:
+class FeatureFilter(_BatchedStage):
     """ctypes view of pt_filter: the weights-free denoiser for width x height frames, a variance-guided edge-avoiding a-trous
     filter on albedo-demodulated colour (DENOISER.md, "Feature-guided filter").  max_frames > 1 reserves the workspace for
     batches of that many frames per group.  samples: the frame's count per pixel; d_counts: a device uint32 [H][W] count image
     (Progressive.counts' layout) that replaces it."""
+    _destroy, _reserve = "pt_filter_destroy", "pt_filter_reserve_frames"
 
     def __init__(self, width, height, max_frames=1, iterations=5, sigma_l=4.0, sigma_n=0.35, sigma_a=0.1, sigma_z=1.0):
-        self.handle = None
         opts = FilterOpts(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_a=sigma_a, sigma_z=sigma_z, max_frames=max_frames)
         h = _vp()
         check(lib.pt_filter_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
@@ -1083,21 +1073,11 @@ class FeatureFilter:
         self.max_frames = max_frames
         self.iterations = iterations
 
-    def reserve_frames(self, n):
-        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
-        check(lib.pt_filter_reserve_frames(self.handle, n))
-        self.max_frames = max(self.max_frames, n)
-
     def memory(self):
         """{"workspace": bytes of the state and guide images of all max_frames frames, "per_pixel": bytes per pixel and frame}."""
         b = ctypes.c_uint64(0)
         check(lib.pt_filter_workspace_bytes(self.handle, ctypes.byref(b)))
         return {"workspace": int(b.value), "per_pixel": int(b.value) // (self.max_frames * self.width * self.height)}
-
-    def _strides(self, frame_stride_floats, rgb_stride_floats):
-        px = self.width * self.height
-        return (px * CHANNELS if frame_stride_floats is None else frame_stride_floats,
-                px * 3 if rgb_stride_floats is None else rgb_stride_floats)
 
     def enqueue(self, d_frame, samples, d_rgb=None, d_counts=None, stream=None):
         """Asynchronous; d_rgb None = in place on the [H][W][14] frame, else [H][W][3] into d_rgb (frame untouched)."""
@@ -1105,9 +1085,7 @@ class FeatureFilter:
 
     def run(self, d_frame, samples, d_rgb=None, d_counts=None):
         """Synchronous; returns device-event milliseconds."""
-        ms = ctypes.c_float(0)
-        check(lib.pt_filter_run(self.handle, d_frame, d_rgb, samples, d_counts, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_filter_run, d_frame, d_rgb, samples, d_counts)
 
     def enqueue_frames(self, d_frames, n, samples, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None, stream=None):
         """Asynchronous; n frames at d_frames + k * frame_stride_floats (default: packed [n][H][W][14]), in place or, with d_rgb,
@@ -1118,15 +1096,7 @@ class FeatureFilter:
     def run_frames(self, d_frames, n, samples, frame_stride_floats=None, d_rgb=None, rgb_stride_floats=None):
         """Synchronous enqueue_frames; returns device-event milliseconds."""
         fs, rs = self._strides(frame_stride_floats, rgb_stride_floats)
-        ms = ctypes.c_float(0)
-        check(lib.pt_filter_run_frames(self.handle, n, d_frames, fs, d_rgb, rs, samples, ctypes.byref(ms)))
-        return ms.value
-
-    @staticmethod
-    def _lab(name):
-        if not IS_LAB:
-            raise RuntimeError(f"{name} is a diagnostic of libptcore_lab.so (include/ptcore_lab.h); the product library has none")
-        return getattr(lib, name)
+        return self._timed(lib.pt_filter_run_frames, n, d_frames, fs, d_rgb, rs, samples)
 
     def step(self, d_frame, samples, step, d_rgb=None, d_counts=None):
         """Lab library only: the set-up and one iteration at `step`, fused with the re-modulation; synchronous."""
@@ -1136,17 +1106,6 @@ class FeatureFilter:
         """Lab library only: steps 1 and 2 through the LDS tile (True) or with direct loads (False)."""
         check(self._lab("pt_debug_filter_tiled")(self.handle, int(bool(on))))
 
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_filter_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **opts):
     """Convenience for tests: upload a host [H][W][14] frame, filter it on the GPU, download.  Returns the frame after the
@@ -1155,21 +1114,11 @@ def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **o
     frame = np.ascontiguousarray(frame, dtype=np.float32)
     h, w = frame.shape[:2]
     ff = filt or FeatureFilter(w, h, **opts)
-    d_frame = DeviceBuffer(frame.nbytes).upload(frame)
-    d_rgb = DeviceBuffer(h * w * 12) if out_of_place else None
-    d_counts = DeviceBuffer(h * w * 4).upload(np.ascontiguousarray(counts, dtype=np.uint32)) if counts is not None else None
-    try:
-        ff.run(d_frame.ptr, samples, d_rgb.ptr if d_rgb else None, d_counts.ptr if d_counts else None)
+    counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    with _on_device(frame, h * w * 12 if out_of_place else None, counts, owned=None if filt else ff) as (d_frame, d_rgb, d_counts):
+        ff.run(d_frame.ptr, samples, _ptr(d_rgb), _ptr(d_counts))
         f = d_frame.download(np.float32, frame.shape)
         return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
-    finally:
-        d_frame.free()
-        if d_rgb:
-            d_rgb.free()
-        if d_counts:
-            d_counts.free()
-        if filt is None:
-            ff.destroy()
 
 
 def filter_frames(frames, samples, out_of_place=False, filt=None, **opts):
@@ -1179,18 +1128,10 @@ def filter_frames(frames, samples, out_of_place=False, filt=None, **opts):
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
     ff = filt or FeatureFilter(w, h, max_frames=n, **opts)
-    d_frames = DeviceBuffer(frames.nbytes).upload(frames)
-    d_rgb = DeviceBuffer(n * h * w * 12) if out_of_place else None
-    try:
-        ff.run_frames(d_frames.ptr, n, samples, d_rgb=d_rgb.ptr if d_rgb else None)
+    with _on_device(frames, n * h * w * 12 if out_of_place else None, owned=None if filt else ff) as (d_frames, d_rgb):
+        ff.run_frames(d_frames.ptr, n, samples, d_rgb=_ptr(d_rgb))
         f = d_frames.download(np.float32, frames.shape)
         return (f, d_rgb.download(np.float32, (n, h, w, 3))) if out_of_place else f
-    finally:
-        d_frames.free()
-        if d_rgb:
-            d_rgb.free()
-        if filt is None:
-            ff.destroy()
 
 
 class TemporalOpts(ctypes.Structure):
@@ -1208,14 +1149,14 @@ def temporal_camera(basis):
     return out.reshape(3, 3)
 
 
-class Temporal:
+class Temporal(_Session):
     """ctypes view of pt_temporal: the temporal accumulator for width x height frames (DENOISER.md, "Temporal accumulation").
     Every call works in place on a device [H][W][14] frame of `samples` samples per pixel rendered with (basis, eye): channels
     0-2 and 10 become those of all the samples accumulated at the pixel's world position; d_counts, a device uint32 [H][W]
     image, receives the accumulated counts (FeatureFilter's d_counts)."""
+    _destroy = "pt_temporal_destroy"
 
     def __init__(self, width, height, history_cap=256.0, depth_tol=0.02, normal_tol=0.9, albedo_tol=0.01, min_weight=0.25):
-        self.handle = None
         opts = TemporalOpts(history_cap=history_cap, depth_tol=depth_tol, normal_tol=normal_tol, albedo_tol=albedo_tol, min_weight=min_weight)
         h = _vp()
         check(lib.pt_temporal_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
@@ -1241,9 +1182,7 @@ class Temporal:
         """Synchronous; returns device-event milliseconds."""
         _, b = _f32(basis, 12)
         _, e = _f32(eye, 3)
-        ms = ctypes.c_float(0)
-        check(lib.pt_temporal_run(self.handle, d_frame, samples, b, e, d_counts, ctypes.byref(ms)))
-        return ms.value
+        return self._timed(lib.pt_temporal_run, d_frame, samples, b, e, d_counts)
 
     def _cameras(self, bases, eyes, frame_stride_floats):
         bases = np.ascontiguousarray(bases, dtype=np.float32).reshape(-1, 12)
@@ -1262,21 +1201,8 @@ class Temporal:
     def run_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None):
         """Synchronous enqueue_frames; returns device-event milliseconds."""
         bases, eyes, fs = self._cameras(bases, eyes, frame_stride_floats)
-        ms = ctypes.c_float(0)
-        check(lib.pt_temporal_run_frames(self.handle, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
-                                         samples, d_counts, ctypes.byref(ms)))
-        return ms.value
-
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_temporal_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return self._timed(lib.pt_temporal_run_frames, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
+                           samples, d_counts)
 
 
 def accumulate_frames(frames, samples, bases, eyes, temporal=None, **opts):
@@ -1286,15 +1212,9 @@ def accumulate_frames(frames, samples, bases, eyes, temporal=None, **opts):
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
     ta = temporal or Temporal(w, h, **opts)
-    d_frames, d_counts = DeviceBuffer(frames.nbytes).upload(frames), DeviceBuffer(h * w * 4)
-    try:
+    with _on_device(frames, h * w * 4, owned=None if temporal else ta) as (d_frames, d_counts):
         ta.run_frames(d_frames.ptr, samples, bases, eyes, d_counts=d_counts.ptr)
         return d_frames.download(np.float32, frames.shape), d_counts.download(np.uint32, (h, w))
-    finally:
-        d_frames.free()
-        d_counts.free()
-        if temporal is None:
-            ta.destroy()
 
 
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
@@ -1316,14 +1236,14 @@ def tonemap_srgb_table():
     return out
 
 
-class Tonemap:
+class Tonemap(_BatchedStage):
     """ctypes view of pt_tonemap: the tone-mapping session for width x height images (DENOISER.md, "Tone mapping").  A call reads
     a device image of linear radiance [H][W][pixel_stride] (14: a frame, 3: a filter's or denoiser's d_rgb; never written) and
     writes device RGBA8 uint32 [H][W].  curve: "clamp" | "reinhard" | "aces"; encode: "srgb" | "linear"; exposure: "auto"
     (metered on the device and adapted from frame to frame at rate `adapt`) or a number > 0."""
+    _destroy, _reserve = "pt_tonemap_destroy", "pt_tonemap_reserve_frames"
 
     def __init__(self, width, height, curve="aces", encode="srgb", exposure="auto", key=0.18, white=4.0, adapt=1.0, max_frames=1):
-        self.handle = None
         if curve not in TONEMAP_CURVES:
             raise ValueError(f"curve {curve!r}: one of {sorted(TONEMAP_CURVES)}")
         if encode not in TONEMAP_ENCODES:
@@ -1337,11 +1257,6 @@ class Tonemap:
         self.handle = h.value
         self.width, self.height = width, height
         self.max_frames = max_frames
-
-    def reserve_frames(self, n):
-        """Workspace for groups of up to n frames (a smaller n is a no-op)."""
-        check(lib.pt_tonemap_reserve_frames(self.handle, n))
-        self.max_frames = max(self.max_frames, n)
 
     def memory(self):
         """{"workspace": bytes of the table, the state and the partial sums of all max_frames frames}."""
@@ -1364,37 +1279,18 @@ class Tonemap:
 
     def run(self, d_src, d_rgba8, pixel_stride=CHANNELS):
         """Synchronous; returns device-event milliseconds."""
-        ms = ctypes.c_float(0)
-        check(lib.pt_tonemap_run(self.handle, d_src, pixel_stride, d_rgba8, ctypes.byref(ms)))
-        return ms.value
-
-    def _strides(self, pixel_stride, src_stride_floats, dst_stride_pixels):
-        px = self.width * self.height
-        return (px * pixel_stride if src_stride_floats is None else src_stride_floats, px if dst_stride_pixels is None else dst_stride_pixels)
+        return self._timed(lib.pt_tonemap_run, d_src, pixel_stride, d_rgba8)
 
     def enqueue_frames(self, d_src, n, d_rgba8, pixel_stride=CHANNELS, src_stride_floats=None, dst_stride_pixels=None, stream=None):
         """Asynchronous; n images at d_src + k * src_stride_floats (default: packed) to d_rgba8 + k * dst_stride_pixels, in order:
         bit for bit n single enqueues, the adaptation included."""
-        ss, ds = self._strides(pixel_stride, src_stride_floats, dst_stride_pixels)
+        ss, ds = self._strides(src_stride_floats, dst_stride_pixels, pixel_stride, 1)
         check(lib.pt_tonemap_enqueue_frames(self.handle, n, d_src, ss, pixel_stride, d_rgba8, ds, stream))
 
     def run_frames(self, d_src, n, d_rgba8, pixel_stride=CHANNELS, src_stride_floats=None, dst_stride_pixels=None):
         """Synchronous enqueue_frames; returns device-event milliseconds."""
-        ss, ds = self._strides(pixel_stride, src_stride_floats, dst_stride_pixels)
-        ms = ctypes.c_float(0)
-        check(lib.pt_tonemap_run_frames(self.handle, n, d_src, ss, pixel_stride, d_rgba8, ds, ctypes.byref(ms)))
-        return ms.value
-
-    def destroy(self):
-        if self.handle:
-            check(lib.pt_tonemap_destroy(self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        ss, ds = self._strides(src_stride_floats, dst_stride_pixels, pixel_stride, 1)
+        return self._timed(lib.pt_tonemap_run_frames, n, d_src, ss, pixel_stride, d_rgba8, ds)
 
 
 def tonemap_frame(frame_or_rgb, tonemap=None, **opts):
@@ -1403,12 +1299,6 @@ def tonemap_frame(frame_or_rgb, tonemap=None, **opts):
     img = np.ascontiguousarray(frame_or_rgb, dtype=np.float32)
     h, w, c = img.shape
     tm = tonemap or Tonemap(w, h, **opts)
-    d_src, d_out = DeviceBuffer(img.nbytes).upload(img), DeviceBuffer(h * w * 4)
-    try:
+    with _on_device(img, h * w * 4, owned=None if tonemap else tm) as (d_src, d_out):
         tm.run(d_src.ptr, d_out.ptr, pixel_stride=c)
         return d_out.download(np.uint8, (h, w, 4))
-    finally:
-        d_src.free()
-        d_out.free()
-        if tonemap is None:
-            tm.destroy()

@@ -26,14 +26,6 @@ int pt_fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define PT_HIP(call)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,    \
-                     hipGetErrorString(e_), __FILE__, __LINE__);                                  \
-  } while (0)
-
 struct pt_renderer {
   int width = 0, height = 0, spp = 0, threads_per_block = 0;
   pt_renderer_opts opts{};

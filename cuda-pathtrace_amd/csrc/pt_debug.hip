@@ -95,12 +95,6 @@ __global__ void __launch_bounds__(256) div_compare_kernel(uint32_t n_first, uint
 
 }  // namespace pt
 
-#define PT_HIPD(call)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess) return pt_fail(PT_EHIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
 extern "C" int pt_debug_unary_map(int fn, const float* d_in, float* d_out, size_t n) {
   if (fn < 0 || fn >= PT_FN_COUNT || (n && (!d_in || !d_out))) return pt_fail(PT_EINVAL, "pt_debug_unary_map: bad arguments");
   if (!n) return PT_OK;

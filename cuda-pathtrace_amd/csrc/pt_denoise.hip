@@ -21,7 +21,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "pt_internal.h"
+#include "pt_stage.h"
 #if PT_BUILD_EXPERIMENTS
 #include "../../include/ptcore_lab.h"
 #endif
@@ -38,8 +38,6 @@ constexpr int BK = 16;              // K per staged chunk (every stored Cin is a
 constexpr int XC = 16;              // channels of the padded input copy (14 + 2 zeros)
 constexpr int PRE_BLOCKS = 256;     // partial maxima of the pre-processing reduction
 constexpr float KEPS = 0.00316f;    // train.py:48-55, model.py forward
-constexpr int64_t MAX_BATCH_PIXELS = (int64_t)1 << 26;  // max_frames x width x height: every row index m stays inside int32
-constexpr int MAX_FRAMES = 65535;                        // frames of one group: gridDim.y of the pre-processing kernels
 constexpr float HALF_MAX = 65504.0f;
 constexpr int HSC = 4;  // half GEMM: 16-wide K chunks staged per LDS buffer (64 of K between two barriers)
 
@@ -625,15 +623,6 @@ struct pt_denoiser {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-
-#define PTDN_HIP(call)                                                                           \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,   \
-                     hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-  } while (0)
-
 static int64_t conv_tiles(const Conv& c, int cfg) {
   const int bn = kCfg[cfg].bn;
   return (int64_t)((c.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((c.N + bn - 1) / bn);
@@ -873,12 +862,12 @@ static int launch_conv_t(const pt_denoiser* d, const Conv& c, float* frame_out, 
     case 3: hipLaunchKernelGGL((conv_kernel<T, 1, 1, 4, 1>), grid, dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL((conv_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a); break;
   }
-  PTDN_HIP(hipGetLastError());
+  PT_HIP(hipGetLastError());
   (*launches)++;
   if (c.splits > 1) {
     const uint32_t n = (uint32_t)c.M * (uint32_t)c.N;
     hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, a, c.splits);
-    PTDN_HIP(hipGetLastError());
+    PT_HIP(hipGetLastError());
     (*launches)++;
   }
   return PT_OK;
@@ -898,10 +887,10 @@ template <class T>
 static int launch_pre(const pt_denoiser* d, float* frames, size_t frame_stride, uint32_t pixels, int g, int inplace, hipStream_t s) {
   T* x0 = reinterpret_cast<T*>(d->d_ws) + d->acts[0].off;
   hipLaunchKernelGGL(pre_max_kernel, dim3(d->pre_blocks, g), dim3(256), 0, s, frames, frame_stride, pixels, d->d_premax);
-  PTDN_HIP(hipGetLastError());
+  PT_HIP(hipGetLastError());
   hipLaunchKernelGGL(pre_apply_kernel<T>, dim3((pixels + 255) / 256, g), dim3(256), 0, s, frames, frame_stride, pixels, d->d_premax,
                      d->pre_blocks, x0, inplace);
-  PTDN_HIP(hipGetLastError());
+  PT_HIP(hipGetLastError());
   return PT_OK;
 }
 
@@ -911,7 +900,7 @@ static int launch_pre(const pt_denoiser* d, float* frames, size_t frame_stride, 
 template <class T>
 static int copy_out(const pt_denoiser* d, const Act& a, float* h_out, size_t n) {
   std::vector<T> tmp(n);
-  PTDN_HIP(hipMemcpy(tmp.data(), d->d_ws + a.off * sizeof(T), n * sizeof(T), hipMemcpyDeviceToHost));
+  PT_HIP(hipMemcpy(tmp.data(), d->d_ws + a.off * sizeof(T), n * sizeof(T), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; i++) h_out[i] = (float)tmp[i];
   return PT_OK;
 }
@@ -920,7 +909,7 @@ static int copy_in(const pt_denoiser* d, const Act& a, const float* h_in, size_t
   std::vector<T> tmp(n);
   for (size_t i = 0; i < n; i++)
     tmp[i] = std::is_same<T, float>::value ? (T)h_in[i] : (T)fminf(fmaxf(h_in[i], -HALF_MAX), HALF_MAX);
-  PTDN_HIP(hipMemcpy(d->d_ws + a.off * sizeof(T), tmp.data(), n * sizeof(T), hipMemcpyHostToDevice));
+  PT_HIP(hipMemcpy(d->d_ws + a.off * sizeof(T), tmp.data(), n * sizeof(T), hipMemcpyHostToDevice));
   return PT_OK;
 }
 #endif
@@ -938,8 +927,7 @@ int pt_denoiser_destroy(pt_denoiser* d) {
   if (d->d_ws) (void)hipFree(d->d_ws);
   if (d->d_partial) (void)hipFree(d->d_partial);
   if (d->d_premax) (void)hipFree(d->d_premax);
-  if (d->ev0) (void)hipEventDestroy(d->ev0);
-  if (d->ev1) (void)hipEventDestroy(d->ev1);
+  pt_stage::destroy_events(d);
   delete d;
   return PT_OK;
 }
@@ -983,19 +971,13 @@ int pt_denoiser_create_opts(int width, int height, const void* blob, size_t byte
     if (opts->reserved[i] != 0) return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: reserved[%d] = %d must be 0", i, opts->reserved[i]);
   if (width <= 0 || height <= 0 || (int64_t)width * height > 4096 * 4096)
     return pt_fail(PT_EINVAL, "pt_denoiser_create: frame size %d x %d outside 1 .. 4096 x 4096 pixels", width, height);
-  if (opts->max_frames > MAX_FRAMES || (int64_t)opts->max_frames * width * height > MAX_BATCH_PIXELS)
-    return pt_fail(PT_EINVAL, "pt_denoiser_create_opts: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
-                   opts->max_frames, width, height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
-  std::map<std::string, Tensor> t;
-  int rc = parse_weights(blob, bytes, &t, "pt_denoiser_create");
+  int rc = pt_stage::check_batch("pt_denoiser_create_opts", opts->max_frames, width, height);
   if (rc != PT_OK) return rc;
+  std::map<std::string, Tensor> t;
+  if ((rc = parse_weights(blob, bytes, &t, "pt_denoiser_create")) != PT_OK) return rc;
   const bool half = opts->precision == PT_DENOISE_F16;
   if (half && (rc = check_half_range(t, "pt_denoiser_create_opts")) != PT_OK) return rc;
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
-    return pt_fail(PT_ENODEVICE, "pt_denoiser_create: no HIP device visible (there is no CPU fallback)");
-  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_denoiser_create: hipGetDeviceCount: %s (no usable device)", hipGetErrorString(e));
+  if ((rc = pt_stage::check_device("pt_denoiser_create")) != PT_OK) return rc;
   pt_denoiser* d = new (std::nothrow) pt_denoiser();
   if (!d) return pt_fail(PT_ENOMEM, "pt_denoiser_create: out of host memory");
   d->width = width, d->height = height;
@@ -1011,7 +993,7 @@ int pt_denoiser_create_opts(int width, int height, const void* blob, size_t byte
   const std::vector<float>& wf = half ? wp : w;  // what d_w holds
   d->pre_blocks = (int)(((uint64_t)width * height + 255) / 256);
   if (d->pre_blocks > PRE_BLOCKS) d->pre_blocks = PRE_BLOCKS;
-  e = hipGetDevice(&d->device);
+  hipError_t e = hipGetDevice(&d->device);
   if (e == hipSuccess) e = hipMalloc((void**)&d->d_w, wf.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(d->d_w, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess && half) e = hipMalloc((void**)&d->d_wh, wh.size() * sizeof(_Float16));
@@ -1020,13 +1002,7 @@ int pt_denoiser_create_opts(int width, int height, const void* blob, size_t byte
   if (e == hipSuccess) e = hipMemset(d->d_ws, 0, d->ws_elems * d->esz);
   if (e == hipSuccess && d->partial_floats) e = hipMalloc((void**)&d->d_partial, d->partial_floats * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->d_premax, PRE_BLOCKS * 5 * sizeof(float));
-  if (e == hipSuccess) e = hipEventCreate(&d->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&d->ev1);
-  if (e != hipSuccess) {
-    rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_denoiser_create: %s", hipGetErrorString(e));
-    pt_denoiser_destroy(d);
-    return rc;
-  }
+  if ((rc = pt_stage::create_events("pt_denoiser_create", e, d, pt_denoiser_destroy)) != PT_OK) return rc;
   if (opts->max_frames > 1 && (rc = pt_denoiser_reserve_frames(d, opts->max_frames)) != PT_OK) {
     pt_denoiser_destroy(d);
     return rc;
@@ -1069,10 +1045,8 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
   if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: null denoiser");
   if (max_frames < 1) return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d < 1", max_frames);
   if (max_frames <= d->max_frames) return PT_OK;
-  const int64_t px = (int64_t)max_frames * d->width * d->height;
-  if (max_frames > MAX_FRAMES || px > MAX_BATCH_PIXELS)
-    return pt_fail(PT_EINVAL, "pt_denoiser_reserve_frames: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
-                   max_frames, d->width, d->height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
+  int rc = pt_stage::check_batch("pt_denoiser_reserve_frames", max_frames, d->width, d->height);
+  if (rc != PT_OK) return rc;
   const std::vector<Conv> plan = batch_plan(d->convs, max_frames, kPlan[d->precision]);
   for (const Conv& c : plan)  // splitk_reduce_kernel indexes M x N elements in 32 bits
     if ((int64_t)c.M * c.N > (int64_t)UINT32_MAX)
@@ -1080,51 +1054,47 @@ int pt_denoiser_reserve_frames(pt_denoiser* d, int max_frames) {
   std::vector<Act> acts = d->acts;
   const size_t ws_elems = layout_acts(acts, max_frames, d->esz);
   const size_t partial_floats = partial_floats_of(plan);
-  char* ws = nullptr;
-  float *partial = nullptr, *premax = nullptr;
-  hipError_t e = hipMalloc((void**)&ws, ws_elems * d->esz);
-  if (e == hipSuccess) e = hipMemset(ws, 0, ws_elems * d->esz);
-  if (e == hipSuccess && partial_floats) e = hipMalloc((void**)&partial, partial_floats * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&premax, (size_t)max_frames * PRE_BLOCKS * 5 * sizeof(float));
-  if (e == hipSuccess) e = hipDeviceSynchronize();  // the old buffers may still be in use by enqueued work
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (ws) (void)hipFree(ws);
-    if (partial) (void)hipFree(partial);
-    if (premax) (void)hipFree(premax);
-    return pt_fail(PT_EHIP, "pt_denoiser_reserve_frames: %d frames (%zu + %zu workspace elements): %s; the old workspace is kept",
-                   max_frames, ws_elems, partial_floats, hipGetErrorString(e));
-  }
-  (void)hipFree(d->d_ws);
-  if (d->d_partial) (void)hipFree(d->d_partial);
-  (void)hipFree(d->d_premax);
-  d->d_ws = ws, d->d_partial = partial, d->d_premax = premax;
+  const pt_stage::Buffer bufs[3] = {{(void**)&d->d_ws, ws_elems * d->esz, true},
+                                    {(void**)&d->d_partial, partial_floats * sizeof(float), false},
+                                    {(void**)&d->d_premax, (size_t)max_frames * PRE_BLOCKS * 5 * sizeof(float), false}};
+  rc = pt_stage::grow_workspace("pt_denoiser_reserve_frames", bufs, "%d frames (%zu + %zu workspace elements)", max_frames, ws_elems,
+                                partial_floats);
+  if (rc != PT_OK) return rc;
   d->acts = acts;
   d->ws_elems = ws_elems, d->partial_floats = partial_floats;
   d->max_frames = max_frames;
   return PT_OK;
 }
 
-int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
-                               size_t rgb_stride_floats, void* hip_stream) {
-  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: null denoiser");
+// (every check before any launch: a refused call launches nothing, and the lab counters say so.  The timed call refuses in the
+// words of the call it wraps.)
+static int check_frames_args(pt_denoiser* d, int n_frames, const float* d_frames, size_t frame_stride_floats, const float* d_rgb,
+                             size_t rgb_stride_floats) {
   d->last_groups = d->last_launches = 0;
   if (!d_frames) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: null d_frames");
   if (n_frames < 1) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: n_frames %d < 1", n_frames);
-  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
-  if (frame_stride_floats < (size_t)pixels * 14)
+  const size_t pixels = (size_t)d->width * d->height;
+  if (frame_stride_floats < pixels * 14)
     return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: frame_stride_floats %zu < width x height x 14 = %zu", frame_stride_floats,
-                   (size_t)pixels * 14);
-  if (d_rgb && rgb_stride_floats < (size_t)pixels * 3)
-    return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: rgb_stride_floats %zu < width x height x 3 = %zu", rgb_stride_floats,
-                   (size_t)pixels * 3);
+                   pixels * 14);
+  if (d_rgb && rgb_stride_floats < pixels * 3)
+    return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: rgb_stride_floats %zu < width x height x 3 = %zu", rgb_stride_floats, pixels * 3);
+  return PT_OK;
+}
+
+int pt_denoiser_enqueue_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
+                               size_t rgb_stride_floats, void* hip_stream) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_enqueue_frames: null denoiser");
+  int rc = check_frames_args(d, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats);
+  if (rc != PT_OK) return rc;
+  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
   hipStream_t s = (hipStream_t)hip_stream;
   for (int f0 = 0; f0 < n_frames; f0 += d->max_frames) {
     const int g = n_frames - f0 < d->max_frames ? n_frames - f0 : d->max_frames;
     float* frames = d_frames + (size_t)f0 * frame_stride_floats;
     float* out = d_rgb ? d_rgb + (size_t)f0 * rgb_stride_floats : frames;
-    int rc = d->precision == PT_DENOISE_F16 ? launch_pre<_Float16>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s)
-                                            : launch_pre<float>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s);
+    rc = d->precision == PT_DENOISE_F16 ? launch_pre<_Float16>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s)
+                                        : launch_pre<float>(d, frames, frame_stride_floats, pixels, g, d_rgb ? 0 : 1, s);
     if (rc != PT_OK) return rc;
     d->last_launches += 2;
     for (const Conv& c : plan_for(d, g)) {
@@ -1146,15 +1116,11 @@ int pt_denoiser_enqueue(pt_denoiser* d, float* d_frame, float* d_rgb, void* hip_
 int pt_denoiser_denoise_frames(pt_denoiser* d, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
                                size_t rgb_stride_floats, float* ms_out) {
   if (!d) return pt_fail(PT_EINVAL, "pt_denoiser_denoise_frames: null denoiser");
-  PTDN_HIP(hipEventRecord(d->ev0, nullptr));
-  const int rc = pt_denoiser_enqueue_frames(d, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, nullptr);
+  const int rc = check_frames_args(d, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats);
   if (rc != PT_OK) return rc;
-  PTDN_HIP(hipEventRecord(d->ev1, nullptr));
-  PTDN_HIP(hipEventSynchronize(d->ev1));
-  float ms = 0.0f;
-  PTDN_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-  if (ms_out) *ms_out = ms;
-  return PT_OK;
+  return pt_stage::run_timed(d->ev0, d->ev1, ms_out, [&] {
+    return pt_denoiser_enqueue_frames(d, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, nullptr);
+  });
 }
 
 int pt_denoiser_denoise(pt_denoiser* d, float* d_frame, float* d_rgb, float* ms_out) {
@@ -1181,7 +1147,7 @@ int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t
   const Act& a = d->acts[layer];
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
-  PTDN_HIP(hipDeviceSynchronize());
+  PT_HIP(hipDeviceSynchronize());
   return d->precision == PT_DENOISE_F16 ? copy_out<_Float16>(d, a, h_out, n) : copy_out<float>(d, a, h_out, n);
 }
 
@@ -1191,7 +1157,7 @@ int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_i
   const Act& a = d->acts[layer];
   const size_t n = (size_t)a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
-  PTDN_HIP(hipDeviceSynchronize());
+  PT_HIP(hipDeviceSynchronize());
   return d->precision == PT_DENOISE_F16 ? copy_in<_Float16>(d, a, h_in, n) : copy_in<float>(d, a, h_in, n);
 }
 
@@ -1215,7 +1181,7 @@ int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
   int launches = 0;
   const int rc = launch_conv(d, c, d_rgb, 3, 0, 1, nullptr, &launches);
   if (rc != PT_OK) return rc;
-  PTDN_HIP(hipDeviceSynchronize());
+  PT_HIP(hipDeviceSynchronize());
   return PT_OK;
 }
 
@@ -1241,7 +1207,7 @@ int pt_debug_denoiser_last_enqueue(pt_denoiser* d, int* groups, int* launches) {
 
 int pt_debug_denoiser_conv_plan(pt_denoiser* d, int n_frames, int conv, int info[6]) {
   if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: null denoiser");
-  if (n_frames < 1 || n_frames > MAX_FRAMES || (int64_t)n_frames * d->width * d->height > MAX_BATCH_PIXELS)
+  if (n_frames < 1 || n_frames > pt_stage::MAX_FRAMES || (int64_t)n_frames * d->width * d->height > pt_stage::MAX_BATCH_PIXELS)
     return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: n_frames %d outside the batch limits", n_frames);
   if (conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_conv_plan: no conv %d", conv);
   const Conv& c = plan_for(d, n_frames)[conv];

@@ -29,12 +29,6 @@ __global__ void __launch_bounds__(256) display_pack_kernel(const float* __restri
 }
 }  // namespace pt
 
-#define PT_HIPD(call)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess) return pt_fail(PT_EHIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
 extern "C" int pt_display_pack(const float* d_buffer, int width, int height, float* d_vertices, void* hip_stream) {
   if (width <= 0 || height <= 0 || !d_buffer || !d_vertices) return pt_fail(PT_EINVAL, "pt_display_pack: bad arguments");
   const uint64_t pixels = (uint64_t)width * (uint64_t)height;

@@ -17,7 +17,7 @@
 
 #include <new>
 
-#include "pt_internal.h"
+#include "pt_stage.h"
 #if PT_BUILD_EXPERIMENTS
 #include "../../include/ptcore_lab.h"
 #endif
@@ -26,8 +26,6 @@ namespace ptflt {
 
 constexpr float EPS = 0.00316f;  // train.py:48-55's pre-processing constant, as in pt_denoise.hip
 constexpr int BX = 32, BY = 8;   // workgroup: 32 columns x 8 rows, a wave covers two rows of 32 pixels
-constexpr int MAX_FRAMES = 65535;                 // gridDim.z
-constexpr int64_t MAX_BATCH_PIXELS = 1ll << 26;   // as pt_denoiser_reserve_frames
 
 struct Params {
   int width, height;
@@ -182,14 +180,6 @@ struct pt_filter {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-#define PTF_HIP(call)                                                                            \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,   \
-                     hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-  } while (0)
-
 static size_t ws_bytes(const pt_filter* f, int frames) { return (size_t)4 * frames * f->width * f->height * sizeof(float4); }
 
 static Params make_params(const pt_filter* f, size_t frame_stride, size_t out_stride, int out_ld, int samples) {
@@ -227,7 +217,7 @@ static int launch_group(const pt_filter* f, const Params& p, int g, const float*
       a = b, b = t;
     }
   }
-  PTF_HIP(hipGetLastError());
+  PT_HIP(hipGetLastError());
   return PT_OK;
 }
 
@@ -274,8 +264,7 @@ void pt_filter_opts_default(pt_filter_opts* opts) {
 int pt_filter_destroy(pt_filter* f) {
   if (!f) return PT_OK;
   if (f->d_ws) (void)hipFree(f->d_ws);
-  if (f->ev0) (void)hipEventDestroy(f->ev0);
-  if (f->ev1) (void)hipEventDestroy(f->ev1);
+  pt_stage::destroy_events(f);
   delete f;
   return PT_OK;
 }
@@ -286,37 +275,23 @@ int pt_filter_create(int width, int height, const pt_filter_opts* opts, pt_filte
   pt_filter_opts o;
   if (opts) o = *opts;
   else pt_filter_opts_default(&o);
-  if (width <= 0 || width > 16384) return pt_fail(PT_EINVAL, "pt_filter_create: width %d outside 1 .. 16384", width);
-  if (height <= 0 || height > 16384) return pt_fail(PT_EINVAL, "pt_filter_create: height %d outside 1 .. 16384", height);
-  if ((int64_t)width * height > 4096 * 4096)
-    return pt_fail(PT_EINVAL, "pt_filter_create: frame size %d x %d (width x height) exceeds 4096 x 4096 pixels", width, height);
+  int rc = pt_stage::check_frame_size("pt_filter_create", width, height);
+  if (rc != PT_OK) return rc;
   if (o.iterations < 1 || o.iterations > 8) return pt_fail(PT_EINVAL, "pt_filter_create: iterations %d outside 1 .. 8", o.iterations);
   const struct { const char* name; float v; } sig[4] = {{"sigma_l", o.sigma_l}, {"sigma_n", o.sigma_n}, {"sigma_a", o.sigma_a}, {"sigma_z", o.sigma_z}};
   for (const auto& s : sig)
     if (!(s.v > 0.0f) || !(s.v <= 3.4028234663852886e38f))
       return pt_fail(PT_EINVAL, "pt_filter_create: %s %g must be finite and > 0", s.name, (double)s.v);
   if (o.max_frames < 1) return pt_fail(PT_EINVAL, "pt_filter_create: max_frames %d < 1", o.max_frames);
-  if (o.max_frames > MAX_FRAMES || (int64_t)o.max_frames * width * height > MAX_BATCH_PIXELS)
-    return pt_fail(PT_EINVAL, "pt_filter_create: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels", o.max_frames,
-                   width, height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
+  if ((rc = pt_stage::check_batch("pt_filter_create", o.max_frames, width, height)) != PT_OK) return rc;
   for (int i = 0; i < 2; i++)
     if (o.reserved[i] != 0) return pt_fail(PT_EINVAL, "pt_filter_create: reserved[%d] = %d must be 0", i, o.reserved[i]);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
-    return pt_fail(PT_ENODEVICE, "pt_filter_create: no HIP device visible (there is no CPU fallback)");
-  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_filter_create: hipGetDeviceCount: %s (no usable device)", hipGetErrorString(e));
+  if ((rc = pt_stage::check_device("pt_filter_create")) != PT_OK) return rc;
   pt_filter* f = new (std::nothrow) pt_filter();
   if (!f) return pt_fail(PT_ENOMEM, "pt_filter_create: out of host memory");
   f->width = width, f->height = height, f->opts = o, f->max_frames = o.max_frames;
-  e = hipMalloc((void**)&f->d_ws, ws_bytes(f, f->max_frames));
-  if (e == hipSuccess) e = hipEventCreate(&f->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&f->ev1);
-  if (e != hipSuccess) {
-    const int rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_filter_create: %s", hipGetErrorString(e));
-    pt_filter_destroy(f);
-    return rc;
-  }
+  const hipError_t e = hipMalloc((void**)&f->d_ws, ws_bytes(f, f->max_frames));
+  if ((rc = pt_stage::create_events("pt_filter_create", e, f, pt_filter_destroy)) != PT_OK) return rc;
   *out = f;
   return PT_OK;
 }
@@ -325,20 +300,11 @@ int pt_filter_reserve_frames(pt_filter* f, int max_frames) {
   if (!f) return pt_fail(PT_EINVAL, "pt_filter_reserve_frames: null filter");
   if (max_frames < 1) return pt_fail(PT_EINVAL, "pt_filter_reserve_frames: max_frames %d < 1", max_frames);
   if (max_frames <= f->max_frames) return PT_OK;
-  if (max_frames > MAX_FRAMES || (int64_t)max_frames * f->width * f->height > MAX_BATCH_PIXELS)
-    return pt_fail(PT_EINVAL, "pt_filter_reserve_frames: max_frames %d x %d x %d pixels exceeds the limit of %d frames and %lld pixels",
-                   max_frames, f->width, f->height, MAX_FRAMES, (long long)MAX_BATCH_PIXELS);
-  float4* ws = nullptr;
-  hipError_t e = hipMalloc((void**)&ws, ws_bytes(f, max_frames));
-  if (e == hipSuccess) e = hipDeviceSynchronize();  // the old workspace may still be in use by enqueued work
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (ws) (void)hipFree(ws);
-    return pt_fail(PT_EHIP, "pt_filter_reserve_frames: %d frames (%zu bytes): %s; the old workspace is kept", max_frames,
-                   ws_bytes(f, max_frames), hipGetErrorString(e));
-  }
-  (void)hipFree(f->d_ws);
-  f->d_ws = ws;
+  int rc = pt_stage::check_batch("pt_filter_reserve_frames", max_frames, f->width, f->height);
+  if (rc != PT_OK) return rc;
+  const pt_stage::Buffer bufs[1] = {{(void**)&f->d_ws, ws_bytes(f, max_frames), false}};
+  rc = pt_stage::grow_workspace("pt_filter_reserve_frames", bufs, "%d frames (%zu bytes)", max_frames, ws_bytes(f, max_frames));
+  if (rc != PT_OK) return rc;
   f->max_frames = max_frames;
   return PT_OK;
 }
@@ -366,15 +332,9 @@ static int run_timed(const char* who, pt_filter* f, int n_frames, float* d_frame
   // (arguments first: a refused call must not touch the device)
   const int rc0 = check_frames_args(who, f, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, samples, d_counts);
   if (rc0 != PT_OK) return rc0;
-  PTF_HIP(hipEventRecord(f->ev0, nullptr));
-  const int rc = enqueue_frames(who, f, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, samples, d_counts, nullptr);
-  if (rc != PT_OK) return rc;
-  PTF_HIP(hipEventRecord(f->ev1, nullptr));
-  PTF_HIP(hipEventSynchronize(f->ev1));
-  float ms = 0.0f;
-  PTF_HIP(hipEventElapsedTime(&ms, f->ev0, f->ev1));
-  if (ms_out) *ms_out = ms;
-  return PT_OK;
+  return pt_stage::run_timed(f->ev0, f->ev1, ms_out, [&] {
+    return enqueue_frames(who, f, n_frames, d_frames, frame_stride_floats, d_rgb, rgb_stride_floats, samples, d_counts, nullptr);
+  });
 }
 
 int pt_filter_run_frames(pt_filter* f, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb, size_t rgb_stride_floats,
@@ -402,7 +362,7 @@ int pt_debug_filter_step(pt_filter* f, float* d_frame, float* d_rgb, int samples
   if (step < 1 || step > 4096) return pt_fail(PT_EINVAL, "pt_debug_filter_step: step %d outside 1 .. 4096", step);
   const Params p = make_params(f, pixels * 14, d_rgb ? pixels * 3 : pixels * 14, d_rgb ? 3 : 14, samples);
   if ((rc = launch_group(f, p, 1, d_frame, d_rgb ? d_rgb : d_frame, d_counts, &step, 1, nullptr)) != PT_OK) return rc;
-  PTF_HIP(hipDeviceSynchronize());
+  PT_HIP(hipDeviceSynchronize());
   return PT_OK;
 }
 #endif

@@ -14,7 +14,7 @@
 
 #include <new>
 
-#include "pt_internal.h"
+#include "pt_stage.h"
 
 namespace pttmp {
 
@@ -129,15 +129,7 @@ struct pt_temporal {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-#define PTT_HIP(call)                                                                            \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,   \
-                     hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-  } while (0)
-
-static bool finite_f(float v) { return v >= -3.4028234663852886e38f && v <= 3.4028234663852886e38f; }
+using pt_stage::finite_f;
 
 // The host step of the definition, in double, no contraction (CXXFLAGS): P = adj(M) / det for M = [B0 | B1-B0 | B2-B0].
 static int camera_matrix(const char* who, const float basis[12], float P[9]) {
@@ -219,7 +211,7 @@ static int enqueue_frames(const char* who, pt_temporal* t, int n_frames, float* 
     // the count image is that of the last frame
     hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, s, p, d_frames + (size_t)f * frame_stride_floats, (const float4*)hin, hout,
                        f == n_frames - 1 ? d_counts : (uint32_t*)nullptr);
-    PTT_HIP(hipGetLastError());
+    PT_HIP(hipGetLastError());
     (void)camera_matrix(who, B, t->P);  // (checked above)
     for (int k = 0; k < 3; k++) t->eye[k] = eyes[3 * f + k];
     t->cur = 1 - t->cur;
@@ -232,15 +224,9 @@ static int run_timed(const char* who, pt_temporal* t, int n_frames, float* d_fra
                      const float* eyes, int samples, uint32_t* d_counts, float* ms_out) {
   const int rc0 = check_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples);
   if (rc0 != PT_OK) return rc0;
-  PTT_HIP(hipEventRecord(t->ev0, nullptr));
-  const int rc = enqueue_frames(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_counts, nullptr);
-  if (rc != PT_OK) return rc;
-  PTT_HIP(hipEventRecord(t->ev1, nullptr));
-  PTT_HIP(hipEventSynchronize(t->ev1));
-  float ms = 0.0f;
-  PTT_HIP(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-  if (ms_out) *ms_out = ms;
-  return PT_OK;
+  return pt_stage::run_timed(t->ev0, t->ev1, ms_out, [&] {
+    return enqueue_frames(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_counts, nullptr);
+  });
 }
 
 extern "C" {
@@ -265,8 +251,7 @@ int pt_temporal_camera(const float basis[12], float P_out[9]) {
 int pt_temporal_destroy(pt_temporal* t) {
   if (!t) return PT_OK;
   if (t->d_hist) (void)hipFree(t->d_hist);
-  if (t->ev0) (void)hipEventDestroy(t->ev0);
-  if (t->ev1) (void)hipEventDestroy(t->ev1);
+  pt_stage::destroy_events(t);
   delete t;
   return PT_OK;
 }
@@ -277,10 +262,8 @@ int pt_temporal_create(int width, int height, const pt_temporal_opts* opts, pt_t
   pt_temporal_opts o;
   if (opts) o = *opts;
   else pt_temporal_opts_default(&o);
-  if (width <= 0 || width > 16384) return pt_fail(PT_EINVAL, "pt_temporal_create: width %d outside 1 .. 16384", width);
-  if (height <= 0 || height > 16384) return pt_fail(PT_EINVAL, "pt_temporal_create: height %d outside 1 .. 16384", height);
-  if ((int64_t)width * height > 4096 * 4096)
-    return pt_fail(PT_EINVAL, "pt_temporal_create: frame size %d x %d (width x height) exceeds 4096 x 4096 pixels", width, height);
+  int rc = pt_stage::check_frame_size("pt_temporal_create", width, height);
+  if (rc != PT_OK) return rc;
   if (!(o.history_cap >= 1.0f)) return pt_fail(PT_EINVAL, "pt_temporal_create: history_cap %g must be >= 1", (double)o.history_cap);
   if (!(o.depth_tol > 0.0f) || !finite_f(o.depth_tol))
     return pt_fail(PT_EINVAL, "pt_temporal_create: depth_tol %g must be finite and > 0", (double)o.depth_tol);
@@ -291,22 +274,12 @@ int pt_temporal_create(int width, int height, const pt_temporal_opts* opts, pt_t
   if (!(o.min_weight > 0.0f && o.min_weight <= 1.0f))
     return pt_fail(PT_EINVAL, "pt_temporal_create: min_weight %g outside (0, 1]", (double)o.min_weight);
   if (o.reserved != 0) return pt_fail(PT_EINVAL, "pt_temporal_create: reserved = %d must be 0", o.reserved);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
-    return pt_fail(PT_ENODEVICE, "pt_temporal_create: no HIP device visible (there is no CPU fallback)");
-  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_temporal_create: hipGetDeviceCount: %s (no usable device)", hipGetErrorString(e));
+  if ((rc = pt_stage::check_device("pt_temporal_create")) != PT_OK) return rc;
   pt_temporal* t = new (std::nothrow) pt_temporal();
   if (!t) return pt_fail(PT_ENOMEM, "pt_temporal_create: out of host memory");
   t->width = width, t->height = height, t->opts = o;
-  e = hipMalloc((void**)&t->d_hist, ws_bytes(t));
-  if (e == hipSuccess) e = hipEventCreate(&t->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&t->ev1);
-  if (e != hipSuccess) {
-    const int rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_temporal_create: %s", hipGetErrorString(e));
-    pt_temporal_destroy(t);
-    return rc;
-  }
+  const hipError_t e = hipMalloc((void**)&t->d_hist, ws_bytes(t));
+  if ((rc = pt_stage::create_events("pt_temporal_create", e, t, pt_temporal_destroy)) != PT_OK) return rc;
   *out = t;
   return PT_OK;
 }

@@ -15,7 +15,7 @@
 
 #include <new>
 
-#include "pt_internal.h"
+#include "pt_stage.h"
 
 namespace pttm {
 
@@ -186,15 +186,7 @@ struct pt_tonemap {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-#define PTM_HIP(call)                                                                            \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return pt_fail(e_ == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "%s: %s (%s:%d)", #call,   \
-                     hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-  } while (0)
-
-static bool finite_f(float v) { return v >= -3.4028234663852886e38f && v <= 3.4028234663852886e38f; }
+using pt_stage::finite_f;
 
 static void srgb_table(float out[255]) {
   for (int k = 1; k <= 255; k++) {
@@ -245,15 +237,15 @@ static int enqueue_frames(const char* who, pt_tonemap* t, int n_frames, const fl
     const dim3 grid(t->blocks, (unsigned)n), block(BLOCK);
     if (automatic) {
       hipLaunchKernelGGL(meter_kernel, grid, block, 0, s, im, t->blocks, t->d_partials);
-      PTM_HIP(hipGetLastError());
+      PT_HIP(hipGetLastError());
       hipLaunchKernelGGL(adapt_kernel, dim3(1), block, 0, s, (const ulonglong2*)t->d_partials, t->blocks, n, t->has_history ? 0 : 1,
                          t->opts.key, t->opts.adapt, t->d_state, t->d_exposures);
-      PTM_HIP(hipGetLastError());
+      PT_HIP(hipGetLastError());
       t->has_history = true;
     }
     hipLaunchKernelGGL(map, grid, block, 0, s, im, automatic ? (const float*)t->d_exposures : (const float*)nullptr, t->opts.exposure, w2,
                        (const float*)t->d_table, d_rgba8 + (size_t)f0 * dst_stride_pixels, dst_stride_pixels);
-    PTM_HIP(hipGetLastError());
+    PT_HIP(hipGetLastError());
   }
   return PT_OK;
 }
@@ -262,15 +254,9 @@ static int run_timed(const char* who, pt_tonemap* t, int n_frames, const float* 
                      uint32_t* d_rgba8, size_t dst_stride_pixels, float* ms_out) {
   const int rc0 = check_args(who, t, n_frames, d_src, src_stride_floats, pixel_stride, d_rgba8, dst_stride_pixels);
   if (rc0 != PT_OK) return rc0;
-  PTM_HIP(hipEventRecord(t->ev0, nullptr));
-  const int rc = enqueue_frames(who, t, n_frames, d_src, src_stride_floats, pixel_stride, d_rgba8, dst_stride_pixels, nullptr);
-  if (rc != PT_OK) return rc;
-  PTM_HIP(hipEventRecord(t->ev1, nullptr));
-  PTM_HIP(hipEventSynchronize(t->ev1));
-  float ms = 0.0f;
-  PTM_HIP(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-  if (ms_out) *ms_out = ms;
-  return PT_OK;
+  return pt_stage::run_timed(t->ev0, t->ev1, ms_out, [&] {
+    return enqueue_frames(who, t, n_frames, d_src, src_stride_floats, pixel_stride, d_rgba8, dst_stride_pixels, nullptr);
+  });
 }
 
 extern "C" {
@@ -294,8 +280,7 @@ int pt_tonemap_destroy(pt_tonemap* t) {
   if (!t) return PT_OK;
   if (t->d_table) (void)hipFree(t->d_table);  // (the state lives behind the table)
   if (t->d_partials) (void)hipFree(t->d_partials);
-  if (t->ev0) (void)hipEventDestroy(t->ev0);
-  if (t->ev1) (void)hipEventDestroy(t->ev1);
+  pt_stage::destroy_events(t);
   delete t;
   return PT_OK;
 }
@@ -306,10 +291,8 @@ int pt_tonemap_create(int width, int height, const pt_tonemap_opts* opts, pt_ton
   pt_tonemap_opts o;
   if (opts) o = *opts;
   else pt_tonemap_opts_default(&o);
-  if (width <= 0 || width > 16384) return pt_fail(PT_EINVAL, "pt_tonemap_create: width %d outside 1 .. 16384", width);
-  if (height <= 0 || height > 16384) return pt_fail(PT_EINVAL, "pt_tonemap_create: height %d outside 1 .. 16384", height);
-  if ((int64_t)width * height > 4096 * 4096)
-    return pt_fail(PT_EINVAL, "pt_tonemap_create: frame size %d x %d (width x height) exceeds 4096 x 4096 pixels", width, height);
+  int rc = pt_stage::check_frame_size("pt_tonemap_create", width, height);
+  if (rc != PT_OK) return rc;
   if (o.curve < PT_TONEMAP_CLAMP || o.curve > PT_TONEMAP_ACES)
     return pt_fail(PT_EINVAL, "pt_tonemap_create: curve %d is none of PT_TONEMAP_CLAMP, _REINHARD, _ACES", o.curve);
   if (o.encode != PT_ENCODE_SRGB && o.encode != PT_ENCODE_LINEAR)
@@ -320,15 +303,10 @@ int pt_tonemap_create(int width, int height, const pt_tonemap_opts* opts, pt_ton
   if (!(o.white >= 1e-18f && o.white <= 1e18f))
     return pt_fail(PT_EINVAL, "pt_tonemap_create: white %g outside 1e-18 .. 1e18 (its square must be a float)", (double)o.white);
   if (!(o.adapt > 0.0f && o.adapt <= 1.0f)) return pt_fail(PT_EINVAL, "pt_tonemap_create: adapt %g outside (0, 1]", (double)o.adapt);
-  int rc = check_frames("pt_tonemap_create", o.max_frames, width, height);
-  if (rc != PT_OK) return rc;
+  if ((rc = check_frames("pt_tonemap_create", o.max_frames, width, height)) != PT_OK) return rc;
   for (int k = 0; k < 2; k++)
     if (o.reserved[k] != 0) return pt_fail(PT_EINVAL, "pt_tonemap_create: reserved[%d] = %d must be 0", k, o.reserved[k]);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e == hipErrorNoDevice || (e == hipSuccess && n == 0))
-    return pt_fail(PT_ENODEVICE, "pt_tonemap_create: no HIP device visible (there is no CPU fallback)");
-  if (e != hipSuccess) return pt_fail(PT_EHIP, "pt_tonemap_create: hipGetDeviceCount: %s (no usable device)", hipGetErrorString(e));
+  if ((rc = pt_stage::check_device("pt_tonemap_create")) != PT_OK) return rc;
   pt_tonemap* t = new (std::nothrow) pt_tonemap();
   if (!t) return pt_fail(PT_ENOMEM, "pt_tonemap_create: out of host memory");
   t->width = width, t->height = height, t->opts = o;
@@ -338,16 +316,10 @@ int pt_tonemap_create(int width, int height, const pt_tonemap_opts* opts, pt_ton
   float host[256 + sizeof(State) / sizeof(float)] = {};
   srgb_table(host + 1);
   host[256] = 1.0f;  // State::e
-  e = hipMalloc((void**)&t->d_table, fixed_bytes());
+  hipError_t e = hipMalloc((void**)&t->d_table, fixed_bytes());
   if (e == hipSuccess) e = hipMemcpy(t->d_table, host, fixed_bytes(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&t->d_partials, group_bytes(t, t->max_frames));
-  if (e == hipSuccess) e = hipEventCreate(&t->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&t->ev1);
-  if (e != hipSuccess) {
-    rc = pt_fail(e == hipErrorNoDevice ? PT_ENODEVICE : PT_EHIP, "pt_tonemap_create: %s", hipGetErrorString(e));
-    pt_tonemap_destroy(t);
-    return rc;
-  }
+  if ((rc = pt_stage::create_events("pt_tonemap_create", e, t, pt_tonemap_destroy)) != PT_OK) return rc;
   t->d_state = reinterpret_cast<State*>(t->d_table + 256);
   t->d_exposures = reinterpret_cast<float*>(t->d_partials + (size_t)t->max_frames * t->blocks);
   *out = t;
@@ -368,14 +340,12 @@ int pt_tonemap_workspace_bytes(const pt_tonemap* t, uint64_t* bytes) {
 
 int pt_tonemap_reserve_frames(pt_tonemap* t, int max_frames) {
   if (!t) return pt_fail(PT_EINVAL, "pt_tonemap_reserve_frames: null tone mapper");
-  const int rc = check_frames("pt_tonemap_reserve_frames", max_frames, t->width, t->height);
+  int rc = check_frames("pt_tonemap_reserve_frames", max_frames, t->width, t->height);
   if (rc != PT_OK) return rc;
   if (max_frames <= t->max_frames) return PT_OK;
-  PTM_HIP(hipDeviceSynchronize());  // (the old partials may be in use; the state is not in this allocation)
-  ulonglong2* grown = nullptr;
-  PTM_HIP(hipMalloc((void**)&grown, group_bytes(t, max_frames)));
-  (void)hipFree(t->d_partials);
-  t->d_partials = grown;
+  const pt_stage::Buffer bufs[1] = {{(void**)&t->d_partials, group_bytes(t, max_frames), false}};  // (the state is not in this allocation)
+  rc = pt_stage::grow_workspace("pt_tonemap_reserve_frames", bufs, "%d frames (%zu bytes)", max_frames, group_bytes(t, max_frames));
+  if (rc != PT_OK) return rc;
   t->max_frames = max_frames;
   t->d_exposures = reinterpret_cast<float*>(t->d_partials + (size_t)max_frames * t->blocks);
   return PT_OK;
@@ -412,8 +382,8 @@ int pt_tonemap_exposure(pt_tonemap* t, float* out) {
     *out = 1.0f;
     return PT_OK;
   }
-  PTM_HIP(hipDeviceSynchronize());
-  PTM_HIP(hipMemcpy(out, &t->d_state->e, sizeof(float), hipMemcpyDeviceToHost));
+  PT_HIP(hipDeviceSynchronize());
+  PT_HIP(hipMemcpy(out, &t->d_state->e, sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 
