@@ -189,6 +189,19 @@ ABI = {
     "pt_tonemap_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp]),
     "pt_tonemap_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _fp]),
     "pt_tonemap_exposure": (ctypes.c_int, [_vp, _fp]),
+    "pt_compare_opts_default": (None, [_vp]),
+    "pt_compare_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "pt_compare_destroy": (ctypes.c_int, [_vp]),
+    "pt_compare_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_compare_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_compare_ssim_weights": (ctypes.c_int, [_fp]),
+    "pt_compare_enqueue": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp]),
+    "pt_compare_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _fp]),
+    "pt_compare_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp,
+                                                 ctypes.c_size_t, _vp]),
+    "pt_compare_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp,
+                                             ctypes.c_size_t, _fp]),
+    "pt_compare_result": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -1302,3 +1315,93 @@ def tonemap_frame(frame_or_rgb, tonemap=None, **opts):
     with _on_device(img, h * w * 4, owned=None if tonemap else tm) as (d_src, d_out):
         tm.run(d_src.ptr, d_out.ptr, pixel_stride=c)
         return d_out.download(np.uint8, (h, w, 4))
+
+
+# ---- frame comparison -----------------------------------------------------------------
+class CompareOpts(ctypes.Structure):
+    """pt_compare_opts (include/ptcore.h)."""
+    _fields_ = [("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class CompareValues(ctypes.Structure):
+    """pt_compare_values (include/ptcore.h)."""
+    _fields_ = [("sum_mse", ctypes.c_uint64), ("sum_relmse", ctypes.c_uint64), ("sum_ssim", ctypes.c_int64), ("pixels", ctypes.c_uint64),
+                ("saturated", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64), ("mse", ctypes.c_double), ("rms", ctypes.c_double),
+                ("psnr", ctypes.c_double), ("relmse", ctypes.c_double), ("ssim", ctypes.c_double)]
+
+
+def ssim_weights():
+    """pt_compare_ssim_weights: the eleven float32 weights of the SSIM window; host only."""
+    out = np.zeros(11, dtype=np.float32)
+    check(lib.pt_compare_ssim_weights(out.ctypes.data_as(_fp)))
+    return out
+
+
+class Compare(_BatchedStage):
+    """ctypes view of pt_compare: the comparison session for width x height images (DENOISER.md, "Frame comparison").  A call
+    reads two device images [H][W][pixel_stride] (14: a frame, 3: an rgb image; the two strides are independent), writes neither
+    and leaves clamped MSE, relMSE and SSIM of each frame on the device; d_map (optional) receives [H][W][3] = (m, r, s)."""
+    _destroy, _reserve = "pt_compare_destroy", "pt_compare_reserve_frames"
+
+    def __init__(self, width, height, max_frames=1):
+        opts = CompareOpts(max_frames=max_frames)
+        h = _vp()
+        check(lib.pt_compare_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height = width, height
+        self.max_frames = max_frames
+
+    def memory(self):
+        """{"workspace": bytes of the partial sums of all max_frames frames and of the records}."""
+        b = ctypes.c_uint64(0)
+        check(lib.pt_compare_workspace_bytes(self.handle, ctypes.byref(b)))
+        return {"workspace": int(b.value)}
+
+    def enqueue(self, d_img, d_ref, d_map=None, img_pixel_stride=CHANNELS, ref_pixel_stride=CHANNELS, stream=None):
+        check(lib.pt_compare_enqueue(self.handle, d_img, img_pixel_stride, d_ref, ref_pixel_stride, d_map, stream))
+
+    def run(self, d_img, d_ref, d_map=None, img_pixel_stride=CHANNELS, ref_pixel_stride=CHANNELS):
+        """Synchronous; returns device-event milliseconds."""
+        return self._timed(lib.pt_compare_run, d_img, img_pixel_stride, d_ref, ref_pixel_stride, d_map)
+
+    def _frame_strides(self, img_px, ref_px, img_stride, ref_stride, map_stride):
+        px = self.width * self.height
+        return (px * img_px if img_stride is None else img_stride, px * ref_px if ref_stride is None else ref_stride,
+                px * 3 if map_stride is None else map_stride)
+
+    def enqueue_frames(self, d_img, n, d_ref, d_map=None, img_pixel_stride=CHANNELS, ref_pixel_stride=CHANNELS, img_stride_floats=None,
+                       ref_stride_floats=None, map_stride_floats=None, stream=None):
+        """Asynchronous; frame k compares d_img + k * img_stride_floats with d_ref + k * ref_stride_floats (default: packed;
+        ref_stride_floats=0: one reference for all n frames): bit for bit n single enqueues."""
+        si, sr, sm = self._frame_strides(img_pixel_stride, ref_pixel_stride, img_stride_floats, ref_stride_floats, map_stride_floats)
+        check(lib.pt_compare_enqueue_frames(self.handle, n, d_img, si, img_pixel_stride, d_ref, sr, ref_pixel_stride, d_map, sm, stream))
+
+    def run_frames(self, d_img, n, d_ref, d_map=None, img_pixel_stride=CHANNELS, ref_pixel_stride=CHANNELS, img_stride_floats=None,
+                   ref_stride_floats=None, map_stride_floats=None):
+        """Synchronous enqueue_frames; returns device-event milliseconds."""
+        si, sr, sm = self._frame_strides(img_pixel_stride, ref_pixel_stride, img_stride_floats, ref_stride_floats, map_stride_floats)
+        return self._timed(lib.pt_compare_run_frames, n, d_img, si, img_pixel_stride, d_ref, sr, ref_pixel_stride, d_map, sm)
+
+    def result(self, k=0):
+        """Synchronous: frame k of the last call as a dict -- the integer sums (sum_mse, sum_relmse, sum_ssim), pixels, saturated,
+        nonfinite, and the doubles mse, rms, psnr, relmse, ssim."""
+        v = CompareValues()
+        check(lib.pt_compare_result(self.handle, k, ctypes.byref(v)))
+        return {name: getattr(v, name) for name, _ in CompareValues._fields_}
+
+    def results(self, n):
+        return [self.result(k) for k in range(n)]
+
+
+def compare_frames(img, ref, want_map=False, compare=None):
+    """Convenience for tests: upload two host images [H][W][C] (C = 14: a frame, 3: an rgb image, anything in 3 .. 64; the two may
+    differ in C), compare them on the GPU.  Returns the result dict, and the [H][W][3] map (m, r, s) too when want_map."""
+    img, ref = np.ascontiguousarray(img, dtype=np.float32), np.ascontiguousarray(ref, dtype=np.float32)
+    h, w, c = img.shape
+    if ref.shape[:2] != (h, w):
+        raise ValueError(f"compare_frames: image {w} x {h}, reference {ref.shape[1]} x {ref.shape[0]}")
+    cmp_ = compare or Compare(w, h)
+    with _on_device(img, ref, h * w * 12 if want_map else None, owned=None if compare else cmp_) as (d_img, d_ref, d_map):
+        cmp_.run(d_img.ptr, d_ref.ptr, _ptr(d_map), img_pixel_stride=c, ref_pixel_stride=ref.shape[2])
+        res = cmp_.result(0)
+        return (res, d_map.download(np.float32, (h, w, 3))) if want_map else res

@@ -16,6 +16,7 @@
 #include <new>
 
 #include "pt_stage.h"
+#include "pt_stage_device.h"
 
 namespace pttm {
 
@@ -38,28 +39,8 @@ struct Image {
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ float lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // (lane 0 holds the sum)
-}
-
-// the sum over the workgroup's lanes, valid in thread 0; `red` holds one word per wave
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();  // (the previous use of red is over)
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  uint64_t s = 0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; w++) s += red[w];
-  }
-  return s;
-}
+using pt_stage::lum;
+__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* red) { return pt_stage::block_sum<BLOCK>(v, red); }
 
 // partials[frame][workgroup] = {S, K} of the workgroup's 256 pixels.  Every workgroup writes its word: nothing to clear.
 __global__ void __launch_bounds__(BLOCK) meter_kernel(Image im, uint32_t blocks, ulonglong2* __restrict__ partials) {

@@ -21,7 +21,10 @@
 // after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts),
 // --tonemap CURVE (ToneMapper / pt_tonemap_*: every frame of the headless loop and every progressive pass goes through the
 // session after --temporal, --filter and -d, so that --tonemap-adapt acts as eye adaptation; the last frame's sRGB picture is
-// written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes).
+// written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes),
+// --compare REF.exr (FrameCompare / pt_compare_*: the final colour of every frame of the headless loop and of every progressive
+// pass is compared on the device with the colour of REF, an EXR of the same size read by ExrReader.h, after --temporal, --filter
+// and -d and before --tonemap; one "compare:" line per frame or pass).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,7 +40,9 @@
 #include "Camera.h"
 #include "DenoiseNet.h"
 #include "Denoiser.h"
+#include "ExrReader.h"
 #include "FeatureFilter.h"
+#include "FrameCompare.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
 #include "ProgressiveRenderer.h"
@@ -89,6 +94,7 @@ static void usage() {
                "  --tonemap-white arg           with --tonemap reinhard: luminance that maps to white (default 4)\n"
                "  --tonemap-adapt arg           with --tonemap: share of the way to the metered exposure per frame, (0, 1] (default 1)\n"
                "  --tonemap-encode arg          with --tonemap: srgb (default) | linear\n"
+               "  --compare arg                 compare every frame or pass with the colour of this EXR: rms, psnr, relmse, ssim\n"
             << std::endl;
 }
 
@@ -128,6 +134,8 @@ int main(int argc, const char** argv) {
   const char* tonemapOption = NULL;  // the first --exposure / --tonemap-* option seen
   double tonemapKey = 0.18, tonemapWhite = 4.0, tonemapAdapt = 1.0;
   bool tonemapKeyGiven = false, tonemapWhiteGiven = false, tonemapAdaptGiven = false;
+  // --compare REF.exr: the comparison session (pt_compare_*) after every other stage of a frame and before the tone mapper
+  std::string compareFile;
   void* batch_frames = NULL;
 
   for (int i = 1; i < argc; i++) {
@@ -174,6 +182,7 @@ int main(int argc, const char** argv) {
     else if (a == "--tonemap-white") { tonemapWhite = atof(value("--tonemap-white")); tonemapWhiteGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-white"; }
     else if (a == "--tonemap-adapt") { tonemapAdapt = atof(value("--tonemap-adapt")); tonemapAdaptGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-adapt"; }
     else if (a == "--tonemap-encode") { tonemapEncode = value("--tonemap-encode"); if (!tonemapOption) tonemapOption = "--tonemap-encode"; }
+    else if (a == "--compare") compareFile = value("--compare");
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
@@ -338,6 +347,23 @@ int main(int argc, const char** argv) {
     }
     tonemapOpts.key = (float)tonemapKey, tonemapOpts.white = (float)tonemapWhite, tonemapOpts.adapt = (float)tonemapAdapt;
   }
+  ptexr::FeatureImage compareReference;
+  if (!compareFile.empty()) {  // (before any device is touched, and before anything is rendered)
+    if (batch) {
+      std::cerr << "ERROR: --compare cannot be combined with --batch: the comparison runs after every frame of the loop" << std::endl;
+      return 1;
+    }
+    std::string why;
+    if (!ptexr::LoadFeatureEXR(compareFile, &compareReference, &why)) {
+      std::cerr << "ERROR: --compare " << compareFile << ": " << why << std::endl;
+      return 1;
+    }
+    if (compareReference.width != width || compareReference.height != height) {
+      std::cerr << "ERROR: --compare " << compareFile << ": the reference is " << compareReference.width << " x " << compareReference.height
+                << ", the frame " << width << " x " << height << std::endl;
+      return 1;
+    }
+  }
   if ((adaptiveGiven || adaptiveMinGiven || adaptiveRadiusGiven) && !progressiveGiven) {  // (before any device is touched)
     std::cerr << "ERROR: " << (adaptiveGiven ? "--adaptive" : adaptiveMinGiven ? "--adaptive-min" : "--adaptive-radius")
               << " needs --progressive: adaptive sampling refines a progressive session" << std::endl;
@@ -423,12 +449,23 @@ int main(int argc, const char** argv) {
   if (accumulator && filter) gpuErrchk(pt_malloc((void**)&d_temporalCounts, (size_t)width * height * sizeof(unsigned int)));
   // --tonemap: likewise; it reads the frame the other stages left and writes its own RGBA8 image
   ToneMapper* mapper = tonemapGiven ? new ToneMapper(width, height, tonemapOpts) : NULL;
-  float denoiseTime = 0.0f, filterTime = 0.0f, temporalTime = 0.0f, tonemapTime = 0.0f;
+  // --compare: likewise; it reads the frame the other stages left, before the tone mapper, and writes nothing
+  FrameCompare* comparison = compareFile.empty() ? NULL : new FrameCompare(width, height, compareReference.buffer.data());
+  float denoiseTime = 0.0f, filterTime = 0.0f, temporalTime = 0.0f, tonemapTime = 0.0f, compareTime = 0.0f;
+  auto compare = [&](const OutputBuffer& b) {
+    compareTime = comparison->Compare(b);
+    const pt_compare_values v = comparison->Result();
+    char text[256];
+    snprintf(text, sizeof(text), "compare: rms %.17g psnr %.17g relmse %.17g ssim %.17g (saturated %llu, nonfinite %llu)", v.rms, v.psnr,
+             v.relmse, v.ssim, (unsigned long long)v.saturated, (unsigned long long)v.nonfinite);
+    std::cout << text << std::endl;
+  };
   auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
     if (accumulator) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, d_temporalCounts);
     if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
     if (filter) filterTime = filter->Filter(b, samplesPerPixel, d_temporalCounts);
+    if (comparison) compare(b);
     if (mapper) tonemapTime = mapper->Map(b);
     return ms;
   };
@@ -509,6 +546,7 @@ int main(int argc, const char** argv) {
       if (adaptiveGiven) session.Counts(d_counts);
       // --filter: with the session's count so far; under --adaptive with every pixel's own count
       if (filter) filterTime = filter->Filter(d_buffer, (int)session.Samples(), d_counts);
+      if (comparison) compare(d_buffer);
       if (mapper) tonemapTime = mapper->Map(d_buffer);
       if (adaptiveGiven) {
         gpuErrchk(pt_memcpy_d2h(counts.data(), d_counts, counts.size() * sizeof(unsigned int)));
@@ -534,6 +572,7 @@ int main(int argc, const char** argv) {
   if (accumulator) std::cout << "Temporal accumulation completed in " << temporalTime << "ms" << std::endl;
   if (net) std::cout << "Denoise completed in " << denoiseTime << "ms" << std::endl;
   if (filter) std::cout << "Filter completed in " << filterTime << "ms" << std::endl;
+  if (comparison) std::cout << "Comparison completed in " << compareTime << "ms" << std::endl;
   if (mapper) std::cout << "Tone mapping completed in " << tonemapTime << "ms (exposure " << mapper->Exposure() << ")" << std::endl;
   if (tiled) {
     std::cout << "Tile kernel times:";
@@ -578,6 +617,7 @@ int main(int argc, const char** argv) {
   delete net;
   delete filter;
   delete accumulator;
+  delete comparison;
   delete mapper;
   if (d_temporalCounts) (void)pt_free(d_temporalCounts);
   delete single;

@@ -565,6 +565,90 @@ int pt_tonemap_run_frames(pt_tonemap* t, int n_frames, const float* d_src, size_
  * frame and after a reset. */
 int pt_tonemap_exposure(pt_tonemap* t, float* out);
 
+/* ---- frame comparison: clamped MSE, relMSE and SSIM against a reference ------------------------ */
+/* How far an image is from its reference, measured on the device: the stage beside the four above, for whoever chooses a filter
+ * sigma, a denoiser precision, an adaptive tolerance or a temporal cap.  The reference renders every pose twice (2 spp and
+ * 20000 spp) and judges one against the other off the device; this stage keeps both frames where they are.  A session belongs
+ * to one frame size.  It reads two device images and writes neither; the results stay on the device until pt_compare_result
+ * asks for them.  EXACT code, like the tone mapper's: float32 adds, multiplies, divides and compares without contraction, and
+ * integer sums, so the kernels equal the float32 restatement (tests/compare_model.py) bit for bit and the sums do not depend
+ * on their order.  DENOISER.md, "Frame comparison", says the same.
+ *   input     two device images [height][width][pixel_stride], each with its own pixel_stride in 3 .. 64, colour in the first
+ *             three floats of a pixel (14: a frame, 3: an rgb image).
+ *   1 sanitise  per channel x = c > 0 ? c : 0 (NaN becomes 0);  x = x < 65504 ? x : 65504: a for the image, b for the reference.
+ *             A pixel with a non-finite colour channel in either input counts once in `nonfinite`.  Display values:
+ *             a' = a < 1 ? a : 1, b' likewise.
+ *   2 MSE     per channel d = a' - b';  t = d d;  per pixel m = (t0 + t1) + t2 <= 3: what a display shows.
+ *   3 relMSE  per channel d = a - b;  t = (d d) / (b b + 0.01f);  t = t < 1024 ? t : 1024, and a channel that hit the cap counts
+ *             in `saturated`;  per pixel r = (t0 + t1) + t2 <= 3072.
+ *   4 SSIM    Wang et al.: 11 x 11 Gaussian window, sigma 1.5, L = 1, C1 = 0.01f 0.01f, C2 = 0.03f 0.03f, on la = lum(a') and
+ *             lb = lum(b') (lum: the tone mapper's).  The 11 weights w are formed on the host in double, exp(-(k - 5)^2 / 4.5)
+ *             divided by their sum, and rounded to float32 (pt_compare_ssim_weights).  The filter is separable, first along a
+ *             row, then along a column, on the five quantities la, lb, la la, lb lb, la lb;  a pass is
+ *             v = w[0] q[-5];  v = v + w[k] q[k - 5] for k = 1 .. 10, and coordinates clamp to the frame (edges replicate), so
+ *             every pixel has a window and a 1 x 1 frame is legal.  With the filtered values ua, ub, Eaa, Ebb, Eab:
+ *             va = Eaa - ua ua;  vb = Ebb - ub ub;  cab = Eab - ua ub;
+ *             s = ((2 (ua ub) + C1) (2 cab + C2)) / (((ua ua + ub ub) + C1) ((va + vb) + C2)).
+ *   5 sums    per pixel qm = (uint64)floor((double)m 2^34), qr = (uint64)floor((double)r 2^24), qs = (int64)floor((double)s 2^32);
+ *             a frame's three sums are 64-bit integers (each term is below 2^36 in size, a group has at most 2^26 pixels).
+ *   6 result  mse = (double)sum qm / 2^34 / (3 pixels);  rms = sqrt(mse);  psnr = mse > 0 ? -10 log10(mse) : +inf;
+ *             relmse = (double)sum qr / 2^24 / (3 pixels);  ssim = (double)sum qs / 2^32 / pixels.
+ *   7 map     optional: d_map[3 p ..] = (m, r, s) of pixel p, an error picture.
+ * Launches: two per group of up to max_frames frames (one workgroup per 16 x 16 tile writes its partial sums into the
+ * workspace; one workgroup adds them into the frames' records).  No float atomics, no memset, no host synchronisation.
+ * Workspace: per frame of a group 32 bytes per tile, and 40 bytes per frame of the largest call so far
+ * (pt_compare_workspace_bytes).  One session's calls share its workspace and are ordered by the stream: do not run two of them
+ * concurrently. */
+typedef struct pt_compare_opts {
+  int32_t max_frames;  /* frames per group, >= 1 (default 1) */
+  int32_t reserved[3]; /* must be 0                          */
+} pt_compare_opts;
+typedef struct pt_compare_values {
+  uint64_t sum_mse;    /* the sum of qm                                        */
+  uint64_t sum_relmse; /* the sum of qr                                        */
+  int64_t sum_ssim;    /* the sum of qs                                        */
+  uint64_t pixels;     /* width x height                                       */
+  uint64_t saturated;  /* channels whose relMSE term hit the cap of 1024       */
+  uint64_t nonfinite;  /* pixels with a NaN or an infinity in either input     */
+  double mse, rms, psnr, relmse, ssim; /* step 6                               */
+} pt_compare_values;
+typedef struct pt_compare pt_compare; /* opaque: the weights, the partial sums and the records of one frame size */
+void pt_compare_opts_default(pt_compare_opts* opts);
+/* opts may be NULL (= defaults).  Every option and size is validated BEFORE a device is touched (the size limits are
+ * pt_filter_create's, max_frames' those of pt_filter_reserve_frames); a bad value is PT_EINVAL naming the argument.  Allocates
+ * the workspace on the current device. */
+int pt_compare_create(int width, int height, const pt_compare_opts* opts, pt_compare** out);
+int pt_compare_destroy(pt_compare* c);
+int pt_compare_workspace_bytes(const pt_compare* c, uint64_t* bytes);
+/* Grows the workspace for groups of up to max_frames frames, with pt_filter_reserve_frames' limits and rules; the results of
+ * the last call are kept. */
+int pt_compare_reserve_frames(pt_compare* c, int max_frames);
+/* Host only: the eleven float32 weights of step 4. */
+int pt_compare_ssim_weights(float out[11]);
+/* Compares the device image d_img with its reference d_ref, asynchronous on hip_stream (NULL = default stream).  d_map may be
+ * NULL; otherwise it receives width x height x 3 floats.  A null session, image or reference, or a pixel stride outside
+ * 3 .. 64, is PT_EINVAL naming the argument; nothing is launched and the results of the last call stay as they were. */
+int pt_compare_enqueue(pt_compare* c, const float* d_img, int img_pixel_stride, const float* d_ref, int ref_pixel_stride, float* d_map,
+                       void* hip_stream);
+/* The same, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events around it. */
+int pt_compare_run(pt_compare* c, const float* d_img, int img_pixel_stride, const float* d_ref, int ref_pixel_stride, float* d_map,
+                   float* ms_out);
+/* n frames, bit for bit what n single calls give: frame k compares d_img + k * img_stride_floats with
+ * d_ref + k * ref_stride_floats and writes its map to d_map + k * map_stride_floats.  ref_stride_floats == 0 is ONE reference
+ * for all n frames: the convergence curve of a session's passes, or of a fly-through's frames, against one converged picture.
+ * Otherwise strides may leave gaps (img_stride_floats >= width x height x img_pixel_stride, likewise the reference's;
+ * map_stride_floats >= width x height x 3 when d_map is given).  A group of up to max_frames frames goes out in two launches.
+ * A call with more frames than any call before first makes room for their records, which waits for the device once.
+ * n_frames < 1, a stride too small, and everything pt_compare_enqueue refuses is PT_EINVAL and nothing is launched. */
+int pt_compare_enqueue_frames(pt_compare* c, int n_frames, const float* d_img, size_t img_stride_floats, int img_pixel_stride,
+                              const float* d_ref, size_t ref_stride_floats, int ref_pixel_stride, float* d_map, size_t map_stride_floats,
+                              void* hip_stream);
+int pt_compare_run_frames(pt_compare* c, int n_frames, const float* d_img, size_t img_stride_floats, int img_pixel_stride, const float* d_ref,
+                          size_t ref_stride_floats, int ref_pixel_stride, float* d_map, size_t map_stride_floats, float* ms_out);
+/* Synchronous (it waits for the device): *out = steps 5 and 6 for frame frame_index of the last accepted call (0 for a single
+ * call).  A frame_index outside the last call's frames, also before the first call, is PT_EINVAL. */
+int pt_compare_result(pt_compare* c, int frame_index, pt_compare_values* out);
+
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
  * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.
