@@ -202,6 +202,17 @@ ABI = {
     "pt_compare_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp,
                                              ctypes.c_size_t, _fp]),
     "pt_compare_result": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_patches_opts_default": (None, [_vp]),
+    "pt_patches_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "pt_patches_destroy": (ctypes.c_int, [_vp]),
+    "pt_patches_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_patches_prepare": (ctypes.c_int, [_vp, _vp, _vp]),
+    "pt_patches_score": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
+    "pt_patches_result": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_patches_gather": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "pt_patches_run_prepare": (ctypes.c_int, [_vp, _vp, _fp]),
+    "pt_patches_run_score": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _fp]),
+    "pt_patches_run_gather": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _fp]),
     "pt_progressive_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "pt_progressive_reset": (ctypes.c_int, [_vp]),
     "pt_progressive_enqueue": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _fp, _fp, _vp]),
@@ -1405,3 +1416,134 @@ def compare_frames(img, ref, want_map=False, compare=None):
         cmp_.run(d_img.ptr, d_ref.ptr, _ptr(d_map), img_pixel_stride=c, ref_pixel_stride=ref.shape[2])
         res = cmp_.result(0)
         return (res, d_map.download(np.float32, (h, w, 3))) if want_map else res
+
+
+# ---- training patches -----------------------------------------------------------------
+class PatchesOpts(ctypes.Structure):
+    """pt_patches_opts (include/ptcore.h)."""
+    _fields_ = [("patch", ctypes.c_int32), ("max_patches", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class PatchesValues(ctypes.Structure):
+    """pt_patches_values (include/ptcore.h)."""
+    _fields_ = [("colour_s1", ctypes.c_int64), ("colour_a", ctypes.c_uint64), ("colour_b", ctypes.c_uint64), ("colour_c", ctypes.c_uint64),
+                ("normal_s1", ctypes.c_int64), ("normal_a", ctypes.c_uint64), ("normal_b", ctypes.c_uint64), ("normal_c", ctypes.c_uint64),
+                ("values", ctypes.c_uint64), ("var_colour", ctypes.c_double), ("var_normal", ctypes.c_double), ("score", ctypes.c_double)]
+
+
+def _corner_array(corners):
+    """Corners as the C ABI takes them: a contiguous int32 [n][2] host array of (x, y)."""
+    a = np.asarray(corners, dtype=np.int64).reshape(-1, 2)
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("a corner does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class Patches(_Session):
+    """ctypes view of pt_patches: the training-patch session for width x height frames, patches of `patch` x `patch` pixels, up
+    to max_patches per call (DENOISER.md, "Training patches").  prepare(d_train) meters the frame's divisors; score and gather take
+    the same device [H][W][14] frame again with host corners [(x, y), ...] and write neither it nor the target image."""
+    _destroy = "pt_patches_destroy"
+
+    def __init__(self, width, height, patch, max_patches=64):
+        opts = PatchesOpts(patch=patch, max_patches=max_patches)
+        h = _vp()
+        check(lib.pt_patches_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
+        self.handle = h.value
+        self.width, self.height, self.patch, self.max_patches = width, height, patch, max_patches
+
+    def memory(self):
+        """{"workspace": device bytes of the maxima, the corners, the partial sums and the records}."""
+        b = ctypes.c_uint64(0)
+        check(lib.pt_patches_workspace_bytes(self.handle, ctypes.byref(b)))
+        return {"workspace": int(b.value)}
+
+    def prepare(self, d_train, stream=None):
+        """Asynchronous: the divisors of this frame; needed again for every new frame."""
+        check(lib.pt_patches_prepare(self.handle, d_train, stream))
+
+    def run_prepare(self, d_train):
+        """Synchronous prepare; returns device-event milliseconds."""
+        return self._timed(lib.pt_patches_run_prepare, d_train)
+
+    def enqueue_score(self, d_train, corners, stream=None):
+        c = _corner_array(corners)
+        check(lib.pt_patches_score(self.handle, d_train, len(c), c.ctypes.data, stream))
+
+    def score(self, d_train, corners):
+        """Synchronous enqueue_score; returns device-event milliseconds (the values: result / results)."""
+        c = _corner_array(corners)
+        return self._timed(lib.pt_patches_run_score, d_train, len(c), c.ctypes.data)
+
+    def result(self, k=0):
+        """Synchronous: patch k of the last score call as a dict -- the eight integer sums, values, and the doubles var_colour,
+        var_normal, score."""
+        v = PatchesValues()
+        check(lib.pt_patches_result(self.handle, k, ctypes.byref(v)))
+        return {name: getattr(v, name) for name, _ in PatchesValues._fields_}
+
+    def results(self, n):
+        return [self.result(k) for k in range(n)]
+
+    def enqueue_gather(self, d_train, corners, d_inputs, d_gt=None, d_targets=None, gt_pixel_stride=CHANNELS, stream=None):
+        """Asynchronous: d_inputs receives [n][14][P][P] floats, d_targets (optional, from the device image d_gt) [n][3][P][P]."""
+        c = _corner_array(corners)
+        check(lib.pt_patches_gather(self.handle, d_train, d_gt, gt_pixel_stride, len(c), c.ctypes.data, d_inputs, d_targets, stream))
+
+    def gather(self, d_train, corners, d_inputs, d_gt=None, d_targets=None, gt_pixel_stride=CHANNELS):
+        """Synchronous enqueue_gather; returns device-event milliseconds."""
+        c = _corner_array(corners)
+        return self._timed(lib.pt_patches_run_gather, d_train, d_gt, gt_pixel_stride, len(c), c.ctypes.data, d_inputs, d_targets)
+
+
+def pick_patches(scores, n, rng):
+    """The reference's selection among scored candidates (load_data.py: get_patches): the total of the scores is fixed once;
+    the remaining candidates are scanned in order, each taken with probability score / total -- or unconditionally once more
+    than 10 n candidates have been passed over; a take removes the candidate and restarts the scan, until n are taken.  rng is a
+    random.Random (one random() per candidate looked at).  A total of 0 makes every probability 0, where the reference would
+    divide by zero.  Returns the n indices into `scores`, in the order taken."""
+    scores = [float(s) for s in scores]
+    if n > len(scores):
+        raise ValueError(f"pick_patches: n = {n} of {len(scores)} candidates")
+    total = 0.0
+    for s in scores:
+        total += s
+    left, picked, passed = list(range(len(scores))), [], 0
+    while len(picked) < n:
+        for pos, k in enumerate(left):
+            p = scores[k] / total if total != 0.0 else 0.0
+            if rng.random() < p or passed > 10 * n:
+                picked.append(k)
+                del left[pos]
+                break
+            passed += 1
+    return picked
+
+
+def training_patches(train, gt, patch_size=256, num_patches=16, rng=None, patches=None):
+    """The reference's get_patches on the device: from a host train frame [H][W][14] and a host target image [H][W][C] (C in
+    3 .. 64, colour first), draw 4 num_patches corners with rng (a random.Random; x then y, each from the reference's range
+    randint(0, side - patch_size - 1)), score them on the GPU, pick num_patches with pick_patches and gather those.  Returns
+    (inputs [N][14][P][P], targets [N][3][P][P], corners int32 [N][2] as (x, y), scores float64 [N]) of the picked patches.
+    patches: a Patches session of this frame size and patch_size with max_patches >= 4 num_patches, instead of one made here."""
+    import random
+
+    train, gt = np.ascontiguousarray(train, dtype=np.float32), np.ascontiguousarray(gt, dtype=np.float32)
+    h, w, c = train.shape
+    if c != CHANNELS or gt.shape[:2] != (h, w):
+        raise ValueError(f"training_patches: train {train.shape}, target {gt.shape}: [H][W][14] and [H][W][C] of one size")
+    rng = rng or random.Random()
+    p, n, cand = patch_size, num_patches, 4 * num_patches
+    ps = patches or Patches(w, h, p, max_patches=cand)
+    if (ps.width, ps.height, ps.patch) != (w, h, p) or ps.max_patches < cand:
+        raise ValueError(f"training_patches: the session is for {ps.width} x {ps.height}, patch {ps.patch}, {ps.max_patches} patches")
+    corners = [(rng.randint(0, max(w - p - 1, 0)), rng.randint(0, max(h - p - 1, 0))) for _ in range(cand)]
+    with _on_device(train, gt, n * 14 * p * p * 4, n * 3 * p * p * 4, owned=None if patches else ps) as (d_train, d_gt, d_in, d_out):
+        ps.prepare(d_train.ptr)
+        ps.score(d_train.ptr, corners)
+        scores = [r["score"] for r in ps.results(cand)]
+        picked = pick_patches(scores, n, rng)
+        chosen = _corner_array([corners[k] for k in picked])
+        ps.gather(d_train.ptr, chosen, d_in.ptr, d_gt=d_gt.ptr, d_targets=d_out.ptr, gt_pixel_stride=gt.shape[2])
+        return (d_in.download(np.float32, (n, 14, p, p)), d_out.download(np.float32, (n, 3, p, p)), chosen,
+                np.array([scores[k] for k in picked], dtype=np.float64))

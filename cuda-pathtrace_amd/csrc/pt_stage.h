@@ -1,5 +1,5 @@
 // pt_stage.h -- the host scaffold of a post-process stage session (pt_denoise.hip, pt_filter.hip, pt_temporal.hip,
-// pt_tonemap.hip, pt_compare.hip): the checks, the timed run, the workspace growth and the create / destroy tail that every stage needs and
+// pt_tonemap.hip, pt_compare.hip, pt_patches.hip): the checks, the timed run, the workspace growth and the create / destroy tail that every stage needs and
 // none should spell out again.  Host code only; a stage keeps its own plain struct (with `hipEvent_t ev0, ev1`), its option
 // checks, its check_args, its launch loops and its kernels.  Every helper takes the caller's `who` for the message.
 #pragma once

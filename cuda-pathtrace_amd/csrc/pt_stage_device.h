@@ -1,4 +1,4 @@
-// pt_stage_device.h -- the device code that the exact post-process stages share (pt_tonemap.hip, pt_compare.hip): the luminance
+// pt_stage_device.h -- the device code that the exact post-process stages share (pt_tonemap.hip, pt_compare.hip, pt_patches.hip): the luminance
 // and the integer sum over a workgroup, which is exact in any order.  EXACT code, like the kernels that use it: no contraction.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -649,6 +649,86 @@ int pt_compare_run_frames(pt_compare* c, int n_frames, const float* d_img, size_
  * call).  A frame_index outside the last call's frames, also before the first call, is PT_EINVAL. */
 int pt_compare_result(pt_compare* c, int frame_index, pt_compare_values* out);
 
+/* ---- training patches: pre-process, score and gather on the device ------------------------------ */
+/* From a (train frame, target image) pair on the device, what a CNN's data loader consumes: the pre-processed inputs
+ * [N][14][P][P] and the clamped targets [N][3][P][P] of N square patches, and the score by which patches are chosen.  This is
+ * what the reference's denoise_cnn/load_data.py computes off the device in float64 (load_exr_data's pre-processing, get_score,
+ * the crops of get_patches); the pre-processing here is the one pt_denoiser_* applies at inference, bit for bit
+ * (tests/denoise_restatement.py: preprocess).  Training itself stays with the caller.  EXACT code, like the tone mapper's and
+ * the comparison's: float32 divides and compares without contraction and integer sums, so the kernels equal the float32
+ * restatement (tests/patches_model.py) bit for bit and the sums do not depend on their order.  DENOISER.md, "Training patches",
+ * says the same.
+ *   input     a train frame [height][width][14] (pixel stride 14 only) and a target image [height][width][gt_pixel_stride],
+ *             stride 3 .. 64, colour in the first three floats.  Neither is ever written.
+ *   session   belongs to (width, height, patch P, max_patches K): 1 <= P <= min(width, height, 1024), 1 <= K <= 65535,
+ *             K P P <= 2^26.
+ *   indices   "row" and "column" are the frame's first and second index as it lies in memory: the orientation in which the
+ *             project's own Denoiser sees a frame.  The reference's tensors are the transpose (swapaxes(0, 2)), in training
+ *             and in inference alike: the one deliberate difference.
+ *   1 divisors  m_k = the maximum of channel k in 9 .. 13 over the WHOLE train frame, by fmaxf from -inf (NaNs are ignored);
+ *             div_k = (float)(0.00316 + (double)m_k);  EPS = 0.00316f.
+ *   2 pixel   x[0..2] = colour / (EPS + albedo), an IEEE float32 divide;  x[3..8] unchanged;  x[9..13] = c / div_k.
+ *   3 score   of the patch with corner (cx, cy), 0 <= cx <= width - P, 0 <= cy <= height - P.  Two populations of 3 P P values:
+ *             the pre-processed colour x[0..2] and the normal x[3..5].  Per value: colour v = x > 0 ? x : 0 (NaN becomes 0),
+ *             v = v < 65504 ? v : 65504;  normal NaN becomes 0, then clamped to +-65504;  q = (int64)floor((double)v 2^20).
+ *             Per population, with a = |q|, ah = a >> 18, al = a & (2^18 - 1):  S1 = sum q (int64);  A = sum ah ah,
+ *             B = sum ah al, C = sum al al (uint64): all exact in 64 bits for P <= 1024.  pt_patches_result then forms, in
+ *             128-bit integers, S2 = A 2^36 + B 2^19 + C (= sum q q), N = 3 P P, num = N S2 - S1 S1, and
+ *             var = ((double)num / (double)(N N)) / 2^40 (the conversion rounds to nearest even, N N is exact);
+ *             score = var_colour + var_normal.  This is get_score's np.var(colour) + np.var(normal), a pooled variance per
+ *             group of three channels, made independent of the order of summation and bounded: where the reference's float64
+ *             value would be inf or NaN this score is finite.
+ *   4 gather  inputs[k][c][j][i] = x[c] of pixel (cy_k + j, cx_k + i): the unsanitised value of step 2, NaNs pass as inference
+ *             would see them.  targets[k][c][j][i] = t, t = g > 0 ? g : 0;  t = t < 1 ? t : 1, g the target's colour:
+ *             np.clip(g, 0, 1) except that NaN becomes 0.  Both float32 and contiguous.
+ * Corners are a HOST array of n (x, y) int32 pairs.  Every corner is validated on the host before anything is launched: a
+ * corner outside 0 .. width - P / 0 .. height - P, n < 1 or n > max_patches is PT_EINVAL naming the index and the value, so no
+ * kernel is handed an address outside the caller's images.  They reach the device through a pinned buffer of the session and an
+ * asynchronous copy on the call's stream; the caller's array may be reused when the call returns.
+ * Launches: prepare one (per-workgroup maxima; whoever divides folds them), score two (per patch, one workgroup per 1024 pixels
+ * writes its eight sums; one workgroup per patch adds them into the patch's record), gather one.  No atomics, no memset, no
+ * host synchronisation.  One session's calls share its workspace and are ordered by the stream: do not run two concurrently. */
+typedef struct pt_patches_opts {
+  int32_t patch;       /* P, the side of a patch in pixels (default 64) */
+  int32_t max_patches; /* K, the most patches of one call (default 64)  */
+  int32_t reserved[2]; /* must be 0                                     */
+} pt_patches_opts;
+typedef struct pt_patches_values {
+  int64_t colour_s1;  /* S1 of the pre-processed colour */
+  uint64_t colour_a, colour_b, colour_c; /* A, B, C     */
+  int64_t normal_s1;  /* S1 of the normal               */
+  uint64_t normal_a, normal_b, normal_c;
+  uint64_t values;    /* N = 3 P P                      */
+  double var_colour, var_normal, score; /* step 3       */
+} pt_patches_values;
+typedef struct pt_patches pt_patches; /* opaque: the maxima, the corners, the partial sums and the records */
+void pt_patches_opts_default(pt_patches_opts* opts);
+/* opts may be NULL (= defaults).  Every option and size is validated BEFORE a device is touched (the frame's size limits are
+ * pt_filter_create's); a bad value is PT_EINVAL naming the argument.  Allocates the workspace on the current device. */
+int pt_patches_create(int width, int height, const pt_patches_opts* opts, pt_patches** out);
+int pt_patches_destroy(pt_patches* s);
+int pt_patches_workspace_bytes(const pt_patches* s, uint64_t* bytes);
+/* Step 1 for the frame d_train, asynchronous on hip_stream (NULL = default stream).  The maxima stay on the device.  A score or
+ * a gather before the first prepare is PT_EINVAL.  A new frame needs a new prepare: score and gather take the same frame again,
+ * and its CONTENT cannot be checked (the rule a progressive session has for its scene). */
+int pt_patches_prepare(pt_patches* s, const float* d_train, void* hip_stream);
+/* Step 3 for n corners, asynchronous; the records stay on the device until pt_patches_result asks for them.  A batch of n
+ * patches gives the records of n single calls. */
+int pt_patches_score(pt_patches* s, const float* d_train, int n, const int32_t* corners, void* hip_stream);
+/* Synchronous (it waits for the device): *out = step 3 for patch patch_index of the last accepted score call.  A patch_index
+ * outside that call's patches, also before the first call, is PT_EINVAL.  A gather in between changes nothing. */
+int pt_patches_result(pt_patches* s, int patch_index, pt_patches_values* out);
+/* Steps 2 and 4 for n corners, asynchronous: d_inputs receives n x 14 x P x P floats, d_targets (may be NULL; then d_gt and
+ * gt_pixel_stride are not looked at) n x 3 x P x P.  A null session, frame or d_inputs, a null d_gt or a gt_pixel_stride
+ * outside 3 .. 64 with d_targets given, is PT_EINVAL naming the argument; nothing is launched. */
+int pt_patches_gather(pt_patches* s, const float* d_train, const float* d_gt, int gt_pixel_stride, int n, const int32_t* corners,
+                      float* d_inputs, float* d_targets, void* hip_stream);
+/* The same three, synchronous on the default stream; *ms_out (may be NULL) = milliseconds between two device events. */
+int pt_patches_run_prepare(pt_patches* s, const float* d_train, float* ms_out);
+int pt_patches_run_score(pt_patches* s, const float* d_train, int n, const int32_t* corners, float* ms_out);
+int pt_patches_run_gather(pt_patches* s, const float* d_train, const float* d_gt, int gt_pixel_stride, int n, const int32_t* corners,
+                          float* d_inputs, float* d_targets, float* ms_out);
+
 /* ---- progressive rendering ------------------------------------------------------------ */
 /* A still frame refined pass by pass.  The reference renders the same frame again and again while the camera rests
  * (src/main.cu:146-177: Render() of `spp` fresh samples, pathtrace.cu:212-256); a session instead ADDS samples to one frame.
