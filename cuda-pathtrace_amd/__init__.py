@@ -255,6 +255,7 @@ LAB_ABI = {
     "pt_debug_denoiser_conv_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_filter_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "pt_debug_filter_tiled": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_debug_filter_state": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, _vp, _vp]),
     "pt_debug_progressive_set_samples": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "pt_debug_progressive_record": (ctypes.c_int, [_vp, _vp]),
     "pt_debug_progressive_set_active": (ctypes.c_int, [_vp, _vp]),
@@ -1129,6 +1130,20 @@ class FeatureFilter(_BatchedStage):
     def tiled(self, on):
         """Lab library only: steps 1 and 2 through the LDS tile (True) or with direct loads (False)."""
         check(self._lab("pt_debug_filter_tiled")(self.handle, int(bool(on))))
+
+    def state(self, d_frame, samples, steps=(), d_counts=None):
+        """Lab library only: the set-up and one UNFUSED iteration per entry of `steps` (none: the set-up alone) on the device
+        frame; returns host copies (state {ill.rgb, var}, guide {n.xyz, z}, guide {alb.rgb, dz}), each [H][W][4] float32."""
+        steps = [int(s) for s in steps]
+        arr = (ctypes.c_int * max(len(steps), 1))(*steps)
+        nbytes = self.width * self.height * 16
+        bufs = [DeviceBuffer(nbytes) for _ in range(3)]
+        try:
+            check(self._lab("pt_debug_filter_state")(self.handle, d_frame, samples, d_counts, arr, len(steps), *(b.ptr for b in bufs)))
+            return tuple(b.download(np.float32, (self.height, self.width, 4)) for b in bufs)
+        finally:
+            for b in bufs:
+                b.free()
 
 
 def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **opts):

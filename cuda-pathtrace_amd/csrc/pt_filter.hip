@@ -10,7 +10,9 @@
 //            caller's frame (or d_rgb), so no iteration ever reads the caller's frame and in-place use is safe.
 // Per tap: three 16-byte loads, one sum of the four stops, ONE exp2.  Per pixel: the reciprocals of the luminance stop and of
 // the depth stop's five distinct tap distances.  Steps 1 and 2 read an LDS tile of the workgroup's pixels and their halo, the
-// larger steps load directly (DENOISER.md, "Speed": the tile makes those two launches 1.7 times faster).
+// larger steps load directly (DENOISER.md, "Speed": the tile makes those two launches 1.7 times faster).  The lab library's
+// pt_debug_filter_state runs unfused iterations and copies the state and the guides out; tests/test_filter_exact_gpu.py holds
+// the set-up, every stop and var' to the bit with it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -140,10 +142,11 @@ __global__ void __launch_bounds__(BX* BY) atrous_kernel(Params p, int step, cons
     for (int k = -2; k <= 2; k++) {
       const int qx = x + k * step;
       const bool in = rowin && qx >= 0 && qx < p.width;
-      // a tap outside the frame is skipped: it reads a pixel inside the frame instead (direct: the pixel's own row / column;
-      // tiled: the clamped halo) and gets weight 0
+      // a tap outside the frame is skipped: it reads a pixel inside the frame instead (the pixel's own row / column, in both
+      // forms: one of its own taps, so a non-finite pixel reaches the same outputs through the tile and through direct loads)
+      // and gets weight 0
       const uint32_t q = qrow + (uint32_t)(qx >= 0 && qx < p.width ? qx : x);
-      const int tq = ti + j * TILE * TW + k * TILE;
+      const int tq = ti + (rowin ? j : 0) * TILE * TW + (qx >= 0 && qx < p.width ? k : 0) * TILE;
       const float4 sq = TILE ? ts[tq] : src[q], nq = TILE ? tn[tq] : g0[q], aq = TILE ? ta[tq] : g1[q];
       const float kj = j == 0 ? 0.375f : (j == 1 || j == -1) ? 0.25f : 0.0625f;
       const float kk = k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f;
@@ -187,17 +190,21 @@ static Params make_params(const pt_filter* f, size_t frame_stride, size_t out_st
   p.width = f->width, p.height = f->height;
   p.pixels = (uint32_t)f->width * (uint32_t)f->height;
   p.frame_stride = frame_stride, p.out_stride = out_stride, p.out_ld = out_ld;
-  const double log2e = 1.4426950408889634;
-  p.cn = (float)(log2e / ((double)f->opts.sigma_n * (double)f->opts.sigma_n));
-  p.ca = (float)(log2e / ((double)f->opts.sigma_a * (double)f->opts.sigma_a));
+  // clamped to the largest float: a sigma below about 6.6e-20 is a hard stop (0 stays 0, any difference is refused), where an
+  // infinite factor would make the centre tap's 0 x inf a NaN
+  const double log2e = 1.4426950408889634, flt_max = 3.4028234663852886e38;
+  p.cn = (float)fmin(log2e / ((double)f->opts.sigma_n * (double)f->opts.sigma_n), flt_max);
+  p.ca = (float)fmin(log2e / ((double)f->opts.sigma_a * (double)f->opts.sigma_a), flt_max);
   p.sz = f->opts.sigma_z, p.sl = f->opts.sigma_l;
   p.samples = (float)samples;
   return p;
 }
 
-// One group of g <= max_frames frames: prepare, then the iterations (steps[0 .. n_steps)), the last one fused.
+// One group of g <= max_frames frames: prepare, then the iterations (steps[0 .. n_steps)), the last one fused.  With `state`
+// (the lab library's pt_debug_filter_state) no iteration is fused, nothing is written to `out`, and *state receives the
+// workspace image that holds the state after the last iteration.
 static int launch_group(const pt_filter* f, const Params& p, int g, const float* frames, float* out, const uint32_t* counts,
-                        const int* steps, int n_steps, hipStream_t s) {
+                        const int* steps, int n_steps, hipStream_t s, const float4** state = nullptr) {
   const size_t n = (size_t)f->max_frames * p.pixels;
   float4 *a = f->d_ws, *b = f->d_ws + n, *g0 = f->d_ws + 2 * n, *g1 = f->d_ws + 3 * n;
   const dim3 block(BX, BY), grid((unsigned)((p.width + BX - 1) / BX), (unsigned)((p.height + BY - 1) / BY), (unsigned)g);
@@ -207,7 +214,7 @@ static int launch_group(const pt_filter* f, const Params& p, int g, const float*
                                        {atrous_kernel<true, 0>, atrous_kernel<true, 1>, atrous_kernel<true, 2>}};
   for (int k = 0; k < n_steps; k++) {
     const int tile = f->tiled && steps[k] <= 2 ? steps[k] : 0;
-    if (k == n_steps - 1) {
+    if (k == n_steps - 1 && !state) {
       hipLaunchKernelGGL(kernels[1][tile], grid, block, 0, s, p, steps[k], (const float4*)a, (const float4*)g0, (const float4*)g1,
                          (float4*)nullptr, out);
     } else {
@@ -217,6 +224,7 @@ static int launch_group(const pt_filter* f, const Params& p, int g, const float*
       a = b, b = t;
     }
   }
+  if (state) *state = a;
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -362,6 +370,29 @@ int pt_debug_filter_step(pt_filter* f, float* d_frame, float* d_rgb, int samples
   if (step < 1 || step > 4096) return pt_fail(PT_EINVAL, "pt_debug_filter_step: step %d outside 1 .. 4096", step);
   const Params p = make_params(f, pixels * 14, d_rgb ? pixels * 3 : pixels * 14, d_rgb ? 3 : 14, samples);
   if ((rc = launch_group(f, p, 1, d_frame, d_rgb ? d_rgb : d_frame, d_counts, &step, 1, nullptr)) != PT_OK) return rc;
+  PT_HIP(hipDeviceSynchronize());
+  return PT_OK;
+}
+
+int pt_debug_filter_state(pt_filter* f, const float* d_frame, int samples, const uint32_t* d_counts, const int* steps, int n_steps,
+                          float* d_state, float* d_guide0, float* d_guide1) {
+  const char* who = "pt_debug_filter_state";
+  const size_t pixels = f ? (size_t)f->width * f->height : 0;
+  int rc = check_frames_args(who, f, 1, d_frame, pixels * 14, nullptr, 0, samples, d_counts);
+  if (rc != PT_OK) return rc;
+  if (n_steps < 0 || n_steps > 8) return pt_fail(PT_EINVAL, "%s: n_steps %d outside 0 .. 8", who, n_steps);
+  if (n_steps > 0 && !steps) return pt_fail(PT_EINVAL, "%s: null steps", who);
+  for (int k = 0; k < n_steps; k++)
+    if (steps[k] < 1 || steps[k] > 4096) return pt_fail(PT_EINVAL, "%s: steps[%d] = %d outside 1 .. 4096", who, k, steps[k]);
+  if (!d_state || !d_guide0 || !d_guide1)
+    return pt_fail(PT_EINVAL, "%s: null %s", who, !d_state ? "d_state" : !d_guide0 ? "d_guide0" : "d_guide1");
+  const Params p = make_params(f, pixels * 14, pixels * 14, 14, samples);
+  const float4* state = nullptr;
+  if ((rc = launch_group(f, p, 1, d_frame, nullptr, d_counts, steps, n_steps, nullptr, &state)) != PT_OK) return rc;
+  const size_t n = (size_t)f->max_frames * p.pixels, bytes = pixels * sizeof(float4);
+  PT_HIP(hipMemcpy(d_state, state, bytes, hipMemcpyDeviceToDevice));
+  PT_HIP(hipMemcpy(d_guide0, f->d_ws + 2 * n, bytes, hipMemcpyDeviceToDevice));
+  PT_HIP(hipMemcpy(d_guide1, f->d_ws + 3 * n, bytes, hipMemcpyDeviceToDevice));
   PT_HIP(hipDeviceSynchronize());
   return PT_OK;
 }

@@ -136,6 +136,12 @@ int pt_debug_filter_step(pt_filter* f, float* d_frame, float* d_rgb, int samples
 /* on != 0: the iterations at steps 1 and 2 read an LDS tile (the workgroup's pixels and a clamped halo) instead of global
  * memory; the same bits (DENOISER.md, "Speed", has the measurement that decided the product's choice). */
 int pt_debug_filter_tiled(pt_filter* f, int on);
+/* The set-up and n_steps (0 .. 8) UNFUSED iterations at steps[k] (1 .. 4096 each), through the tile or direct loads as
+ * pt_debug_filter_tiled says; then the current state {ill.rgb, var} and the guides {n.xyz, z}, {alb.rgb, dz}, each
+ * [H][W][4] float32, are copied to d_state, d_guide0 and d_guide1.  The frame is only read.  d_frame, samples and d_counts as
+ * pt_filter_enqueue.  Synchronous. */
+int pt_debug_filter_state(pt_filter* f, const float* d_frame, int samples, const uint32_t* d_counts, const int* steps, int n_steps,
+                          float* d_state, float* d_guide0, float* d_guide1);
 
 /* Progressive sessions: set the session's sample count without rendering (the INT_MAX limit's test; the record is left as it
  * is, so the frames of later passes are meaningless).  samples < 0 is PT_EINVAL. */
