@@ -59,6 +59,23 @@ def test_preprocess_is_exact(pt, lab, gpu, sd):
         assert np.array_equal(bits(x0[..., :14]), bits(ref)) and not x0[..., 14:].any()
 
 
+def test_preprocess_finds_maxima_in_every_trip_of_the_reduction(pt, gpu, sd):
+    """520 x 516 (256 workgroups of pre_max_kernel, five trips each), the maxima of channels 9-13 planted where the scene never
+    puts them (tests/stage_sum_cases.py): the start of the second trip, the last pixel, the end of the first trip, pixel 0, the
+    third trip.  Channels 9-13 of the in-place frame have the restatement's bits."""
+    import stage_sum_cases as sc
+
+    frame = sc.patches_planted()[0]
+    with np.errstate(all="ignore"):
+        ref = R.preprocess(frame)
+    after = pt.denoise_frame(frame, sd)
+    for c in range(9, 14):
+        assert ref[..., c].max() == np.float32(sc.PLANTED_VALUES[c]) / np.float32(0.00316 + sc.PLANTED_VALUES[c])
+        bad = np.argwhere(bits(after[..., c]) != bits(ref[..., c]))
+        assert len(bad) == 0, f"channel {c} (maximum at pixel {sc.PLANTED[c]}): {len(bad)} differ, first (y, x) = {bad[0].tolist()}"
+    assert np.array_equal(bits(after[..., 3:9]), bits(frame[..., 3:9]))
+
+
 def _conv_ref64(x, w, stride, ks):
     """float64 conv of NHWC x with torch weight w (no bias): NHWC result."""
     xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).permute(2, 0, 1).unsqueeze(0)
