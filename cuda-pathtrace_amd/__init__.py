@@ -177,6 +177,14 @@ ABI = {
     "pt_temporal_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _fp]),
     "pt_temporal_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _vp]),
     "pt_temporal_run_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _fp]),
+    "pt_temporal_scene_check": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp]),
+    "pt_temporal_motion": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _fp, _fp, _vp, _vp]),
+    "pt_temporal_enqueue_motion": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _vp, _vp]),
+    "pt_temporal_run_motion": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _vp, _fp]),
+    "pt_temporal_enqueue_scene": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, ctypes.c_int, _vp, _vp]),
+    "pt_temporal_run_scene": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, ctypes.c_int, _vp, _fp]),
+    "pt_temporal_enqueue_frames_scenes": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "pt_temporal_run_frames_scenes": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, _vp, ctypes.c_int, ctypes.c_int, _vp, _fp]),
     "pt_tonemap_opts_default": (None, [_vp]),
     "pt_tonemap_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "pt_tonemap_destroy": (ctypes.c_int, [_vp]),
@@ -1203,7 +1211,8 @@ class Temporal(_Session):
         self.width, self.height = width, height
 
     def memory(self):
-        """{"workspace": bytes of the two history images, "per_pixel": bytes per pixel}."""
+        """{"workspace": bytes of the two history images (and, once a call with spheres= or scenes= needed it, of the session's
+        motion image), "per_pixel": bytes per pixel: 96, then 112}."""
         b = ctypes.c_uint64(0)
         check(lib.pt_temporal_workspace_bytes(self.handle, ctypes.byref(b)))
         return {"workspace": int(b.value), "per_pixel": int(b.value) // (self.width * self.height)}
@@ -1212,16 +1221,72 @@ class Temporal(_Session):
         """Forget the history: the next frame passes through."""
         check(lib.pt_temporal_reset(self.handle))
 
-    def enqueue(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None, stream=None):
-        _, b = _f32(basis, 12)
-        _, e = _f32(eye, 3)
-        check(lib.pt_temporal_enqueue(self.handle, d_frame, samples, b, e, d_counts, stream))
+    @staticmethod
+    def _spheres(spheres):
+        s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1)
+        return s, s.ctypes.data, len(s)
 
-    def run(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None):
-        """Synchronous; returns device-event milliseconds."""
+    @staticmethod
+    def _device_ptr(image):
+        """A device address from an int, a DeviceBuffer or a torch tensor."""
+        return image.data_ptr() if hasattr(image, "data_ptr") else getattr(image, "ptr", image)
+
+    def motion(self, spheres_now, spheres_prev, basis, eye=DEFAULT_EYE, out=None, stream=None):
+        """pt_temporal_motion: the motion image of two index-matched host scenes under (basis, eye), a float32 torch tensor
+        [H][W][4] {mx, my, mz, w} on the current device (synchronous).  Pass it as `motion=` to enqueue / run.
+        out: a DeviceBuffer (or any device address) of width x height x 16 bytes to write into instead, asynchronously on
+        `stream`, and to return: no torch is involved then."""
+        now, pn, n = self._spheres(spheres_now)
+        prev, pp, n_prev = self._spheres(spheres_prev)
+        if n != n_prev:
+            raise ValueError(f"motion: {n} spheres now, {n_prev} before: the scenes are index-matched")
         _, b = _f32(basis, 12)
         _, e = _f32(eye, 3)
+        if out is not None:
+            check(lib.pt_temporal_motion(self.handle, pn, pp, n, b, e, self._device_ptr(out), stream))
+            return out
+        import torch
+
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        check(lib.pt_temporal_motion(self.handle, pn, pp, n, b, e, out.data_ptr(), None))
+        torch.cuda.synchronize()
+        return out
+
+    def enqueue(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None, stream=None, motion=None, spheres=None):
+        """motion: a device motion image [H][W][4] (self.motion, or any device address); spheres: the HOST scene the frame was
+        rendered from (pt_temporal_enqueue_scene: the session remembers it and follows the spheres from call to call).  At most
+        one of the two."""
+        if motion is not None and spheres is not None:
+            raise ValueError("motion and spheres are mutually exclusive")
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        if spheres is not None:
+            _keep, ps, n = self._spheres(spheres)
+            check(lib.pt_temporal_enqueue_scene(self.handle, d_frame, samples, b, e, ps, n, d_counts, stream))
+        elif motion is not None:
+            check(lib.pt_temporal_enqueue_motion(self.handle, d_frame, samples, b, e, self._device_ptr(motion), d_counts, stream))
+        else:
+            check(lib.pt_temporal_enqueue(self.handle, d_frame, samples, b, e, d_counts, stream))
+
+    def run(self, d_frame, samples, basis, eye=DEFAULT_EYE, d_counts=None, motion=None, spheres=None):
+        """Synchronous; returns device-event milliseconds.  motion, spheres: as for enqueue."""
+        if motion is not None and spheres is not None:
+            raise ValueError("motion and spheres are mutually exclusive")
+        _, b = _f32(basis, 12)
+        _, e = _f32(eye, 3)
+        if spheres is not None:
+            _keep, ps, n = self._spheres(spheres)
+            return self._timed(lib.pt_temporal_run_scene, d_frame, samples, b, e, ps, n, d_counts)
+        if motion is not None:
+            return self._timed(lib.pt_temporal_run_motion, d_frame, samples, b, e, self._device_ptr(motion), d_counts)
         return self._timed(lib.pt_temporal_run, d_frame, samples, b, e, d_counts)
+
+    def _scenes(self, scenes, n_frames):
+        s = np.ascontiguousarray(scenes, dtype=SPHERE_DTYPE)
+        if s.ndim != 2 or s.shape[0] != n_frames:
+            raise ValueError(f"scenes: [{n_frames}][n] spheres expected, got shape {s.shape}")
+        return s, s.ctypes.data, s.shape[1]
 
     def _cameras(self, bases, eyes, frame_stride_floats):
         bases = np.ascontiguousarray(bases, dtype=np.float32).reshape(-1, 12)
@@ -1230,29 +1295,54 @@ class Temporal(_Session):
         fs = self.width * self.height * CHANNELS if frame_stride_floats is None else frame_stride_floats
         return bases, eyes, fs
 
-    def enqueue_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None, stream=None):
+    def enqueue_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None, stream=None, scenes=None):
         """Asynchronous; the n = len(bases) frames at d_frames + k * frame_stride_floats (default: packed) in order, bit for
-        bit n single enqueues; d_counts receives the last frame's counts."""
+        bit n single enqueues; d_counts receives the last frame's counts.  scenes: host spheres [n][n_spheres], the scene of
+        every frame (pt_temporal_enqueue_frames_scenes: bit for bit n single enqueues with spheres=)."""
         bases, eyes, fs = self._cameras(bases, eyes, frame_stride_floats)
+        if scenes is not None:
+            _keep, ps, n = self._scenes(scenes, len(bases))
+            check(lib.pt_temporal_enqueue_frames_scenes(self.handle, len(bases), d_frames, fs, bases.ctypes.data_as(_fp),
+                                                        eyes.ctypes.data_as(_fp), ps, n, samples, d_counts, stream))
+            return
         check(lib.pt_temporal_enqueue_frames(self.handle, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
                                              samples, d_counts, stream))
 
-    def run_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None):
+    def run_frames(self, d_frames, samples, bases, eyes, frame_stride_floats=None, d_counts=None, scenes=None):
         """Synchronous enqueue_frames; returns device-event milliseconds."""
         bases, eyes, fs = self._cameras(bases, eyes, frame_stride_floats)
+        if scenes is not None:
+            _keep, ps, n = self._scenes(scenes, len(bases))
+            return self._timed(lib.pt_temporal_run_frames_scenes, len(bases), d_frames, fs, bases.ctypes.data_as(_fp),
+                               eyes.ctypes.data_as(_fp), ps, n, samples, d_counts)
         return self._timed(lib.pt_temporal_run_frames, len(bases), d_frames, fs, bases.ctypes.data_as(_fp), eyes.ctypes.data_as(_fp),
                            samples, d_counts)
 
 
-def accumulate_frames(frames, samples, bases, eyes, temporal=None, **opts):
+MOTION_CHUNK = 256  # PT_MOTION_CHUNK (include/ptcore.h): spheres per round of the motion kernel's staging
+
+
+def temporal_scene_check(spheres_now, spheres_prev, basis, eye=DEFAULT_EYE):
+    """pt_temporal_scene_check: the host checks of Temporal.motion alone; host only.  Raises PtError for what it refuses."""
+    now = np.ascontiguousarray(spheres_now, dtype=SPHERE_DTYPE).reshape(-1)
+    prev = np.ascontiguousarray(spheres_prev, dtype=SPHERE_DTYPE).reshape(-1)
+    if len(now) != len(prev):
+        raise ValueError("the scenes are index-matched")
+    _, b = _f32(basis, 12)
+    _, e = _f32(eye, 3)
+    check(lib.pt_temporal_scene_check(now.ctypes.data, prev.ctypes.data, len(now), b, e))
+
+
+def accumulate_frames(frames, samples, bases, eyes, temporal=None, scenes=None, **opts):
     """Convenience for tests, like filter_frames: host frames [N][H][W][14] of one fly-through through ONE
     pt_temporal_run_frames call of a fresh session (or `temporal`, whose history then goes in).  Returns (the frames after the
-    stage, the uint32 [H][W] counts of the last frame).  opts: of the Temporal made here."""
+    stage, the uint32 [H][W] counts of the last frame).  scenes: host spheres [N][n], the scene of every frame (animated
+    scenes: pt_temporal_run_frames_scenes).  opts: of the Temporal made here."""
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
     ta = temporal or Temporal(w, h, **opts)
     with _on_device(frames, h * w * 4, owned=None if temporal else ta) as (d_frames, d_counts):
-        ta.run_frames(d_frames.ptr, samples, bases, eyes, d_counts=d_counts.ptr)
+        ta.run_frames(d_frames.ptr, samples, bases, eyes, d_counts=d_counts.ptr, scenes=scenes)
         return d_frames.download(np.float32, frames.shape), d_counts.download(np.uint32, (h, w))
 
 

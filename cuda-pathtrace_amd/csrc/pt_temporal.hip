@@ -5,12 +5,16 @@
 // reference.  DENOISER.md, "Temporal accumulation", states the definition; tests/temporal_model.py restates it in NumPy.
 // EXACT code, unlike pt_filter.hip: no contraction, no rcp, IEEE divisions -- the kernel is held to the float32 model bit for bit.
 //
-// One kernel, one lane per pixel, one launch per frame (frame k reads what frame k-1 wrote).  The two cameras are kernel
-// arguments; the history is three float4 images per pixel {colour, s2}, {normal, z}, {albedo, count}, two copies used
+// One accumulate kernel, one lane per pixel, one launch per frame (frame k reads what frame k-1 wrote).  The two cameras are
+// kernel arguments; the history is three float4 images per pixel {colour, s2}, {normal, z}, {albedo, count}, two copies used
 // ping-pong: a launch gathers four taps from one (16-byte loads) and writes the other.
+// Moving spheres (DENOISER.md, "Moving spheres"; tests/temporal_motion_model.py): the MOTION instantiation of that kernel takes a
+// per-pixel motion image and carries the world point back by it before the previous camera looks; motion_kernel builds such an
+// image from the spheres of this frame and of the previous one, which the _scene calls remember on the host.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <new>
 
@@ -36,8 +40,26 @@ struct Params {
 
 __device__ __forceinline__ float lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
 
+// Component k of the renderer's primary direction of the unjittered pixel (row y, column x): the row is divided by the width,
+// the column by the height: sy = column / fh, v = 1 - row / fw, and the two lerps over (b0, e1 = B1 - B0, b2, e2 = B3 - B2).
+// (Scalars by value: handed the parameter struct by reference, the compiler schedules the accumulate kernel differently.)
+__device__ __forceinline__ float primary_direction(float b0, float e1, float b2, float e2, float sy, float v) {
+  const float a = b0 + sy * e1, b = b2 + sy * e2;
+  return a + v * (b - a);
+}
+
+template <class T>
+__device__ __forceinline__ T first(T a) {
+  return a;
+}
+
+// MOTION: one more argument, `motion`, holds {mx, my, mz, w} per pixel (motion_kernel below) and the world point is carried back
+// by m before the previous camera looks at it.  accumulate_kernel<false> takes no such argument: it has the signature, and
+// instruction for instruction the code, that the kernel had before it became a template.
+template <bool MOTION, class... IMAGE>
 __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __restrict__ frame, const float4* __restrict__ hin,
-                                                            float4* __restrict__ hout, uint32_t* __restrict__ counts) {
+                                                            float4* __restrict__ hout, uint32_t* __restrict__ counts, IMAGE... motion) {
+  static_assert(sizeof...(IMAGE) == (MOTION ? 1 : 0), "accumulate_kernel<true, const float4*> or accumulate_kernel<false>");
   const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
   if (x >= p.width || y >= p.height) return;
   const uint32_t W = (uint32_t)p.width, i = (uint32_t)y * W + (uint32_t)x;
@@ -49,14 +71,16 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
 
   float hx = 0.0f, hy = 0.0f, hz = 0.0f, hs2 = 0.0f, hN = 0.0f;
   if (p.has_history) {  // uniform
-    // the renderer's primary direction of the unjittered pixel: the row is divided by the width, the column by the height
     const float sy = (float)x / p.fh, v = 1.0f - (float)y / p.fw;
     float X[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      const float a = p.b0[k] + sy * p.e1[k], b = p.b2[k] + sy * p.e2[k];
-      const float d = a + v * (b - a);
+      const float d = primary_direction(p.b0[k], p.e1[k], p.b2[k], p.e2[k], sy, v);
       X[k] = p.eye[k] + d * z;
+    }
+    if constexpr (MOTION) {  // where the surface point was one frame ago
+      const float4 m = first(motion...)[i];
+      X[0] = X[0] - m.x, X[1] = X[1] - m.y, X[2] = X[2] - m.z;
     }
     const float qx = X[0] - p.peye[0], qy = X[1] - p.peye[1], qz = X[2] - p.peye[2];
     const float al = (p.P[0] * qx + p.P[1] * qy) + p.P[2] * qz;
@@ -115,9 +139,70 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
   hout[2 * p.pixels + i] = make_float4(ax, ay, az, tot);
   if (counts) counts[i] = (uint32_t)floorf(tot + 0.5f);
 }
+
+// ---- the motion image ---------------------------------------------------------------------------------------------------
+// Which sphere does the centre ray of a pixel hit, and how far has that sphere moved since the previous frame?  One lane per
+// pixel; the spheres of this frame {x, y, z, radius} go through LDS MOTION_CHUNK at a time (the staging and the loop bounds are
+// uniform over the workgroup, the LDS reads are broadcasts), brute force: one primary ray per pixel needs no grid.  The search
+// is the reference's intersectSphere / intersectScene (src/pathtrace.cu:72-107) literally -- the direction not normalised,
+// double where its literals force double, the first of equal roots wins -- as tests/numpy_restatement.py states it.
+constexpr int MOTION_CHUNK = PT_MOTION_CHUNK;
+static_assert(MOTION_CHUNK == BX * BY, "one sphere per lane and round of the staging");
+
+struct MotionParams {
+  int width, height, n;
+  float fw, fh;
+  float b0[3], e1[3], b2[3], e2[3];
+  float eye[3];
+};
+
+__global__ void __launch_bounds__(BX* BY) motion_kernel(MotionParams p, const float4* __restrict__ now, const float4* __restrict__ prev,
+                                                        float4* __restrict__ out) {
+  __shared__ float4 staged[MOTION_CHUNK];
+  const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+  const int lane = threadIdx.y * BX + threadIdx.x;
+  const bool live = x < p.width && y < p.height;  // (a lane outside the frame stages and waits with the others)
+  const float sy = (float)x / p.fh, v = 1.0f - (float)y / p.fw;
+  float d[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) d[k] = primary_direction(p.b0[k], p.e1[k], p.b2[k], p.e2[k], sy, v);
+  const float a = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];  // :74
+  float tNearest = 1000000.0f;
+  int idx = -1;
+  for (int base = 0; base < p.n; base += MOTION_CHUNK) {
+    const int m = min(MOTION_CHUNK, p.n - base);
+    if (lane < m) staged[lane] = now[base + lane];
+    __syncthreads();
+    for (int j = 0; j < m; j++) {
+      const float4 s = staged[j];
+      const float ox = p.eye[0] - s.x, oy = p.eye[1] - s.y, oz = p.eye[2] - s.z;  // :73
+      const float b = (float)(2.0 * (double)((d[0] * ox + d[1] * oy) + d[2] * oz));  // :75
+      const float c = ((ox * ox + oy * oy) + oz * oz) - s.w * s.w;                  // :76
+      const float bb = b * b;
+      const float det = bb - (4.0f * a) * c;  // :77
+      if (det >= 0.0f) {                      // :79
+        const double root = sqrt((double)bb - (4.0 * (double)a) * (double)c), den = 2.0 * (double)a;
+        const float tNear = (float)(((double)(-b) - root) / den), tFar = (float)(((double)(-b) + root) / den);  // :80-81
+        const float t = tNear > 0.0f && tFar > 0.0f ? fminf(tNear, tFar) : tNear > 0.0f ? tNear : tFar;      // :82-87
+        if (t > 0.0f && t < tNearest) tNearest = t, idx = base + j;  // :99
+      }
+    }
+    __syncthreads();
+  }
+  if (!live) return;
+  float4 r = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+  if (idx >= 0) {
+    const float4 pn = now[idx], pp = prev[idx];
+    r = make_float4(pn.x - pp.x, pn.y - pp.y, pn.z - pp.z, (float)idx);
+  }
+  out[(size_t)y * p.width + x] = r;
+}
 }  // namespace pttmp
 
 using namespace pttmp;
+
+constexpr int RING = 4;      // pinned staging slots of the spheres
+constexpr int RETIRED = 20;  // staging buffers a session can outgrow (the capacity doubles: 17 at the most)
 
 struct pt_temporal {
   int width = 0, height = 0;
@@ -127,6 +212,19 @@ struct pt_temporal {
   bool has_history = false;
   float P[9] = {}, eye[3] = {};  // the previous call's camera
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // what the motion calls need, allocated by the first of them that does
+  float4* d_motion = nullptr;   // [pixels], the _scene calls' motion image
+  float4* d_spheres = nullptr;  // [2][sphere_cap]: {pos, radius} of this frame, {pos, -} of the previous one
+  float4* h_spheres = nullptr;  // pinned, [RING][2][sphere_cap]
+  int sphere_cap = 0;
+  float4 *retired_d[RETIRED] = {}, *retired_h[RETIRED] = {};  // outgrown staging buffers, freed with the session
+  int n_retired = 0;
+  hipEvent_t slot_done[RING] = {};  // the copy out of a slot has run
+  bool slot_used[RING] = {};
+  int next_slot = 0;
+  pt_sphere* scene = nullptr;  // host copy of the previous _scene call's spheres, [scene_cap]
+  int scene_n = 0, scene_cap = 0;
+  bool has_scene = false;
 };
 
 using pt_stage::finite_f;
@@ -162,7 +260,9 @@ static int camera_matrix(const char* who, const float basis[12], float P[9]) {
   return PT_OK;
 }
 
-static size_t ws_bytes(const pt_temporal* t) { return (size_t)2 * 3 * t->width * t->height * sizeof(float4); }
+static size_t hist_bytes(const pt_temporal* t) { return (size_t)2 * 3 * t->width * t->height * sizeof(float4); }
+static size_t motion_bytes(const pt_temporal* t) { return (size_t)t->width * t->height * sizeof(float4); }
+static size_t ws_bytes(const pt_temporal* t) { return hist_bytes(t) + (t->d_motion ? motion_bytes(t) : 0); }
 
 // (every check before any launch: a refused call launches nothing and leaves the session as it was)
 static int check_args(const char* who, const pt_temporal* t, int n_frames, const float* d_frames, size_t frame_stride_floats,
@@ -186,46 +286,259 @@ static int check_args(const char* who, const pt_temporal* t, int n_frames, const
   return PT_OK;
 }
 
-static int enqueue_frames(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
-                          const float* eyes, int samples, uint32_t* d_counts, hipStream_t s) {
-  int rc = check_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples);
-  if (rc != PT_OK) return rc;
-  Params p{};
+// ---- the spheres of the motion calls: host checks, staging, the launch ------------------------------------------------------
+
+static int check_sphere_count(const char* who, int n) {
+  if (n < 1 || n > 65535) return pt_fail(PT_EINVAL, "%s: n %d outside 1 .. 65535", who, n);
+  return PT_OK;
+}
+
+static int check_sphere_fields(const char* who, const char* what, const pt_sphere* s, int n) {
+  for (int i = 0; i < n; i++) {
+    const float* f = &s[i].radius;  // radius, pos[3], emission[3], color[3]: ten floats
+    static const char* const names[10] = {"radius", "pos[0]", "pos[1]", "pos[2]", "emission[0]", "emission[1]", "emission[2]",
+                                          "color[0]", "color[1]", "color[2]"};
+    for (int k = 0; k < 10; k++)
+      if (!finite_f(f[k])) return pt_fail(PT_EINVAL, "%s: %s: %s of sphere %d is not finite", who, what, names[k], i);
+  }
+  return PT_OK;
+}
+static_assert(sizeof(pt_sphere) == 10 * sizeof(float), "pt_sphere is ten floats");
+
+static int check_sphere_radii(const char* who, const char* what, const pt_sphere* now, const pt_sphere* prev, int n) {
+  for (int i = 0; i < n; i++)
+    if (memcmp(&now[i].radius, &prev[i].radius, sizeof(float)) != 0)
+      return pt_fail(PT_EINVAL, "%s: %s: the radius of sphere %d changes from %g to %g, which is no rigid translation: reset the session", who,
+                     what, i, (double)prev[i].radius, (double)now[i].radius);
+  return PT_OK;
+}
+
+static int check_camera(const char* who, const float* basis, const float* eye) {
+  if (!basis) return pt_fail(PT_EINVAL, "%s: null basis", who);
+  if (!eye) return pt_fail(PT_EINVAL, "%s: null eye", who);
+  for (int k = 0; k < 3; k++)
+    if (!finite_f(eye[k])) return pt_fail(PT_EINVAL, "%s: eye[%d] is not finite", who, k);
+  float P[9];
+  return camera_matrix(who, basis, P);
+}
+
+// Everything pt_temporal_motion checks about its host arguments; no device.
+static int check_motion_args(const char* who, const pt_sphere* h_now, const pt_sphere* h_prev, int n, const float* basis, const float* eye) {
+  if (!h_now) return pt_fail(PT_EINVAL, "%s: null h_now", who);
+  if (!h_prev) return pt_fail(PT_EINVAL, "%s: null h_prev", who);
+  int rc = check_sphere_count(who, n);
+  if (rc == PT_OK) rc = check_sphere_fields(who, "h_now", h_now, n);
+  if (rc == PT_OK) rc = check_sphere_fields(who, "h_prev", h_prev, n);
+  if (rc == PT_OK) rc = check_sphere_radii(who, "h_now", h_now, h_prev, n);
+  if (rc == PT_OK) rc = check_camera(who, basis, eye);
+  return rc;
+}
+
+// Room for n spheres in the staging buffers.  Nothing waits for the device: work already enqueued may still read the old
+// buffers, so they are retired, not freed -- pt_temporal_destroy frees them.  The capacity at least doubles (up to the 65535
+// spheres a call may have), so a session retires at most RETIRED pairs.  A failure frees what it got and leaves the session as
+// it was.
+static int ensure_staging(const char* who, pt_temporal* t, int n) {
+  if (n <= t->sphere_cap) return PT_OK;
+  const int cap = max(n, min(2 * t->sphere_cap, 65535));
+  float4 *d = nullptr, *h = nullptr;
+  const size_t bytes = (size_t)2 * cap * sizeof(float4);
+  hipError_t e = t->n_retired < RETIRED ? hipSuccess : hipErrorOutOfMemory;  // (unreachable: 1 -> 65535 is 16 doublings)
+  if (e == hipSuccess) e = hipMalloc((void**)&d, bytes);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h, RING * bytes, hipHostMallocDefault);
+  for (int k = 0; k < RING; k++)
+    if (e == hipSuccess && !t->slot_done[k]) e = hipEventCreateWithFlags(&t->slot_done[k], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    return pt_fail(PT_EHIP, "%s: staging buffers for %d spheres: %s; the session is as it was", who, cap, hipGetErrorString(e));
+  }
+  if (t->d_spheres) {
+    t->retired_d[t->n_retired] = t->d_spheres, t->retired_h[t->n_retired] = t->h_spheres;
+    t->n_retired++;
+  }
+  t->d_spheres = d, t->h_spheres = h, t->sphere_cap = cap;
+  for (bool& used : t->slot_used) used = false;
+  t->next_slot = 0;
+  return PT_OK;
+}
+
+static int ensure_motion_image(const char* who, pt_temporal* t) {
+  if (t->d_motion) return PT_OK;
+  const hipError_t e = hipMalloc((void**)&t->d_motion, motion_bytes(t));
+  if (e == hipSuccess) return PT_OK;
+  (void)hipGetLastError();
+  t->d_motion = nullptr;
+  return pt_fail(PT_EHIP, "%s: the motion image of %zu bytes: %s; the session is as it was", who, motion_bytes(t), hipGetErrorString(e));
+}
+
+static int ensure_scene_copy(const char* who, pt_temporal* t, int n) {
+  if (n <= t->scene_cap) return PT_OK;
+  pt_sphere* s = new (std::nothrow) pt_sphere[n];
+  if (!s) return pt_fail(PT_ENOMEM, "%s: out of host memory for the copy of %d spheres", who, n);
+  if (t->scene) memcpy(s, t->scene, (size_t)t->scene_n * sizeof(pt_sphere));
+  delete[] t->scene;
+  t->scene = s, t->scene_cap = n;
+  return PT_OK;
+}
+
+// The checked spheres through a pinned slot to the device and the motion kernel behind them, on the call's stream.  A slot is
+// written again only after the copy out of it has run (with RING slots in flight that wait has normally long passed).
+static int launch_motion(pt_temporal* t, const pt_sphere* now, const pt_sphere* prev, int n, const float* B, const float* eye, float4* d_out,
+                         hipStream_t s) {
+  const int slot = t->next_slot;
+  if (t->slot_used[slot]) PT_HIP(hipEventSynchronize(t->slot_done[slot]));
+  float4* h = t->h_spheres + (size_t)slot * 2 * t->sphere_cap;
+  for (int i = 0; i < n; i++) {
+    h[i] = make_float4(now[i].pos[0], now[i].pos[1], now[i].pos[2], now[i].radius);
+    h[n + i] = make_float4(prev[i].pos[0], prev[i].pos[1], prev[i].pos[2], prev[i].radius);
+  }
+  PT_HIP(hipMemcpyAsync(t->d_spheres, h, (size_t)2 * n * sizeof(float4), hipMemcpyHostToDevice, s));
+  PT_HIP(hipEventRecord(t->slot_done[slot], s));
+  t->slot_used[slot] = true;
+  t->next_slot = (slot + 1) % RING;
+  MotionParams p{};
+  p.width = t->width, p.height = t->height, p.n = n;
+  p.fw = (float)t->width, p.fh = (float)t->height;
+  for (int k = 0; k < 3; k++) p.b0[k] = B[k], p.e1[k] = B[3 + k] - B[k], p.b2[k] = B[6 + k], p.e2[k] = B[9 + k] - B[6 + k], p.eye[k] = eye[k];
+  const dim3 block(BX, BY), grid((unsigned)((p.width + BX - 1) / BX), (unsigned)((p.height + BY - 1) / BY));
+  hipLaunchKernelGGL(motion_kernel, grid, block, 0, s, p, (const float4*)t->d_spheres, (const float4*)(t->d_spheres + n), d_out);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// ---- accumulation ---------------------------------------------------------------------------------------------------------
+
+static void session_params(const pt_temporal* t, int samples, Params& p) {
   p.width = t->width, p.height = t->height;
   p.pixels = (uint32_t)t->width * (uint32_t)t->height;
   p.n = (float)samples;
   p.fw = (float)t->width, p.fh = (float)t->height;
   p.cap = t->opts.history_cap, p.depth_tol = t->opts.depth_tol, p.normal_tol = t->opts.normal_tol;
   p.albedo_tol = t->opts.albedo_tol, p.min_weight = t->opts.min_weight;
+}
+
+// One frame: the launch and the session's step.  d_motion: null for the static kernel.
+static int accumulate_frame(const char* who, pt_temporal* t, Params& p, float* d_frame, const float* B, const float* eye, const float4* d_motion,
+                            uint32_t* d_counts, hipStream_t s) {
+  for (int k = 0; k < 3; k++) {
+    p.b0[k] = B[k], p.e1[k] = B[3 + k] - B[k], p.b2[k] = B[6 + k], p.e2[k] = B[9 + k] - B[6 + k];
+    p.eye[k] = eye[k], p.peye[k] = t->eye[k];
+  }
+  for (int k = 0; k < 9; k++) p.P[k] = t->P[k];
+  p.has_history = t->has_history ? 1 : 0;
+  float4* hin = t->d_hist + (size_t)t->cur * 3 * p.pixels;
+  float4* hout = t->d_hist + (size_t)(1 - t->cur) * 3 * p.pixels;
   const dim3 block(BX, BY), grid((unsigned)((p.width + BX - 1) / BX), (unsigned)((p.height + BY - 1) / BY));
+  if (d_motion)
+    hipLaunchKernelGGL((accumulate_kernel<true, const float4*>), grid, block, 0, s, p, d_frame, (const float4*)hin, hout, d_counts, d_motion);
+  else
+    hipLaunchKernelGGL((accumulate_kernel<false>), grid, block, 0, s, p, d_frame, (const float4*)hin, hout, d_counts);
+  PT_HIP(hipGetLastError());
+  (void)camera_matrix(who, B, t->P);  // (checked by the caller)
+  for (int k = 0; k < 3; k++) t->eye[k] = eye[k];
+  t->cur = 1 - t->cur;
+  t->has_history = true;
+  return PT_OK;
+}
+
+// The calls without a scene; d_motion (single calls only) may be null.  They forget the remembered scene.
+static int enqueue_frames(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                          const float* eyes, int samples, const float4* d_motion, uint32_t* d_counts, hipStream_t s) {
+  int rc = check_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples);
+  if (rc != PT_OK) return rc;
+  Params p{};
+  session_params(t, samples, p);
+  t->has_scene = false;
   for (int f = 0; f < n_frames; f++) {
-    const float* B = bases + 12 * f;
-    for (int k = 0; k < 3; k++) {
-      p.b0[k] = B[k], p.e1[k] = B[3 + k] - B[k], p.b2[k] = B[6 + k], p.e2[k] = B[9 + k] - B[6 + k];
-      p.eye[k] = eyes[3 * f + k], p.peye[k] = t->eye[k];
-    }
-    for (int k = 0; k < 9; k++) p.P[k] = t->P[k];
-    p.has_history = t->has_history ? 1 : 0;
-    float4* hin = t->d_hist + (size_t)t->cur * 3 * p.pixels;
-    float4* hout = t->d_hist + (size_t)(1 - t->cur) * 3 * p.pixels;
     // the count image is that of the last frame
-    hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, s, p, d_frames + (size_t)f * frame_stride_floats, (const float4*)hin, hout,
-                       f == n_frames - 1 ? d_counts : (uint32_t*)nullptr);
-    PT_HIP(hipGetLastError());
-    (void)camera_matrix(who, B, t->P);  // (checked above)
-    for (int k = 0; k < 3; k++) t->eye[k] = eyes[3 * f + k];
-    t->cur = 1 - t->cur;
-    t->has_history = true;
+    rc = accumulate_frame(who, t, p, d_frames + (size_t)f * frame_stride_floats, bases + 12 * f, eyes + 3 * f, d_motion,
+                          f == n_frames - 1 ? d_counts : (uint32_t*)nullptr, s);
+    if (rc != PT_OK) return rc;
   }
   return PT_OK;
 }
 
 static int run_timed(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
-                     const float* eyes, int samples, uint32_t* d_counts, float* ms_out) {
+                     const float* eyes, int samples, const float4* d_motion, uint32_t* d_counts, float* ms_out) {
   const int rc0 = check_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples);
   if (rc0 != PT_OK) return rc0;
   return pt_stage::run_timed(t->ev0, t->ev1, ms_out, [&] {
-    return enqueue_frames(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_counts, nullptr);
+    return enqueue_frames(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_motion, d_counts, nullptr);
+  });
+}
+
+// The _scene calls: h_scenes [n_frames][n].  Frame f takes its motion from scene f - 1, the first one from the scene the session
+// remembers (none after a reset or a call without a scene: that frame runs the static kernel).
+static int check_scene_args(const char* who, const pt_temporal* t, int n_frames, const float* d_frames, size_t frame_stride_floats,
+                            const float* bases, const float* eyes, int samples, const pt_sphere* h_scenes, int n) {
+  int rc = check_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples);
+  if (rc != PT_OK) return rc;
+  if (!h_scenes) return pt_fail(PT_EINVAL, "%s: null h_spheres", who);
+  if ((rc = check_sphere_count(who, n)) != PT_OK) return rc;
+  const bool remembered = t->has_history && t->has_scene;
+  if (remembered && n != t->scene_n)
+    return pt_fail(PT_EINVAL, "%s: n %d differs from the %d spheres of the session's previous scene: reset the session", who, n, t->scene_n);
+  const pt_sphere* prev = remembered ? t->scene : nullptr;
+  for (int f = 0; f < n_frames; f++) {
+    const pt_sphere* now = h_scenes + (size_t)f * n;
+    if ((rc = check_sphere_fields(who, "h_spheres", now, n)) != PT_OK) return rc;
+    if (prev && (rc = check_sphere_radii(who, "h_spheres", now, prev, n)) != PT_OK) return rc;
+    prev = now;
+  }
+  return PT_OK;
+}
+
+// Every allocation the call needs, before its first launch (and outside a timed window).
+static int prepare_scene_call(const char* who, pt_temporal* t, int n_frames, int n) {
+  int rc = ensure_scene_copy(who, t, n);
+  if (rc == PT_OK && (n_frames > 1 || (t->has_history && t->has_scene))) {
+    rc = ensure_motion_image(who, t);
+    if (rc == PT_OK) rc = ensure_staging(who, t, n);
+  }
+  return rc;
+}
+
+// The launches of a checked and prepared _scene call.
+static int launch_scenes(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                         const float* eyes, int samples, const pt_sphere* h_scenes, int n, uint32_t* d_counts, hipStream_t s) {
+  int rc = PT_OK;
+  Params p{};
+  session_params(t, samples, p);
+  for (int f = 0; f < n_frames; f++) {
+    const pt_sphere* now = h_scenes + (size_t)f * n;
+    const pt_sphere* prev = f ? now - n : (t->has_history && t->has_scene ? t->scene : nullptr);
+    const float4* d_motion = nullptr;
+    if (t->has_history && prev) {
+      if ((rc = launch_motion(t, now, prev, n, bases + 12 * f, eyes + 3 * f, t->d_motion, s)) != PT_OK) return rc;
+      d_motion = t->d_motion;
+    }
+    rc = accumulate_frame(who, t, p, d_frames + (size_t)f * frame_stride_floats, bases + 12 * f, eyes + 3 * f, d_motion,
+                          f == n_frames - 1 ? d_counts : (uint32_t*)nullptr, s);
+    if (rc != PT_OK) return rc;
+    // (the host copy is taken at once: the caller's array need not outlive the call)
+    memcpy(t->scene, now, (size_t)n * sizeof(pt_sphere));
+    t->scene_n = n, t->has_scene = true;
+  }
+  return PT_OK;
+}
+
+static int enqueue_scenes(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                          const float* eyes, int samples, const pt_sphere* h_scenes, int n, uint32_t* d_counts, hipStream_t s) {
+  int rc = check_scene_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n);
+  if (rc == PT_OK) rc = prepare_scene_call(who, t, n_frames, n);
+  if (rc != PT_OK) return rc;
+  return launch_scenes(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n, d_counts, s);
+}
+
+static int run_scenes_timed(const char* who, pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                            const float* eyes, int samples, const pt_sphere* h_scenes, int n, uint32_t* d_counts, float* ms_out) {
+  int rc = check_scene_args(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n);
+  if (rc == PT_OK) rc = prepare_scene_call(who, t, n_frames, n);
+  if (rc != PT_OK) return rc;
+  return pt_stage::run_timed(t->ev0, t->ev1, ms_out, [&] {
+    return launch_scenes(who, t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n, d_counts, nullptr);
   });
 }
 
@@ -251,6 +564,16 @@ int pt_temporal_camera(const float basis[12], float P_out[9]) {
 int pt_temporal_destroy(pt_temporal* t) {
   if (!t) return PT_OK;
   if (t->d_hist) (void)hipFree(t->d_hist);
+  if (t->d_motion) (void)hipFree(t->d_motion);
+  if (t->d_spheres) (void)hipFree(t->d_spheres);
+  if (t->h_spheres) (void)hipHostFree(t->h_spheres);
+  for (int k = 0; k < t->n_retired; k++) {
+    (void)hipFree(t->retired_d[k]);
+    (void)hipHostFree(t->retired_h[k]);
+  }
+  for (hipEvent_t e : t->slot_done)
+    if (e) (void)hipEventDestroy(e);
+  delete[] t->scene;
   pt_stage::destroy_events(t);
   delete t;
   return PT_OK;
@@ -278,7 +601,7 @@ int pt_temporal_create(int width, int height, const pt_temporal_opts* opts, pt_t
   pt_temporal* t = new (std::nothrow) pt_temporal();
   if (!t) return pt_fail(PT_ENOMEM, "pt_temporal_create: out of host memory");
   t->width = width, t->height = height, t->opts = o;
-  const hipError_t e = hipMalloc((void**)&t->d_hist, ws_bytes(t));
+  const hipError_t e = hipMalloc((void**)&t->d_hist, hist_bytes(t));
   if ((rc = pt_stage::create_events("pt_temporal_create", e, t, pt_temporal_destroy)) != PT_OK) return rc;
   *out = t;
   return PT_OK;
@@ -287,6 +610,7 @@ int pt_temporal_create(int width, int height, const pt_temporal_opts* opts, pt_t
 int pt_temporal_reset(pt_temporal* t) {
   if (!t) return pt_fail(PT_EINVAL, "pt_temporal_reset: null accumulator");
   t->has_history = false;
+  t->has_scene = false;
   return PT_OK;
 }
 
@@ -299,25 +623,80 @@ int pt_temporal_workspace_bytes(const pt_temporal* t, uint64_t* bytes) {
 int pt_temporal_enqueue(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], uint32_t* d_counts,
                         void* hip_stream) {
   if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_enqueue: null %s", t ? "d_frame" : "accumulator");
-  return enqueue_frames("pt_temporal_enqueue", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, d_counts,
+  return enqueue_frames("pt_temporal_enqueue", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, nullptr, d_counts,
                         (hipStream_t)hip_stream);
 }
 
 int pt_temporal_run(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], uint32_t* d_counts,
                     float* ms_out) {
   if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_run: null %s", t ? "d_frame" : "accumulator");
-  return run_timed("pt_temporal_run", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, d_counts, ms_out);
+  return run_timed("pt_temporal_run", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, nullptr, d_counts, ms_out);
 }
 
 int pt_temporal_enqueue_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
                                const float* eyes, int samples, uint32_t* d_counts, void* hip_stream) {
-  return enqueue_frames("pt_temporal_enqueue_frames", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_counts,
+  return enqueue_frames("pt_temporal_enqueue_frames", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, nullptr, d_counts,
                         (hipStream_t)hip_stream);
 }
 
 int pt_temporal_run_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
                            const float* eyes, int samples, uint32_t* d_counts, float* ms_out) {
-  return run_timed("pt_temporal_run_frames", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, d_counts, ms_out);
+  return run_timed("pt_temporal_run_frames", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, nullptr, d_counts, ms_out);
+}
+
+int pt_temporal_scene_check(const pt_sphere* h_now, const pt_sphere* h_prev, int n, const float basis[12], const float eye[3]) {
+  return check_motion_args("pt_temporal_scene_check", h_now, h_prev, n, basis, eye);
+}
+
+int pt_temporal_motion(pt_temporal* t, const pt_sphere* h_now, const pt_sphere* h_prev, int n, const float basis[12], const float eye[3],
+                       float* d_motion, void* hip_stream) {
+  const char* who = "pt_temporal_motion";
+  if (!t) return pt_fail(PT_EINVAL, "%s: null accumulator", who);
+  if (!d_motion) return pt_fail(PT_EINVAL, "%s: null d_motion", who);
+  int rc = check_motion_args(who, h_now, h_prev, n, basis, eye);
+  if (rc == PT_OK) rc = ensure_staging(who, t, n);
+  if (rc != PT_OK) return rc;
+  return launch_motion(t, h_now, h_prev, n, basis, eye, (float4*)d_motion, (hipStream_t)hip_stream);
+}
+
+int pt_temporal_enqueue_motion(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const float* d_motion,
+                               uint32_t* d_counts, void* hip_stream) {
+  if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_enqueue_motion: null %s", t ? "d_frame" : "accumulator");
+  return enqueue_frames("pt_temporal_enqueue_motion", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples,
+                        (const float4*)d_motion, d_counts, (hipStream_t)hip_stream);
+}
+
+int pt_temporal_run_motion(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const float* d_motion,
+                           uint32_t* d_counts, float* ms_out) {
+  if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_run_motion: null %s", t ? "d_frame" : "accumulator");
+  return run_timed("pt_temporal_run_motion", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, (const float4*)d_motion,
+                   d_counts, ms_out);
+}
+
+int pt_temporal_enqueue_scene(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const pt_sphere* h_spheres,
+                              int n, uint32_t* d_counts, void* hip_stream) {
+  if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_enqueue_scene: null %s", t ? "d_frame" : "accumulator");
+  return enqueue_scenes("pt_temporal_enqueue_scene", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, h_spheres, n,
+                        d_counts, (hipStream_t)hip_stream);
+}
+
+int pt_temporal_run_scene(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const pt_sphere* h_spheres,
+                          int n, uint32_t* d_counts, float* ms_out) {
+  if (!t || !d_frame) return pt_fail(PT_EINVAL, "pt_temporal_run_scene: null %s", t ? "d_frame" : "accumulator");
+  return run_scenes_timed("pt_temporal_run_scene", t, 1, d_frame, (size_t)t->width * t->height * 14, basis, eye, samples, h_spheres, n,
+                          d_counts, ms_out);
+}
+
+int pt_temporal_enqueue_frames_scenes(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                                      const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, void* hip_stream) {
+  return enqueue_scenes("pt_temporal_enqueue_frames_scenes", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n,
+                        d_counts, (hipStream_t)hip_stream);
+}
+
+int pt_temporal_run_frames_scenes(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                                  const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, float* ms_out) {
+  return run_scenes_timed("pt_temporal_run_frames_scenes", t, n_frames, d_frames, frame_stride_floats, bases, eyes, samples, h_scenes, n,
+                          d_counts, ms_out);
 }
 
 }  // extern "C"

@@ -43,6 +43,15 @@ class Scene {
     return Scene(s);
   }
 
+  // Not in the reference: the same number of spheres again, e.g. moved (pathtrace --velocities), into the device array.
+  void Update(const std::vector<Sphere>& spheres) {
+    if ((int)spheres.size() != numObjects || !objects) {
+      std::fprintf(stderr, "GPUassert: Scene::Update: %d spheres for a scene of %d %s %d\n", (int)spheres.size(), numObjects, __FILE__, __LINE__);
+      std::exit(PT_EINVAL);
+    }
+    if (numObjects > 0) gpuErrchk(pt_memcpy_h2d(objects, spheres.data(), numObjects * sizeof(Sphere)));
+  }
+
   // The reference never frees `objects` (Scene.h has no destructor and Scene is passed by
   // value into kernels); an explicit Free() is offered instead of changing copy semantics.
   void Free() {

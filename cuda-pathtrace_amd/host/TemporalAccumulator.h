@@ -10,6 +10,7 @@
 #include "Camera.h"
 #include "HipErrorCheck.h"
 #include "OutputBuffer.h"
+#include "Scene.h"
 
 class TemporalAccumulator {
  private:
@@ -37,6 +38,17 @@ class TemporalAccumulator {
     Pose(camera, basis, eye);
     float ms = 0.0f;
     gpuErrchk(pt_temporal_run(session, d_buffer.buffer, samples, basis, eye, d_counts, &ms));
+    return ms;
+  }
+  // the same for an animated scene: `scene` holds the HOST spheres the frame was rendered from.  The session remembers them,
+  // and from the second call on every pixel follows the sphere its centre ray hits (pt_temporal_run_scene): spheres may move
+  // between calls by rigid translation; a sphere count or a radius that changes exits like every error -- Reset() first.
+  float Accumulate(OutputBuffer& d_buffer, int samples, const Camera& camera, const std::vector<Sphere>& scene, unsigned int* d_counts = NULL) {
+    float basis[12], eye[3];
+    Pose(camera, basis, eye);
+    float ms = 0.0f;
+    gpuErrchk(pt_temporal_run_scene(session, d_buffer.buffer, samples, basis, eye, reinterpret_cast<const pt_sphere*>(scene.data()),
+                                    (int)scene.size(), d_counts, &ms));
     return ms;
   }
   // asynchronous on a HIP stream (NULL = default)

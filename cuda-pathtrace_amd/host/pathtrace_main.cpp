@@ -19,6 +19,8 @@
 // is filtered in place after Render(), where -d would run the network; the saved EXR and bitmaps hold the filtered frame),
 // --temporal (with --frames / --poses: TemporalAccumulator / pt_temporal_* accumulates every frame of the headless loop in place
 // after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts),
+// --velocities FILE (with --frames / --poses: the spheres listed move at a constant velocity, the scene is uploaded before every
+// frame's Render(), and --temporal accumulates through pt_temporal_run_scene, which follows them),
 // --tonemap CURVE (ToneMapper / pt_tonemap_*: every frame of the headless loop and every progressive pass goes through the
 // session after --temporal, --filter and -d, so that --tonemap-adapt acts as eye adaptation; the last frame's sRGB picture is
 // written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes),
@@ -50,6 +52,7 @@
 #include "Scene.h"
 #include "TemporalAccumulator.h"
 #include "ToneMapper.h"
+#include "Velocities.h"
 
 static void usage() {
   std::cout << "cuda-pathtrace" << std::endl
@@ -88,6 +91,8 @@ static void usage() {
                "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
                "  --temporal                    with --frames / --poses: reproject and accumulate every frame over the last ones\n"
                "  --temporal-cap arg            with --temporal: cap of the accumulated history in samples, >= 1 (default 256)\n"
+               "  --velocities arg              with --frames / --poses: file of 'index vx vy vz' lines; sphere index moves by v per frame\n"
+               "                                (with --temporal every pixel follows the sphere it shows)\n"
                "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
                "  --exposure arg                with --tonemap: auto (default, metered on the device) or a number > 0\n"
                "  --tonemap-key arg             with --tonemap: luminance the metered mean is mapped to (default 0.18)\n"
@@ -110,7 +115,7 @@ int main(int argc, const char** argv) {
   std::string outputName = "output/out";
   std::string rng = "xorwow";
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
-  std::string posesFile, previewFile, denoiseWeights, denoisePrecision;
+  std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile;
   bool denoisePrecisionGiven = false;
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
@@ -184,6 +189,7 @@ int main(int argc, const char** argv) {
     else if (a == "--tonemap-encode") { tonemapEncode = value("--tonemap-encode"); if (!tonemapOption) tonemapOption = "--tonemap-encode"; }
     else if (a == "--compare") compareFile = value("--compare");
     else if (a == "--poses") posesFile = value("--poses");
+    else if (a == "--velocities") velocitiesFile = value("--velocities");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
     else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
@@ -297,6 +303,32 @@ int main(int argc, const char** argv) {
       return 1;
     }
     temporalOpts.history_cap = (float)temporalCap;
+  }
+  // --velocities: the list and the scene of frame 0 on the host (before any device is touched)
+  std::vector<SphereVelocity> velocities;
+  std::vector<Sphere> spheresAt0, spheresNow;
+  if (!velocitiesFile.empty()) {
+    if (batch || progressiveGiven) {
+      std::cerr << "ERROR: --velocities cannot be combined with " << (batch ? "--batch" : "--progressive")
+                << ": the scene is uploaded before every frame of the loop" << std::endl;
+      return 1;
+    }
+    if (!framesGiven && posesFile.empty()) {
+      std::cerr << "ERROR: --velocities needs --frames or --poses: the spheres move from frame to frame of the headless loop" << std::endl;
+      return 1;
+    }
+    const int count = nSpheres > 0 ? nSpheres : 9;
+    std::string why;
+    if (!ParseVelocities(velocitiesFile, count, velocities, why)) {
+      std::cerr << "ERROR: --velocities: " << why << std::endl;
+      return 1;
+    }
+    spheresAt0.resize((size_t)count);
+    pt_sphere* host = reinterpret_cast<pt_sphere*>(spheresAt0.data());
+    if ((nSpheres > 0 ? pt_scene_random(nSpheres, 1, 1, host) : pt_scene_cornell(host)) != PT_OK) {
+      std::cerr << "ERROR: --velocities: " << pt_last_error() << std::endl;
+      return 1;
+    }
   }
   pt_tonemap_opts tonemapOpts;
   pt_tonemap_opts_default(&tonemapOpts);
@@ -460,9 +492,15 @@ int main(int argc, const char** argv) {
              v.relmse, v.ssim, (unsigned long long)v.saturated, (unsigned long long)v.nonfinite);
     std::cout << text << std::endl;
   };
-  auto render = [&](OutputBuffer b, const Scene& s, const Camera& c) {
+  int frameIndex = 0;  // (of the headless loop: --velocities)
+  auto render = [&](OutputBuffer b, Scene& s, const Camera& c) {
+    if (!velocities.empty()) {  // the scene of this frame, uploaded before Render()
+      MoveSpheres(spheresAt0, velocities, frameIndex++, spheresNow);
+      s.Update(spheresNow);
+    }
     const float ms = tiled ? tiled->Render(b, s, c) : single->Render(b, s, c);
-    if (accumulator) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, d_temporalCounts);
+    if (accumulator && !velocities.empty()) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, spheresNow, d_temporalCounts);
+    else if (accumulator) temporalTime = accumulator->Accumulate(b, samplesPerPixel, c, d_temporalCounts);
     if (net) denoiseTime = net->Denoise(b);  // main.cu:148-152: Render, then the network in place
     if (filter) filterTime = filter->Filter(b, samplesPerPixel, d_temporalCounts);
     if (comparison) compare(b);

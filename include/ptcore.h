@@ -439,7 +439,7 @@ int pt_filter_run_frames(pt_filter* f, int n_frames, float* d_frames, size_t fra
  *             (hs2 max(hN - 1, 0) + ch10 (n - 1) + (lum(C) - lum(hC))^2 hN n / tot) / (tot - 1);  count = floor(tot + 0.5).
  * The first call of a session and the first after pt_temporal_reset pass the frame through (its own bits, count n).
  * Limits: silhouette pixels carry mixed depths and normals and mostly restart; sky pixels (z <= 0) never accumulate; the scene
- * must not change between calls without a reset.  One session's calls share its workspace and are ordered by the stream: do
+ * must not change between calls except through the _scene calls below, or without a reset.  One session's calls share its workspace and are ordered by the stream: do
  * not run two of them concurrently on different streams. */
 typedef struct pt_temporal_opts {
   float history_cap;  /* the accumulated count never exceeds this many samples, >= 1 (default 256)            */
@@ -481,6 +481,68 @@ int pt_temporal_enqueue_frames(pt_temporal* t, int n_frames, float* d_frames, si
                                const float* eyes, int samples, uint32_t* d_counts, void* hip_stream);
 int pt_temporal_run_frames(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
                            const float* eyes, int samples, uint32_t* d_counts, float* ms_out);
+
+/* -- moving spheres: a motion vector per pixel (DENOISER.md, "Moving spheres") --
+ * A motion image is a device image [height][width] of four floats {mx, my, mz, w}: the sphere that the CENTRE ray of the pixel
+ * hits first in this frame's scene has index w and has moved by m since the previous frame; a miss is {0, 0, 0, -1}.  With a
+ * motion image the pixel step above carries the world point back before the previous camera looks at it: X = eye + d z, then
+ * Xp = X - m, and (alpha, beta, gamma) = P' (Xp - eye'); taps, stops and blend are unchanged.  The depth stop needs no change:
+ * alpha is the distance parameter, in the previous camera, of the point where the surface was, which is what the history holds
+ * there if the same sphere was visible.  A zero motion image gives the bits of the static call; a pixel whose centre ray misses is
+ * treated as static; background uncovered by a departing sphere reprojects onto history that holds the sphere, fails the stops and
+ * restarts; a NaN or infinite motion component restarts the pixel as a NaN depth does.  EXACT code, restated in
+ * tests/temporal_motion_model.py.
+ *   motion    d = the unjittered primary direction of the pixel, NOT normalised; the nearest hit of (eye, d) among the n spheres
+ *             of h_now by the reference's intersectSphere / intersectScene (src/pathtrace.cu:72-107): double where its literals
+ *             force double, float elsewhere, t > 0 && t < tNearest from 1000000.0f, strict <, so the lowest index wins a tie;
+ *             on a hit of sphere i: m = h_now[i].pos - h_prev[i].pos (one float subtraction per component), w = (float)i.
+ * The kernel tests every sphere for every pixel (no grid), PT_MOTION_CHUNK spheres per round through LDS.
+ * Limits: rigid translation only (a changed radius is refused); the centre ray decides a pixel's sphere, so silhouettes restart
+ * as they do anyway; a moving sphere's shadow and its indirect light on static surfaces are not followed and lag by up to
+ * history_cap samples: use a small cap for animated scenes. */
+#define PT_MOTION_CHUNK 256
+/* The host checks of pt_temporal_motion alone (no device, no session): PT_EINVAL naming the argument for a null pointer, n
+ * outside 1 .. 65535, a field of either array that is not finite (colour and emission are checked, though not read), a radius
+ * that is not bitwise equal in both arrays ("reset the session"), a non-finite eye and a basis pt_temporal_camera refuses. */
+int pt_temporal_scene_check(const pt_sphere* h_now, const pt_sphere* h_prev, int n, const float basis[12], const float eye[3]);
+/* The motion image of the HOST arrays h_now, h_prev (n spheres each, index-matched) under the camera (basis, eye) into d_motion
+ * (width x height x 4 floats), asynchronous on hip_stream.  A null accumulator or d_motion and everything
+ * pt_temporal_scene_check refuses is PT_EINVAL, checked before a device is touched; nothing is launched.  The spheres travel
+ * through a pinned staging buffer of the session (32 bytes per sphere on the device, 128 pinned; not part of
+ * pt_temporal_workspace_bytes), so the arrays may be reused as soon as the call returns and no call waits for the device
+ * unless four earlier uploads of the session are still pending (the call then waits for the oldest one's event).  The staging
+ * is allocated by the first call that needs it and again, at twice the size, by a call with more spheres than it holds: such
+ * a call allocates (hipMalloc, hipHostMalloc; do not make it under stream capture) but does not wait for the device's work --
+ * the outgrown buffers, which enqueued work may still read, are kept until pt_temporal_destroy.  Call once with the largest
+ * scene up front to have no allocation later.  Neither the history nor the remembered scene is touched. */
+int pt_temporal_motion(pt_temporal* t, const pt_sphere* h_now, const pt_sphere* h_prev, int n, const float basis[12], const float eye[3],
+                       float* d_motion, void* hip_stream);
+/* pt_temporal_enqueue / pt_temporal_run with a motion image; d_motion == NULL is exactly pt_temporal_enqueue / pt_temporal_run
+ * (the same kernel, the same bits). */
+int pt_temporal_enqueue_motion(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const float* d_motion,
+                               uint32_t* d_counts, void* hip_stream);
+int pt_temporal_run_motion(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const float* d_motion,
+                           uint32_t* d_counts, float* ms_out);
+/* The form for animated scenes: accumulates d_frame, rendered from the n HOST spheres h_spheres.  The session keeps a host copy
+ * of the scene of its previous call, builds the motion image (this scene against that one) into a buffer of its own -- 16 bytes
+ * per pixel, allocated by the first call that needs it and reported by pt_temporal_workspace_bytes from then on -- and
+ * accumulates with it: two launches.  The first call of a session and the first after pt_temporal_reset pass the frame through
+ * and only remember the scene.  Everything pt_temporal_enqueue refuses, a null h_spheres, n outside 1 .. 65535, a field that is
+ * not finite, an n that differs from the remembered scene's and a radius that differs from it ("reset the session") are
+ * PT_EINVAL; nothing is launched and the session, its remembered scene included, is as it was.  The calls above without a scene
+ * may be mixed in: they forget the remembered scene, so the next _scene call accumulates with zero motion (the static kernel)
+ * and remembers its scene.  A session that never uses the calls of this section allocates nothing for them. */
+int pt_temporal_enqueue_scene(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const pt_sphere* h_spheres,
+                              int n, uint32_t* d_counts, void* hip_stream);
+int pt_temporal_run_scene(pt_temporal* t, float* d_frame, int samples, const float basis[12], const float eye[3], const pt_sphere* h_spheres,
+                          int n, uint32_t* d_counts, float* ms_out);
+/* n_frames frames with their scenes h_scenes [n_frames][n], bit for bit the loop of pt_temporal_enqueue_scene calls (two
+ * launches per frame, one for a frame that passes through or has no remembered scene); d_counts receives the counts of the LAST
+ * frame.  Every frame and scene is checked before the first launch. */
+int pt_temporal_enqueue_frames_scenes(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                                      const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, void* hip_stream);
+int pt_temporal_run_frames_scenes(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
+                                  const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, float* ms_out);
 
 /* ---- tone mapping: metered exposure, a filmic curve and sRGB bytes ---------------------------- */
 /* The stage between a frame of linear radiance and a picture; no counterpart in the reference, whose display path is the clamp
