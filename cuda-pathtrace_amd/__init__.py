@@ -173,6 +173,10 @@ ABI = {
     "pt_temporal_reset": (ctypes.c_int, [_vp]),
     "pt_temporal_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     "pt_temporal_camera": (ctypes.c_int, [_fp, _fp]),
+    "pt_temporal_antilag_opts_default": (None, [_vp]),
+    "pt_temporal_antilag_check": (ctypes.c_int, [_vp, ctypes.c_float]),
+    "pt_temporal_set_antilag": (ctypes.c_int, [_vp, _vp]),
+    "pt_temporal_fast": (ctypes.c_int, [_vp, _vp, _vp]),
     "pt_temporal_enqueue": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _vp]),
     "pt_temporal_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _fp, _fp, _vp, _fp]),
     "pt_temporal_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _fp, _fp, ctypes.c_int, _vp, _vp]),
@@ -1187,6 +1191,27 @@ class TemporalOpts(ctypes.Structure):
                 ("albedo_tol", ctypes.c_float), ("min_weight", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class TemporalAntilagOpts(ctypes.Structure):
+    """pt_temporal_antilag_opts (include/ptcore.h)."""
+    _fields_ = [("fast_cap", ctypes.c_float), ("clamp_sigma", ctypes.c_float), ("clamp_radius", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def _antilag_defaults():
+    o = TemporalAntilagOpts()
+    lib.pt_temporal_antilag_opts_default(ctypes.byref(o))
+    return {"fast_cap": float(o.fast_cap), "clamp_sigma": float(o.clamp_sigma), "clamp_radius": int(o.clamp_radius)}
+
+
+ANTILAG_DEFAULTS = _antilag_defaults()  # pt_temporal_antilag_opts_default: fast_cap 0 (off), the library's clamp_sigma and clamp_radius
+
+
+def temporal_antilag_check(fast_cap, clamp_sigma=ANTILAG_DEFAULTS["clamp_sigma"], clamp_radius=ANTILAG_DEFAULTS["clamp_radius"],
+                           history_cap=256.0, reserved=0):
+    """pt_temporal_antilag_check: the host checks of Temporal.set_antilag alone; host only.  Raises PtError for what it refuses."""
+    opts = TemporalAntilagOpts(fast_cap=fast_cap, clamp_sigma=clamp_sigma, clamp_radius=clamp_radius, reserved=reserved)
+    check(lib.pt_temporal_antilag_check(ctypes.byref(opts), history_cap))
+
+
 def temporal_camera(basis):
     """pt_temporal_camera: the float32 inverse [3][3] of [B0 | B1-B0 | B2-B0] that carries a world offset from the eye to
     t (1, sy, v); host only.  Raises PtError for a degenerate or non-parallelogram basis."""
@@ -1203,16 +1228,44 @@ class Temporal(_Session):
     image, receives the accumulated counts (FeatureFilter's d_counts)."""
     _destroy = "pt_temporal_destroy"
 
-    def __init__(self, width, height, history_cap=256.0, depth_tol=0.02, normal_tol=0.9, albedo_tol=0.01, min_weight=0.25):
+    def __init__(self, width, height, history_cap=256.0, depth_tol=0.02, normal_tol=0.9, albedo_tol=0.01, min_weight=0.25, fast_cap=0.0,
+                 clamp_sigma=ANTILAG_DEFAULTS["clamp_sigma"], clamp_radius=ANTILAG_DEFAULTS["clamp_radius"]):
         opts = TemporalOpts(history_cap=history_cap, depth_tol=depth_tol, normal_tol=normal_tol, albedo_tol=albedo_tol, min_weight=min_weight)
+        antilag = TemporalAntilagOpts(fast_cap=fast_cap, clamp_sigma=clamp_sigma, clamp_radius=clamp_radius)
+        if fast_cap != 0.0:  # (refused here, before a session exists)
+            check(lib.pt_temporal_antilag_check(ctypes.byref(antilag), history_cap))
         h = _vp()
         check(lib.pt_temporal_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
         self.handle = h.value
         self.width, self.height = width, height
+        if fast_cap != 0.0:
+            self.set_antilag(fast_cap, clamp_sigma, clamp_radius)
+
+    def set_antilag(self, fast_cap, clamp_sigma=ANTILAG_DEFAULTS["clamp_sigma"], clamp_radius=ANTILAG_DEFAULTS["clamp_radius"]):
+        """pt_temporal_set_antilag: the responsive history (DENOISER.md, "Responsive history") on with fast_cap >= 1, off with 0.
+        Only while the session holds no history: before its first frame or right after reset()."""
+        opts = TemporalAntilagOpts(fast_cap=fast_cap, clamp_sigma=clamp_sigma, clamp_radius=clamp_radius)
+        check(lib.pt_temporal_set_antilag(self.handle, ctypes.byref(opts)))
+
+    def fast(self, out=None, stream=None):
+        """pt_temporal_fast: the fast image the last call wrote, a float32 torch tensor [H][W][4] {fast rgb, fast count} on the
+        current device (synchronous).  out: a tensor, a DeviceBuffer or a device address of width x height x 16 bytes to write
+        into instead, asynchronously on `stream`, and to return."""
+        if out is not None:
+            check(lib.pt_temporal_fast(self.handle, self._device_ptr(out), stream))
+            return out
+        import torch
+
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        check(lib.pt_temporal_fast(self.handle, out.data_ptr(), None))
+        torch.cuda.synchronize()
+        return out
 
     def memory(self):
         """{"workspace": bytes of the two history images (and, once a call with spheres= or scenes= needed it, of the session's
-        motion image), "per_pixel": bytes per pixel: 96, then 112}."""
+        motion image, and, once anti-lag was switched on, of the two fast images), "per_pixel": bytes per pixel: 96, + 16 with a
+        motion image, + 32 with anti-lag}."""
         b = ctypes.c_uint64(0)
         check(lib.pt_temporal_workspace_bytes(self.handle, ctypes.byref(b)))
         return {"workspace": int(b.value), "per_pixel": int(b.value) // (self.width * self.height)}
@@ -1337,7 +1390,8 @@ def accumulate_frames(frames, samples, bases, eyes, temporal=None, scenes=None, 
     """Convenience for tests, like filter_frames: host frames [N][H][W][14] of one fly-through through ONE
     pt_temporal_run_frames call of a fresh session (or `temporal`, whose history then goes in).  Returns (the frames after the
     stage, the uint32 [H][W] counts of the last frame).  scenes: host spheres [N][n], the scene of every frame (animated
-    scenes: pt_temporal_run_frames_scenes).  opts: of the Temporal made here."""
+    scenes: pt_temporal_run_frames_scenes).  opts: of the Temporal made here, fast_cap, clamp_sigma and clamp_radius (the
+    responsive history) among them."""
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
     ta = temporal or Temporal(w, h, **opts)

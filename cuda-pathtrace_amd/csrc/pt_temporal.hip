@@ -11,6 +11,9 @@
 // Moving spheres (DENOISER.md, "Moving spheres"; tests/temporal_motion_model.py): the MOTION instantiation of that kernel takes a
 // per-pixel motion image and carries the world point back by it before the previous camera looks; motion_kernel builds such an
 // image from the spheres of this frame and of the previous one, which the _scene calls remember on the host.
+// Responsive history (DENOISER.md, "Responsive history"; tests/temporal_antilag_model.py): the FAST instantiations of the
+// accumulate kernel carry a second, short history {colour, count} through the same four taps, and rectify_kernel clamps the long
+// history's colour into the range that short history shows in the (2R+1)^2 window around the pixel.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -48,18 +51,28 @@ __device__ __forceinline__ float primary_direction(float b0, float e1, float b2,
   return a + v * (b - a);
 }
 
-template <class T>
-__device__ __forceinline__ T first(T a) {
+template <class T, class... REST>
+__device__ __forceinline__ T first(T a, REST...) {
   return a;
+}
+
+template <int N, class T, class... REST>
+__device__ __forceinline__ auto pick(T a, REST... rest) {
+  if constexpr (N == 0) return a;
+  else return pick<N - 1>(rest...);
 }
 
 // MOTION: one more argument, `motion`, holds {mx, my, mz, w} per pixel (motion_kernel below) and the world point is carried back
 // by m before the previous camera looks at it.  accumulate_kernel<false> takes no such argument: it has the signature, and
 // instruction for instruction the code, that the kernel had before it became a template.
+// FAST: three more arguments behind that, `fin`, `fout` (the fast history read and written, one float4 {colour, count} per pixel)
+// and `fast_cap` -- in the pack and not in Params, so that the kernels without them keep their argument layout and their code.
 template <bool MOTION, class... IMAGE>
 __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __restrict__ frame, const float4* __restrict__ hin,
                                                             float4* __restrict__ hout, uint32_t* __restrict__ counts, IMAGE... motion) {
-  static_assert(sizeof...(IMAGE) == (MOTION ? 1 : 0), "accumulate_kernel<true, const float4*> or accumulate_kernel<false>");
+  constexpr int NM = MOTION ? 1 : 0;
+  constexpr bool FAST = sizeof...(IMAGE) == NM + 3;
+  static_assert(sizeof...(IMAGE) == NM || FAST, "accumulate_kernel<MOTION[, const float4* motion][, const float4* fin, float4* fout, float fast_cap]>");
   const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
   if (x >= p.width || y >= p.height) return;
   const uint32_t W = (uint32_t)p.width, i = (uint32_t)y * W + (uint32_t)x;
@@ -70,6 +83,7 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
   const float z = px[9], s2c = px[10];
 
   float hx = 0.0f, hy = 0.0f, hz = 0.0f, hs2 = 0.0f, hN = 0.0f;
+  float fx = 0.0f, fy = 0.0f, fz = 0.0f, fN = 0.0f;  // FAST: the fast history of the pixel
   if (p.has_history) {  // uniform
     const float sy = (float)x / p.fh, v = 1.0f - (float)y / p.fw;
     float X[3];
@@ -95,6 +109,7 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
     const int r0 = (int)r0f, c0 = (int)c0f;  // -1 .. height - 1, -1 .. width - 1
     const float dtol = p.depth_tol * al;
     float ws = 0.0f, sx = 0.0f, sy2 = 0.0f, sz = 0.0f, ss = 0.0f, sn = 0.0f;
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f, gn = 0.0f;
 #pragma unroll
     for (int dr = 0; dr < 2; dr++) {
 #pragma unroll
@@ -118,12 +133,22 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
         sx = sx + w * tx, sy2 = sy2 + w * ty, sz = sz + w * tz;
         ss = ss + w * ts;
         sn = sn + w * tn;
+        if constexpr (FAST) {  // the same taps, the same weights: all four components selected, never multiplied
+          const float4 tf = pick<NM>(motion...)[q];
+          const float ux = valid ? tf.x : 0.0f, uy = valid ? tf.y : 0.0f, uz = valid ? tf.z : 0.0f, un = valid ? tf.w : 0.0f;
+          gx = gx + w * ux, gy = gy + w * uy, gz = gz + w * uz;
+          gn = gn + w * un;
+        }
       }
     }
     const bool keep = ws >= p.min_weight;
     hx = keep ? sx / ws : 0.0f, hy = keep ? sy2 / ws : 0.0f, hz = keep ? sz / ws : 0.0f;
     hs2 = keep ? ss / ws : 0.0f;
     hN = keep ? fminf(sn / ws, p.cap) : 0.0f;
+    if constexpr (FAST) {
+      fx = keep ? gx / ws : 0.0f, fy = keep ? gy / ws : 0.0f, fz = keep ? gz / ws : 0.0f;
+      fN = keep ? fminf(gn / ws, pick<NM + 2>(motion...)) : 0.0f;
+    }
   }
 
   const float tot = hN + p.n, k = p.n / tot;
@@ -138,6 +163,71 @@ __global__ void __launch_bounds__(BX* BY) accumulate_kernel(Params p, float* __r
   hout[p.pixels + i] = make_float4(nx, ny, nz, z);
   hout[2 * p.pixels + i] = make_float4(ax, ay, az, tot);
   if (counts) counts[i] = (uint32_t)floorf(tot + 0.5f);
+  if constexpr (FAST) {
+    const float ftot = fN + p.n, kf = p.n / ftot;
+    pick<NM + 1>(motion...)[i] = make_float4(fx + kf * (cx - fx), fy + kf * (cy - fy), fz + kf * (cz - fz), ftot);
+  }
+}
+
+// ---- rectify: clamp the long history's colour into the fast history's neighbourhood range --------------------------------------
+// One lane per pixel.  The workgroup stages the (BX + 2R) x (BY + 2R) tile of the fast image that its windows cover in LDS
+// (38 x 14 float4 = 8.3 KB at R = 3); a tap outside the frame is FLAGGED there (.w = -1: a fast count is >= n >= 1), not clamped
+// to the edge, and does not count.  The staging loop and the barrier are uniform over the workgroup: lanes outside the frame stage
+// with the others and leave after the barrier.  Each lane then walks its window in row-major order, unrolled by R, so the sums
+// are the definition's: sequential from +0, every product rounded before it is added.
+struct RectifyParams {
+  int width, height;
+  uint32_t pixels;
+  float k;  // clamp_sigma
+};
+
+__device__ __forceinline__ float rectify_channel(float x, float s1, float s2, float m, float k) {
+  const float mu = s1 / m;
+  const float v = s2 / m - mu * mu;
+  const float var = v > 0.0f ? v : 0.0f;  // (a NaN gives 0)
+  const float sd = k * sqrtf(var);  // (IEEE: the compiler expands it with its fix-up, as in pt_device.h)
+  const float lo = mu - sd, hi = mu + sd;
+  return x < lo ? lo : (x > hi ? hi : x);  // (NaN bounds pass x)
+}
+
+template <int R>
+__global__ void __launch_bounds__(BX* BY) rectify_kernel(RectifyParams p, float* __restrict__ frame, const float4* __restrict__ fast,
+                                                         float4* __restrict__ hist) {
+  constexpr int TW = BX + 2 * R, TH = BY + 2 * R;
+  __shared__ float4 tile[TH * TW];
+  const int x0 = blockIdx.x * BX - R, y0 = blockIdx.y * BY - R;
+  const int lane = threadIdx.y * BX + threadIdx.x;
+  for (int j = lane; j < TH * TW; j += BX * BY) {  // (uniform bounds)
+    const int ty = j / TW, tx = j - ty * TW;
+    const int gx = x0 + tx, gy = y0 + ty;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    if (gx >= 0 && gx < p.width && gy >= 0 && gy < p.height) t = fast[(uint32_t)gy * (uint32_t)p.width + (uint32_t)gx];
+    tile[j] = t;
+  }
+  __syncthreads();
+  const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+  if (x >= p.width || y >= p.height) return;
+  const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+  const float ftot = tile[(threadIdx.y + R) * TW + threadIdx.x + R].w;
+  const float tot = hist[2 * p.pixels + i].w;
+  if (!(tot > ftot)) return;  // inactive: the long history is no longer than the fast one, nothing is written
+  float m = 0.0f, ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f;
+#pragma unroll
+  for (int dy = 0; dy <= 2 * R; dy++) {
+#pragma unroll
+    for (int dx = 0; dx <= 2 * R; dx++) {
+      const float4 t = tile[(threadIdx.y + dy) * TW + threadIdx.x + dx];
+      const bool in = !(t.w < 0.0f);
+      m = in ? m + 1.0f : m;
+      ax = in ? ax + t.x : ax, ay = in ? ay + t.y : ay, az = in ? az + t.z : az;
+      bx = in ? bx + t.x * t.x : bx, by = in ? by + t.y * t.y : by, bz = in ? bz + t.z * t.z : bz;
+    }
+  }
+  const float4 c = hist[i];
+  const float ox = rectify_channel(c.x, ax, bx, m, p.k), oy = rectify_channel(c.y, ay, by, m, p.k), oz = rectify_channel(c.z, az, bz, m, p.k);
+  float* px = frame + (size_t)i * 14;
+  px[0] = ox, px[1] = oy, px[2] = oz;
+  hist[i] = make_float4(ox, oy, oz, c.w);
 }
 
 // ---- the motion image ---------------------------------------------------------------------------------------------------
@@ -225,6 +315,10 @@ struct pt_temporal {
   pt_sphere* scene = nullptr;  // host copy of the previous _scene call's spheres, [scene_cap]
   int scene_n = 0, scene_cap = 0;
   bool has_scene = false;
+  // responsive history (pt_temporal_set_antilag): off while antilag.fast_cap == 0
+  pt_temporal_antilag_opts antilag{};
+  float4* d_fast = nullptr;  // [2][pixels] {fast colour, fast count}, allocated by the first call that switches on
+  int fcur = 0;              // the copy the last call wrote
 };
 
 using pt_stage::finite_f;
@@ -262,7 +356,22 @@ static int camera_matrix(const char* who, const float basis[12], float P[9]) {
 
 static size_t hist_bytes(const pt_temporal* t) { return (size_t)2 * 3 * t->width * t->height * sizeof(float4); }
 static size_t motion_bytes(const pt_temporal* t) { return (size_t)t->width * t->height * sizeof(float4); }
-static size_t ws_bytes(const pt_temporal* t) { return hist_bytes(t) + (t->d_motion ? motion_bytes(t) : 0); }
+static size_t fast_bytes(const pt_temporal* t) { return (size_t)2 * t->width * t->height * sizeof(float4); }
+static size_t ws_bytes(const pt_temporal* t) {
+  return hist_bytes(t) + (t->d_motion ? motion_bytes(t) : 0) + (t->d_fast ? fast_bytes(t) : 0);
+}
+
+// Everything pt_temporal_set_antilag checks about its options; no device.
+static int check_antilag(const char* who, const pt_temporal_antilag_opts* o, float history_cap) {
+  if (!o) return pt_fail(PT_EINVAL, "%s: null opts", who);
+  if (o->fast_cap != 0.0f && !(o->fast_cap >= 1.0f && o->fast_cap < history_cap))
+    return pt_fail(PT_EINVAL, "%s: fast_cap %g must be 0 (off) or >= 1 and < history_cap = %g", who, (double)o->fast_cap, (double)history_cap);
+  if (!(o->clamp_sigma > 0.0f) || !finite_f(o->clamp_sigma))
+    return pt_fail(PT_EINVAL, "%s: clamp_sigma %g must be finite and > 0", who, (double)o->clamp_sigma);
+  if (o->clamp_radius < 1 || o->clamp_radius > 3) return pt_fail(PT_EINVAL, "%s: clamp_radius %d outside 1 .. 3", who, o->clamp_radius);
+  if (o->reserved != 0) return pt_fail(PT_EINVAL, "%s: reserved = %d must be 0", who, o->reserved);
+  return PT_OK;
+}
 
 // (every check before any launch: a refused call launches nothing and leaves the session as it was)
 static int check_args(const char* who, const pt_temporal* t, int n_frames, const float* d_frames, size_t frame_stride_floats,
@@ -431,7 +540,28 @@ static int accumulate_frame(const char* who, pt_temporal* t, Params& p, float* d
   float4* hin = t->d_hist + (size_t)t->cur * 3 * p.pixels;
   float4* hout = t->d_hist + (size_t)(1 - t->cur) * 3 * p.pixels;
   const dim3 block(BX, BY), grid((unsigned)((p.width + BX - 1) / BX), (unsigned)((p.height + BY - 1) / BY));
-  if (d_motion)
+  if (t->antilag.fast_cap > 0.0f) {
+    // the FAST form, and behind it -- unless the frame passes through -- the rectify launch on what it wrote
+    const float4* fin = t->d_fast + (size_t)t->fcur * p.pixels;
+    float4* fout = t->d_fast + (size_t)(1 - t->fcur) * p.pixels;
+    const float fast_cap = t->antilag.fast_cap;
+    if (d_motion)
+      hipLaunchKernelGGL((accumulate_kernel<true, const float4*, const float4*, float4*, float>), grid, block, 0, s, p, d_frame, (const float4*)hin,
+                         hout, d_counts, d_motion, fin, fout, fast_cap);
+    else
+      hipLaunchKernelGGL((accumulate_kernel<false, const float4*, float4*, float>), grid, block, 0, s, p, d_frame, (const float4*)hin, hout,
+                         d_counts, fin, fout, fast_cap);
+    PT_HIP(hipGetLastError());
+    if (p.has_history) {
+      RectifyParams rp{p.width, p.height, p.pixels, t->antilag.clamp_sigma};
+      switch (t->antilag.clamp_radius) {
+        case 1: hipLaunchKernelGGL((rectify_kernel<1>), grid, block, 0, s, rp, d_frame, (const float4*)fout, hout); break;
+        case 2: hipLaunchKernelGGL((rectify_kernel<2>), grid, block, 0, s, rp, d_frame, (const float4*)fout, hout); break;
+        default: hipLaunchKernelGGL((rectify_kernel<3>), grid, block, 0, s, rp, d_frame, (const float4*)fout, hout); break;
+      }
+    }
+    t->fcur = 1 - t->fcur;
+  } else if (d_motion)
     hipLaunchKernelGGL((accumulate_kernel<true, const float4*>), grid, block, 0, s, p, d_frame, (const float4*)hin, hout, d_counts, d_motion);
   else
     hipLaunchKernelGGL((accumulate_kernel<false>), grid, block, 0, s, p, d_frame, (const float4*)hin, hout, d_counts);
@@ -565,6 +695,7 @@ int pt_temporal_destroy(pt_temporal* t) {
   if (!t) return PT_OK;
   if (t->d_hist) (void)hipFree(t->d_hist);
   if (t->d_motion) (void)hipFree(t->d_motion);
+  if (t->d_fast) (void)hipFree(t->d_fast);
   if (t->d_spheres) (void)hipFree(t->d_spheres);
   if (t->h_spheres) (void)hipHostFree(t->h_spheres);
   for (int k = 0; k < t->n_retired; k++) {
@@ -617,6 +748,45 @@ int pt_temporal_reset(pt_temporal* t) {
 int pt_temporal_workspace_bytes(const pt_temporal* t, uint64_t* bytes) {
   if (!t || !bytes) return pt_fail(PT_EINVAL, "pt_temporal_workspace_bytes: null %s", t ? "output pointer" : "accumulator");
   *bytes = ws_bytes(t);
+  return PT_OK;
+}
+
+void pt_temporal_antilag_opts_default(pt_temporal_antilag_opts* opts) {
+  if (!opts) return;
+  *opts = pt_temporal_antilag_opts{};
+  opts->fast_cap = 0.0f;
+  opts->clamp_sigma = PT_ANTILAG_DEFAULT_SIGMA, opts->clamp_radius = PT_ANTILAG_DEFAULT_RADIUS;
+}
+
+int pt_temporal_antilag_check(const pt_temporal_antilag_opts* opts, float history_cap) {
+  return check_antilag("pt_temporal_antilag_check", opts, history_cap);
+}
+
+int pt_temporal_set_antilag(pt_temporal* t, const pt_temporal_antilag_opts* opts) {
+  const char* who = "pt_temporal_set_antilag";
+  if (!t) return pt_fail(PT_EINVAL, "%s: null accumulator", who);
+  const int rc = check_antilag(who, opts, t->opts.history_cap);
+  if (rc != PT_OK) return rc;
+  if (t->has_history) return pt_fail(PT_EINVAL, "%s: the session holds a history: reset the session", who);
+  if (opts->fast_cap > 0.0f && !t->d_fast) {
+    const hipError_t e = hipMalloc((void**)&t->d_fast, fast_bytes(t));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      t->d_fast = nullptr;
+      return pt_fail(PT_EHIP, "%s: the fast images of %zu bytes: %s; the session is as it was", who, fast_bytes(t), hipGetErrorString(e));
+    }
+  }
+  t->antilag = *opts;
+  return PT_OK;
+}
+
+int pt_temporal_fast(pt_temporal* t, float* d_out, void* hip_stream) {
+  const char* who = "pt_temporal_fast";
+  if (!t || !d_out) return pt_fail(PT_EINVAL, "%s: null %s", who, t ? "d_out" : "accumulator");
+  if (!(t->antilag.fast_cap > 0.0f)) return pt_fail(PT_EINVAL, "%s: anti-lag is off (pt_temporal_set_antilag, fast_cap > 0)", who);
+  if (!t->has_history) return pt_fail(PT_EINVAL, "%s: no frame has run since the session was made or reset", who);
+  const size_t pixels = (size_t)t->width * t->height;
+  PT_HIP(hipMemcpyAsync(d_out, t->d_fast + (size_t)t->fcur * pixels, pixels * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
   return PT_OK;
 }
 

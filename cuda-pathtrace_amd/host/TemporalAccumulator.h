@@ -59,6 +59,18 @@ class TemporalAccumulator {
   }
   // the scene changed: the next frame passes through
   void Reset() { gpuErrchk(pt_temporal_reset(session)); }
+  // the responsive history (pt_temporal_set_antilag): a second history of at most fast_cap samples, and after every Accumulate
+  // the long history's colour is clamped into mu +- sigma standard deviations of the fast colours in the (2 radius + 1)^2 window
+  // around the pixel, so that shadows and indirect light of moving spheres do not lag.  fast_cap 0 switches it off.  Only before
+  // the first frame or right after Reset(); a bad value exits like every error.
+  void SetAntilag(float fast_cap, float sigma = PT_ANTILAG_DEFAULT_SIGMA, int radius = PT_ANTILAG_DEFAULT_RADIUS) {
+    pt_temporal_antilag_opts o;
+    pt_temporal_antilag_opts_default(&o);
+    o.fast_cap = fast_cap, o.clamp_sigma = sigma, o.clamp_radius = radius;
+    gpuErrchk(pt_temporal_set_antilag(session, &o));
+  }
+  // debug view: the fast image the last Accumulate wrote, [height][width][4] floats {fast rgb, fast count}, into d_out
+  void Fast(float* d_out, void* hip_stream = NULL) { gpuErrchk(pt_temporal_fast(session, d_out, hip_stream)); }
 
  private:
   void Pose(const Camera& camera, float basis[12], float eye[3]) const {

@@ -21,6 +21,7 @@
 // after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts),
 // --velocities FILE (with --frames / --poses: the spheres listed move at a constant velocity, the scene is uploaded before every
 // frame's Render(), and --temporal accumulates through pt_temporal_run_scene, which follows them),
+// --temporal-fast-cap X (with --temporal: the accumulator's responsive history, pt_temporal_set_antilag, against lagging light),
 // --tonemap CURVE (ToneMapper / pt_tonemap_*: every frame of the headless loop and every progressive pass goes through the
 // session after --temporal, --filter and -d, so that --tonemap-adapt acts as eye adaptation; the last frame's sRGB picture is
 // written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes),
@@ -91,6 +92,12 @@ static void usage() {
                "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
                "  --temporal                    with --frames / --poses: reproject and accumulate every frame over the last ones\n"
                "  --temporal-cap arg            with --temporal: cap of the accumulated history in samples, >= 1 (default 256)\n"
+               "  --temporal-fast-cap arg       with --temporal: responsive history: keep a second history of at most arg samples\n"
+               "                                (>= 1 and < the cap) and clamp the long one into its neighbourhood range, so that\n"
+               "                                shadows and indirect light of moving spheres do not lag (default: off)\n"
+               "  --temporal-clamp-sigma arg    with --temporal-fast-cap: half-width of the clamp box in standard deviations, > 0\n"
+               "                                (default 1)\n"
+               "  --temporal-clamp-radius arg   with --temporal-fast-cap: the window is (2 arg + 1)^2 pixels, 1 .. 3 (default 1)\n"
                "  --velocities arg              with --frames / --poses: file of 'index vx vy vz' lines; sphere index moves by v per frame\n"
                "                                (with --temporal every pixel follows the sphere it shows)\n"
                "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
@@ -133,6 +140,10 @@ int main(int argc, const char** argv) {
   // --temporal: the temporal accumulator (pt_temporal_*) in place after every Render() of the frame loop
   bool temporal = false, temporalCapGiven = false;
   double temporalCap = 256.0;
+  // --temporal-fast-cap [--temporal-clamp-sigma, --temporal-clamp-radius]: the responsive history (pt_temporal_set_antilag)
+  bool fastCapGiven = false, clampSigmaGiven = false, clampRadiusGiven = false;
+  pt_temporal_antilag_opts antilagOpts;
+  pt_temporal_antilag_opts_default(&antilagOpts);
   // --tonemap CURVE: the tone-mapping session (pt_tonemap_*) after every other stage of a frame
   std::string tonemapCurve, tonemapExposure, tonemapEncode;
   bool tonemapGiven = false;
@@ -181,6 +192,9 @@ int main(int argc, const char** argv) {
     else if (a == "--filter-sigma") { filterSigma = value("--filter-sigma"); filterSigmaGiven = true; }
     else if (a == "--temporal") temporal = true;
     else if (a == "--temporal-cap") { temporalCap = atof(value("--temporal-cap")); temporalCapGiven = true; }
+    else if (a == "--temporal-fast-cap") { antilagOpts.fast_cap = (float)atof(value("--temporal-fast-cap")); fastCapGiven = true; }
+    else if (a == "--temporal-clamp-sigma") { antilagOpts.clamp_sigma = (float)atof(value("--temporal-clamp-sigma")); clampSigmaGiven = true; }
+    else if (a == "--temporal-clamp-radius") { antilagOpts.clamp_radius = atoi(value("--temporal-clamp-radius")); clampRadiusGiven = true; }
     else if (a == "--tonemap") { tonemapCurve = value("--tonemap"); tonemapGiven = true; }
     else if (a == "--exposure") { tonemapExposure = value("--exposure"); if (!tonemapOption) tonemapOption = "--exposure"; }
     else if (a == "--tonemap-key") { tonemapKey = atof(value("--tonemap-key")); tonemapKeyGiven = true; if (!tonemapOption) tonemapOption = "--tonemap-key"; }
@@ -285,6 +299,15 @@ int main(int argc, const char** argv) {
     std::cerr << "ERROR: --temporal-cap needs --temporal: it caps the accumulator's history" << std::endl;
     return 1;
   }
+  if (fastCapGiven && !temporal) {
+    std::cerr << "ERROR: --temporal-fast-cap needs --temporal: it is the accumulator's second, short history" << std::endl;
+    return 1;
+  }
+  if ((clampSigmaGiven || clampRadiusGiven) && !fastCapGiven) {
+    std::cerr << "ERROR: " << (clampSigmaGiven ? "--temporal-clamp-sigma" : "--temporal-clamp-radius")
+              << " needs --temporal-fast-cap: it shapes the clamp of the responsive history" << std::endl;
+    return 1;
+  }
   if (temporal) {
     if (progressiveGiven) {
       std::cerr << "ERROR: --temporal cannot be combined with --progressive: a still frame has the progressive session" << std::endl;
@@ -303,6 +326,16 @@ int main(int argc, const char** argv) {
       return 1;
     }
     temporalOpts.history_cap = (float)temporalCap;
+    if (fastCapGiven) {  // the library's own host checks, before any device is touched
+      if (!(antilagOpts.fast_cap >= 1.0f)) {
+        std::cerr << "ERROR: --temporal-fast-cap: fast_cap " << antilagOpts.fast_cap << " must be >= 1 (leave the option out for off)" << std::endl;
+        return 1;
+      }
+      if (pt_temporal_antilag_check(&antilagOpts, temporalOpts.history_cap) != PT_OK) {
+        std::cerr << "ERROR: --temporal-fast-cap: " << pt_last_error() << std::endl;
+        return 1;
+      }
+    }
   }
   // --velocities: the list and the scene of frame 0 on the host (before any device is touched)
   std::vector<SphereVelocity> velocities;
@@ -477,6 +510,7 @@ int main(int argc, const char** argv) {
   FeatureFilter* filter = filtering ? new FeatureFilter(width, height, filterOpts) : NULL;
   // --temporal: likewise; with --filter its per-pixel counts replace the filter's uniform count
   TemporalAccumulator* accumulator = temporal ? new TemporalAccumulator(width, height, temporalOpts) : NULL;
+  if (accumulator && fastCapGiven) accumulator->SetAntilag(antilagOpts.fast_cap, antilagOpts.clamp_sigma, antilagOpts.clamp_radius);
   unsigned int* d_temporalCounts = NULL;
   if (accumulator && filter) gpuErrchk(pt_malloc((void**)&d_temporalCounts, (size_t)width * height * sizeof(unsigned int)));
   // --tonemap: likewise; it reads the frame the other stages left and writes its own RGBA8 image

@@ -499,7 +499,7 @@ int pt_temporal_run_frames(pt_temporal* t, int n_frames, float* d_frames, size_t
  * The kernel tests every sphere for every pixel (no grid), PT_MOTION_CHUNK spheres per round through LDS.
  * Limits: rigid translation only (a changed radius is refused); the centre ray decides a pixel's sphere, so silhouettes restart
  * as they do anyway; a moving sphere's shadow and its indirect light on static surfaces are not followed and lag by up to
- * history_cap samples: use a small cap for animated scenes. */
+ * history_cap samples: use a small cap for animated scenes, or the responsive history below. */
 #define PT_MOTION_CHUNK 256
 /* The host checks of pt_temporal_motion alone (no device, no session): PT_EINVAL naming the argument for a null pointer, n
  * outside 1 .. 65535, a field of either array that is not finite (colour and emission are checked, though not read), a radius
@@ -543,6 +543,47 @@ int pt_temporal_enqueue_frames_scenes(pt_temporal* t, int n_frames, float* d_fra
                                       const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, void* hip_stream);
 int pt_temporal_run_frames_scenes(pt_temporal* t, int n_frames, float* d_frames, size_t frame_stride_floats, const float* bases,
                                   const float* eyes, const pt_sphere* h_scenes, int n, int samples, uint32_t* d_counts, float* ms_out);
+
+/* -- responsive history: a fast history that clamps the long one (DENOISER.md, "Responsive history") --
+ * What a moving sphere does to OTHER surfaces -- its shadow, its indirect light -- is not followed by the motion image and would
+ * lag by up to history_cap samples.  With anti-lag on, the session keeps a second history of at most fast_cap samples beside the
+ * long one (two more images used ping-pong, one float4 {colour, count} per pixel each: 32 more bytes of workspace per pixel), and
+ * after every accumulate launch a second launch clamps the long history's colour, per pixel and channel, into mu +- clamp_sigma x
+ * sigma of the fast colours in the (2 clamp_radius + 1)^2 window around the pixel.  Stable light lies inside that box and keeps
+ * all its samples; changed light is pulled to the recent frames.  EXACT code, restated in tests/temporal_antilag_model.py:
+ *   fast      the same four taps, validity and weights as the pixel step above; {fC', fn'} = the tap's fast float4, selected to 0
+ *             when invalid; fhC = sum(w fC') / Ws, fhN = min(sum(w fn') / Ws, fast_cap) when Ws >= min_weight, else 0;
+ *             ftot = fhN + n;  fC = fhC + (n / ftot) (C - fhC);  {fC, ftot} goes into the other fast image.
+ *   rectify   not issued on a call without history.  Window rows r-R .. r+R, columns c-R .. c+R in row-major order, only the m
+ *             taps inside the frame; per channel S1 = sum x, S2 = sum (x x) sequentially from +0; mu = S1 / m; v = S2 / m - mu mu;
+ *             var = v > 0 ? v : 0; sigma = sqrt(var); lo = mu - k sigma; hi = mu + k sigma.  A pixel is active iff tot > ftot;
+ *             an active pixel's colour x becomes x < lo ? lo : (x > hi ? hi : x) in channels 0-2 of the frame and in the long
+ *             history; channel 10, the counts and the fast image are not touched, an inactive pixel is not written.
+ * Limits: the window ignores surfaces (a silhouette widens sigma, so the clamp only acts less there); a clamped pixel keeps its
+ * count and its variance; a +-Inf in a window drags its neighbours' bounds to it (a NaN switches their clamp off). */
+typedef struct pt_temporal_antilag_opts {
+  float fast_cap;       /* 0 = off (the session of the sections above).  Otherwise >= 1 and < the session's history_cap */
+  float clamp_sigma;    /* k: half-width of the clamp box in standard deviations, finite, > 0 (default 1)             */
+  int32_t clamp_radius; /* R: the window is (2R+1)^2, 1 .. 3 (default 1)                                              */
+  int32_t reserved;     /* must be 0                                                                                  */
+} pt_temporal_antilag_opts;
+#define PT_ANTILAG_DEFAULT_SIGMA 1.0f
+#define PT_ANTILAG_DEFAULT_RADIUS 1
+void pt_temporal_antilag_opts_default(pt_temporal_antilag_opts* opts); /* fast_cap 0 (off), clamp_sigma and clamp_radius as above */
+/* The host checks of pt_temporal_set_antilag alone (no device, no session) for a session of the given history_cap: PT_EINVAL
+ * naming the field for a null opts, fast_cap that is neither 0 nor in [1, history_cap), clamp_sigma that is not finite and > 0,
+ * clamp_radius outside 1 .. 3 and reserved != 0. */
+int pt_temporal_antilag_check(const pt_temporal_antilag_opts* opts, float history_cap);
+/* Switches the responsive history of a session on (fast_cap > 0) or off (fast_cap == 0: today's launches; the fast images may
+ * stay allocated and reported).  Accepted only while the session holds no history -- before its first frame or right after
+ * pt_temporal_reset -- otherwise PT_EINVAL "reset the session".  Every value is checked before a device is touched
+ * (pt_temporal_antilag_check); a refused call leaves the session as it was.  Switching on allocates the fast images (hipMalloc:
+ * not under stream capture), reported by pt_temporal_workspace_bytes from then on.  Every enqueue / run call of the session,
+ * with or without a motion image or a scene, then takes the FAST form; a batch stays the loop of single calls bit for bit. */
+int pt_temporal_set_antilag(pt_temporal* t, const pt_temporal_antilag_opts* opts);
+/* Debug view: copies the fast image the last call wrote, [height][width][4] floats {fast rgb, fast count}, into d_out,
+ * asynchronous on hip_stream.  PT_EINVAL if anti-lag is off or no frame has run since the session was made or reset. */
+int pt_temporal_fast(pt_temporal* t, float* d_out, void* hip_stream);
 
 /* ---- tone mapping: metered exposure, a filmic curve and sRGB bytes ---------------------------- */
 /* The stage between a frame of linear radiance and a picture; no counterpart in the reference, whose display path is the clamp
