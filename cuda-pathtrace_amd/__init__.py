@@ -262,6 +262,10 @@ LAB_ABI = {
     "pt_debug_denoiser_conv_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                    ctypes.c_char_p, ctypes.c_size_t]),
     "pt_debug_denoiser_run_conv": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "pt_debug_denoiser_activation_frames": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_size_t]),
+    "pt_debug_denoiser_set_activation_frames": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_size_t]),
+    "pt_debug_denoiser_run_conv_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t]),
+    "pt_debug_denoiser_run_pre": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_int]),
     "pt_debug_denoiser_memory": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "pt_debug_denoiser_last_enqueue": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_denoiser_conv_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -1011,15 +1015,23 @@ class Denoiser(_BatchedStage):
             out.append((name.value.decode(), tuple(shape)))
         return out
 
-    def activation(self, layer):
+    def activation(self, layer, frames=None):
+        """Layer `layer` of the first frame, [rows][cols][channels]; frames=g: of the first g frames, [g][rows][cols][channels]."""
         shape = self.layers()[layer][1]
-        out = np.empty(shape, dtype=np.float32)
-        check(lib.pt_debug_denoiser_activation(self.handle, layer, out.ctypes.data, out.size))
+        if frames is None:
+            out = np.empty(shape, dtype=np.float32)
+            check(lib.pt_debug_denoiser_activation(self.handle, layer, out.ctypes.data, out.size))
+        else:
+            out = np.empty((max(frames, 0),) + shape, dtype=np.float32)
+            check(lib.pt_debug_denoiser_activation_frames(self.handle, layer, frames, out.ctypes.data, out.size))
         return out
 
-    def set_activation(self, layer, arr):
+    def set_activation(self, layer, arr, frames=None):
         arr = np.ascontiguousarray(arr, dtype=np.float32)
-        check(lib.pt_debug_denoiser_set_activation(self.handle, layer, arr.ctypes.data, arr.size))
+        if frames is None:
+            check(lib.pt_debug_denoiser_set_activation(self.handle, layer, arr.ctypes.data, arr.size))
+        else:
+            check(lib.pt_debug_denoiser_set_activation_frames(self.handle, layer, frames, arr.ctypes.data, arr.size))
 
     def convs(self):
         """[(name, info dict)] of every convolution in execution order (pt_debug_denoiser_conv_info)."""
@@ -1032,8 +1044,19 @@ class Denoiser(_BatchedStage):
             out.append((name.value.decode(), dict(zip(keys, list(info)))))
         return out
 
-    def run_conv(self, conv, d_rgb=None):
-        check(lib.pt_debug_denoiser_run_conv(self.handle, conv, d_rgb))
+    def run_conv(self, conv, d_out=None, frames=None, ld=3, frame_stride=None):
+        """Convolution `conv` alone, synchronous.  frames=g: of the plan of a group of g frames, on the first g frames of the
+        workspace; the head writes d_out[f * frame_stride + pixel * ld + (0 .. 2)] (frame_stride in floats, default packed)."""
+        if frames is None:
+            check(lib.pt_debug_denoiser_run_conv(self.handle, conv, d_out))
+        else:
+            fs = self.width * self.height * ld if frame_stride is None else frame_stride
+            check(lib.pt_debug_denoiser_run_conv_frames(self.handle, conv, d_out, frames, ld, fs))
+
+    def run_pre(self, d_frames, frames, frame_stride=None, inplace=True):
+        """The pre-processing of a group of `frames` frames alone, synchronous (frame_stride in floats, default packed)."""
+        fs = self.width * self.height * CHANNELS if frame_stride is None else frame_stride
+        check(lib.pt_debug_denoiser_run_pre(self.handle, d_frames, frames, fs, 1 if inplace else 0))
 
     def memory(self):
         """Bytes (pt_debug_denoiser_memory): {"element", "workspace", "partials", "weights", "layers": [(name, offset, bytes

@@ -1141,24 +1141,44 @@ int pt_debug_denoiser_layer_info(pt_denoiser* d, int layer, int* n_layers, int s
   return PT_OK;
 }
 
-int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats) {
+// The group hooks take 1 .. max_frames frames: what the workspace was laid out for.
+static int check_group(const pt_denoiser* d, int frames, const char* who) {
+  if (frames < 1 || frames > d->max_frames)
+    return pt_fail(PT_EINVAL, "%s: frames %d outside 1 .. max_frames = %d", who, frames, d->max_frames);
+  return PT_OK;
+}
+
+// (the first `frames` frames of an activation laid out for max_frames are contiguous from its offset)
+int pt_debug_denoiser_activation_frames(pt_denoiser* d, int layer, int frames, float* h_out, size_t n_floats) {
   if (!d || !h_out || layer < 0 || layer >= (int)d->acts.size())
     return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: bad arguments");
+  const int rc = check_group(d, frames, "pt_debug_denoiser_activation");
+  if (rc != PT_OK) return rc;
   const Act& a = d->acts[layer];
-  const size_t n = (size_t)a.h * a.w * a.c;
+  const size_t n = (size_t)frames * a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PT_HIP(hipDeviceSynchronize());
   return d->precision == PT_DENOISE_F16 ? copy_out<_Float16>(d, a, h_out, n) : copy_out<float>(d, a, h_out, n);
 }
 
-int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats) {
+int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats) {
+  return pt_debug_denoiser_activation_frames(d, layer, 1, h_out, n_floats);
+}
+
+int pt_debug_denoiser_set_activation_frames(pt_denoiser* d, int layer, int frames, const float* h_in, size_t n_floats) {
   if (!d || !h_in || layer < 0 || layer >= (int)d->acts.size())
     return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: bad arguments");
+  const int rc = check_group(d, frames, "pt_debug_denoiser_set_activation");
+  if (rc != PT_OK) return rc;
   const Act& a = d->acts[layer];
-  const size_t n = (size_t)a.h * a.w * a.c;
+  const size_t n = (size_t)frames * a.h * a.w * a.c;
   if (n_floats != n) return pt_fail(PT_EINVAL, "pt_debug_denoiser_set_activation: layer %d holds %zu floats, not %zu", layer, n, n_floats);
   PT_HIP(hipDeviceSynchronize());
   return d->precision == PT_DENOISE_F16 ? copy_in<_Float16>(d, a, h_in, n) : copy_in<float>(d, a, h_in, n);
+}
+
+int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats) {
+  return pt_debug_denoiser_set_activation_frames(d, layer, 1, h_in, n_floats);
 }
 
 int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len) {
@@ -1174,12 +1194,39 @@ int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info
   return PT_OK;
 }
 
-int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
+int pt_debug_denoiser_run_conv_frames(pt_denoiser* d, int conv, float* d_out, int frames, int ld, size_t frame_stride) {
   if (!d || conv < 0 || conv >= (int)d->convs.size()) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: bad arguments");
-  const Conv& c = d->convs[conv];
-  if (c.out0 < 0 && !d_rgb) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: the rgb head needs an output buffer");
+  int rc = check_group(d, frames, "pt_debug_denoiser_run_conv");
+  if (rc != PT_OK) return rc;
+  const Conv& c = plan_for(d, frames)[conv];
+  if (c.out0 < 0) {  // the head writes d_out + f * frame_stride + pixel * ld + (0 .. 2)
+    if (!d_out) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: the rgb head needs an output buffer");
+    const size_t pixels = (size_t)d->width * d->height;
+    if (ld < 3) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: ld %d < 3", ld);
+    if (frame_stride < pixels * (size_t)ld)
+      return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: frame_stride %zu < width x height x ld = %zu", frame_stride, pixels * (size_t)ld);
+  }
   int launches = 0;
-  const int rc = launch_conv(d, c, d_rgb, 3, 0, 1, nullptr, &launches);
+  rc = launch_conv(d, c, d_out, ld, frame_stride, frames, nullptr, &launches);
+  if (rc != PT_OK) return rc;
+  PT_HIP(hipDeviceSynchronize());
+  return PT_OK;
+}
+
+int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb) {
+  if (!d) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_conv: bad arguments");
+  return pt_debug_denoiser_run_conv_frames(d, conv, d_rgb, 1, 3, (size_t)d->width * d->height * 3);
+}
+
+int pt_debug_denoiser_run_pre(pt_denoiser* d, float* d_frames, int frames, size_t frame_stride, int inplace) {
+  if (!d || !d_frames) return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_pre: null denoiser or frames");
+  const int rc0 = check_group(d, frames, "pt_debug_denoiser_run_pre");
+  if (rc0 != PT_OK) return rc0;
+  const uint32_t pixels = (uint32_t)d->width * (uint32_t)d->height;
+  if (frame_stride < (size_t)pixels * 14)
+    return pt_fail(PT_EINVAL, "pt_debug_denoiser_run_pre: frame_stride %zu < width x height x 14 = %zu", frame_stride, (size_t)pixels * 14);
+  const int rc = d->precision == PT_DENOISE_F16 ? launch_pre<_Float16>(d, d_frames, frame_stride, pixels, frames, inplace ? 1 : 0, nullptr)
+                                                : launch_pre<float>(d, d_frames, frame_stride, pixels, frames, inplace ? 1 : 0, nullptr);
   if (rc != PT_OK) return rc;
   PT_HIP(hipDeviceSynchronize());
   return PT_OK;

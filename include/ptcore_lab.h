@@ -111,12 +111,27 @@ int pt_debug_denoiser_layer_info(pt_denoiser* d, int layer, int* n_layers, int s
  * single enqueue, or the first frame of the last group). */
 int pt_debug_denoiser_activation(pt_denoiser* d, int layer, float* h_out, size_t n_floats);
 int pt_debug_denoiser_set_activation(pt_denoiser* d, int layer, const float* h_in, size_t n_floats);
+/* The same for the first `frames` frames of the layer, [frames][rows][cols][channels] from the layer's offset (contiguous
+ * whatever max_frames the workspace was laid out for).  frames outside 1 .. max_frames: PT_EINVAL. */
+int pt_debug_denoiser_activation_frames(pt_denoiser* d, int layer, int frames, float* h_out, size_t n_floats);
+int pt_debug_denoiser_set_activation_frames(pt_denoiser* d, int layer, int frames, const float* h_in, size_t n_floats);
 /* Convolution `conv` of the forward pass (execution order): info = {input layer, output layer (-1: the frame / rgb
  * buffer), second output layer, residual layer, upsampled layer, kernel size, stride, columns N, epilogue kind (0 affine,
  * 1 lateral upsample-add, 2 rgb head), split-K slices, tile rows, tile columns}. */
 int pt_debug_denoiser_conv_info(pt_denoiser* d, int conv, int* n_convs, int info[12], char* name, size_t name_len);
 /* Runs convolution `conv` alone on the workspace as it stands (synchronous); the rgb head writes [rows][cols][3] to d_rgb. */
 int pt_debug_denoiser_run_conv(pt_denoiser* d, int conv, float* d_rgb);
+/* Convolution `conv` of the plan of a group of `frames` frames, alone, on the first `frames` frames of the workspace as it
+ * stands (synchronous; frames = 1 is the call above).  The rgb head writes channel n of pixel p of frame f to
+ * d_out[f * frame_stride + p * ld + n]; every other convolution ignores d_out, ld and frame_stride.  Refused with PT_EINVAL,
+ * nothing launched: frames outside 1 .. max_frames; the head without d_out, with ld < 3 or with frame_stride < width x
+ * height x ld. */
+int pt_debug_denoiser_run_conv_frames(pt_denoiser* d, int conv, float* d_out, int frames, int ld, size_t frame_stride);
+/* The pre-processing of a group alone (the channel maxima, then the divisions and the stored copy "input"), synchronous:
+ * `frames` frames of [rows][cols][14] floats, frame_stride floats apart; inplace != 0 also writes the normalised channels
+ * 9-13 back.  Refused with PT_EINVAL, nothing launched: null d_frames, frames outside 1 .. max_frames, frame_stride <
+ * width x height x 14. */
+int pt_debug_denoiser_run_pre(pt_denoiser* d, float* d_frames, int frames, size_t frame_stride, int inplace);
 /* Memory of the denoiser and of activation buffer `layer`, in bytes: info = {bytes per stored activation element (4, or 2
  * for a PT_DENOISE_F16 denoiser), the layer's offset into the workspace, the layer's size for ONE frame, the whole activation
  * workspace (all max_frames frames), the split-K partials (fp32 in both modes), the device weights}.  The activation and

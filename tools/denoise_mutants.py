@@ -2,7 +2,7 @@
 """Builds deliberately wrong lab libraries of the denoiser, to show that tests/test_denoiser_exact_gpu.py can fail
 (profiles/denoise_exact/README.md).  Each mutant is a one-line textual change of a COPY of csrc/pt_denoise.hip -- the
 committed source and the product build know nothing of it -- linked with the unchanged lab objects into
-cuda-pathtrace_amd/alt/denoise_mutant<n>/libptcore_lab.so (alt/ is not in git).  A mutant changes values only: no address, no
+cuda-pathtrace_amd/alt/denoise_mutant<n>/libptcore_lab.so (alt/ is not in git).  Mutants 1-3 change values only: no address, no
 bound of a load or store; mutant 2 launches FEWER K slices of the same size, over the same buffers.
 
   1  upsample(): the row weight is divided by out_w - 1 instead of out_h - 1 (the row index is unchanged): invisible at any
@@ -12,8 +12,23 @@ bound of a load or store; mutant 2 launches FEWER K slices of the same size, ove
   3  conv_kernel's window origin: iy0 one row higher where a stride-2 layer reads a map of odd height that is not square (the
      loads stay bounds-checked): invisible at any square size.
 
-Usage: tools/denoise_mutants.py [1 2 3]   (cross-compiles for gfx950; no GPU needed).  To run the tests against a mutant, put
-its library in the place of cuda-pathtrace_amd/libptcore_lab.so in a scratch copy of the tree."""
+Mutants 4-8 show that tests/test_denoiser_groups_gpu.py can fail where a group of frames has code of its own
+(profiles/denoise_groups/README.md).  Each only misplaces a read inside the workspace, or re-slices K inside the partial sums the
+workspace was sized for; none leaves an allocation:
+
+  4  half main loop: the window of every row block is read from the frame of row block 0 (iyb[0]): wrong only where a TM = 2
+     tile (256x32, 128x128) holds rows of two frames.
+  5  the same in the float32 main loop.
+  6  set-up: the frame of every row is the frame of the wave's first row (frame_of once from m0); the loads stay bounds-checked
+     inside that frame.
+  7  pre_apply_kernel divides every frame of a group by the maxima of frame 0.
+  8  plan_for(): the K slicing is chosen again for the group's M (fewer, longer slices; never more than the single-frame
+     slicing that pt_denoiser_reserve_frames sized the partial sums for, which is why the change is made here and not in
+     batch_plan() itself).  Integer sums are exact in any order: only real weights see it.
+
+Usage: tools/denoise_mutants.py [1 2 ...]   (cross-compiles for gfx950; no GPU needed).  To run the tests against a mutant, put
+its library in the place of cuda-pathtrace_amd/libptcore_lab.so in a scratch copy of the tree; tests that go through the
+product library see it too when PT_LIB_OVERRIDE names the same file."""
 import os
 import re
 import subprocess
@@ -31,6 +46,18 @@ MUTANTS = {
         "c.splits = c.nchunks / c.chunks_per_split;"),
     3: ("iy0[i] = oy * a.stride - pad;",
         "iy0[i] = oy * a.stride - pad - ((a.stride == 2 && (a.in_h & 1) && a.in_h != a.in_w) ? 1 : 0);"),
+    4: ("v_ = *reinterpret_cast<const half8*>(a.in + ((size_t)(iyb[i] + iy)",
+        "v_ = *reinterpret_cast<const half8*>(a.in + ((size_t)(iyb[0] + iy)"),
+    5: ("reinterpret_cast<const float4*>(a.in + ((size_t)(iyb[i] + iy)",
+        "reinterpret_cast<const float4*>(a.in + ((size_t)(iyb[0] + iy)"),
+    6: ("const int f = frame_of(a, mm), pix = mm - f * a.out_hw;",
+        "const int f = frame_of(a, m0 < a.M ? m0 : 0), pix = mm - f * a.out_hw;"),
+    7: ("const float* fp = part + (size_t)blockIdx.y * nparts * 5;",
+        "const float* fp = part + (size_t)0 * nparts * 5;"),
+    8: ("if (it == d->plans.end()) it = d->plans.emplace(n, batch_plan(d->convs, n, kPlan[d->precision])).first;",
+        "if (it == d->plans.end()) { std::vector<Conv> pl = batch_plan(d->convs, n, kPlan[d->precision]); "
+        "for (Conv& c : pl) { const int cfg_ = c.cfg, npad_ = c.npad; choose_tiles(c, kPlan[d->precision]); c.cfg = cfg_, c.npad = npad_; } "
+        "it = d->plans.emplace(n, pl).first; }"),
 }
 
 
@@ -59,7 +86,8 @@ def main():
                 for s in srcs if s != "pt_denoise.hip"]
         objs = [j.result() for j in jobs]
     source = open(os.path.join(CSRC, "pt_denoise.hip")).read()
-    for n in which:
+
+    def build(n):
         old, new = MUTANTS[n]
         if source.count(old) != 1:
             raise SystemExit(f"mutant {n}: the line to change occurs {source.count(old)} times in pt_denoise.hip, not once")
@@ -72,7 +100,11 @@ def main():
         obj = compile_one(src, os.path.join(out, "pt_denoise.o"), [f'-DPT_BUILD_FINGERPRINT="denoise-mutant{n}"'])
         lib = os.path.join(out, "libptcore_lab.so")
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + [obj, "-ldl", "-lpthread"])
-        print(f"mutant {n}: {lib}")
+        return f"mutant {n}: {lib}"
+
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        for line in pool.map(build, which):
+            print(line)
 
 
 if __name__ == "__main__":
