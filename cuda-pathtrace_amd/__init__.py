@@ -163,6 +163,9 @@ ABI = {
     "pt_filter_destroy": (ctypes.c_int, [_vp]),
     "pt_filter_reserve_frames": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_filter_workspace_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_filter_spatial_opts_default": (None, [_vp]),
+    "pt_filter_spatial_check": (ctypes.c_int, [_vp]),
+    "pt_filter_set_spatial": (ctypes.c_int, [_vp, _vp]),
     "pt_filter_enqueue": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "pt_filter_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _fp]),
     "pt_filter_enqueue_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
@@ -1117,21 +1120,59 @@ class FilterOpts(ctypes.Structure):
                 ("sigma_z", ctypes.c_float), ("max_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
+class FilterSpatialOpts(ctypes.Structure):
+    """pt_filter_spatial_opts (include/ptcore.h)."""
+    _fields_ = [("below", ctypes.c_uint32), ("radius", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+FILTER_SPATIAL_ALL = 0xFFFFFFFF  # PT_FILTER_SPATIAL_ALL: every pixel takes the estimate
+
+
+def _filter_spatial_opts(below, radius, reserved=(0, 0)):
+    if below == "all":
+        below = FILTER_SPATIAL_ALL
+    if not 0 <= int(below) <= FILTER_SPATIAL_ALL:
+        raise ValueError(f"spatial_below {below} outside 0 .. 2^32 - 1")
+    o = FilterSpatialOpts(below=int(below), radius=radius)
+    o.reserved[0], o.reserved[1] = reserved
+    return o
+
+
+def filter_spatial_check(below, radius=2, reserved=(0, 0)):
+    """pt_filter_spatial_check: the host checks of FeatureFilter.set_spatial alone; host only.  Raises PtError for what it refuses."""
+    check(lib.pt_filter_spatial_check(ctypes.byref(_filter_spatial_opts(below, radius, reserved))))
+
+
 class FeatureFilter(_BatchedStage):
     """ctypes view of pt_filter: the weights-free denoiser for width x height frames, a variance-guided edge-avoiding a-trous
     filter on albedo-demodulated colour (DENOISER.md, "Feature-guided filter").  max_frames > 1 reserves the workspace for
     batches of that many frames per group.  samples: the frame's count per pixel; d_counts: a device uint32 [H][W] count image
-    (Progressive.counts' layout) that replaces it."""
+    (Progressive.counts' layout) that replaces it.  spatial_below > 0 (or "all"): the spatial variance estimate for the pixels
+    with fewer samples than that, over a (2 spatial_radius + 1)^2 window (set_spatial)."""
     _destroy, _reserve = "pt_filter_destroy", "pt_filter_reserve_frames"
 
-    def __init__(self, width, height, max_frames=1, iterations=5, sigma_l=4.0, sigma_n=0.35, sigma_a=0.1, sigma_z=1.0):
+    def __init__(self, width, height, max_frames=1, iterations=5, sigma_l=4.0, sigma_n=0.35, sigma_a=0.1, sigma_z=1.0, spatial_below=0,
+                 spatial_radius=2):
         opts = FilterOpts(iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_a=sigma_a, sigma_z=sigma_z, max_frames=max_frames)
+        spatial = _filter_spatial_opts(spatial_below, spatial_radius)
+        if spatial.below != 0:  # (refused here, before a filter exists)
+            check(lib.pt_filter_spatial_check(ctypes.byref(spatial)))
         h = _vp()
         check(lib.pt_filter_create(width, height, ctypes.byref(opts), ctypes.byref(h)))
         self.handle = h.value
         self.width, self.height = width, height
         self.max_frames = max_frames
         self.iterations = iterations
+        if spatial.below != 0:
+            self.set_spatial(spatial_below, spatial_radius)
+
+    def set_spatial(self, below, radius=2):
+        """pt_filter_set_spatial: the spatial variance estimate (DENOISER.md, "Spatial variance estimate") for the pixels with
+        fewer than `below` samples ("all": every pixel; 0 or None: off), window (2 radius + 1)^2.  Holds for later calls."""
+        if below is None:
+            check(lib.pt_filter_set_spatial(self.handle, None))
+        else:
+            check(lib.pt_filter_set_spatial(self.handle, ctypes.byref(_filter_spatial_opts(below, radius))))
 
     def memory(self):
         """{"workspace": bytes of the state and guide images of all max_frames frames, "per_pixel": bytes per pixel and frame}."""
@@ -1181,13 +1222,16 @@ class FeatureFilter(_BatchedStage):
                 b.free()
 
 
-def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **opts):
+def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, spatial_below=None, spatial_radius=2, **opts):
     """Convenience for tests: upload a host [H][W][14] frame, filter it on the GPU, download.  Returns the frame after the
     in-place step, or (frame untouched, rgb [H][W][3]) with out_of_place=True.  counts: a host uint32 [H][W] count image.
+    spatial_below, spatial_radius: FeatureFilter.set_spatial before the run (it holds on a `filt` passed in).
     opts: of the FeatureFilter made here (iterations, sigma_*)."""
     frame = np.ascontiguousarray(frame, dtype=np.float32)
     h, w = frame.shape[:2]
-    ff = filt or FeatureFilter(w, h, **opts)
+    ff = filt or FeatureFilter(w, h, spatial_below=spatial_below or 0, spatial_radius=spatial_radius, **opts)
+    if filt and spatial_below is not None:
+        filt.set_spatial(spatial_below, spatial_radius)
     counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
     with _on_device(frame, h * w * 12 if out_of_place else None, counts, owned=None if filt else ff) as (d_frame, d_rgb, d_counts):
         ff.run(d_frame.ptr, samples, _ptr(d_rgb), _ptr(d_counts))
@@ -1195,13 +1239,15 @@ def filter_frame(frame, samples, out_of_place=False, filt=None, counts=None, **o
         return (f, d_rgb.download(np.float32, (h, w, 3))) if out_of_place else f
 
 
-def filter_frames(frames, samples, out_of_place=False, filt=None, **opts):
+def filter_frames(frames, samples, out_of_place=False, filt=None, spatial_below=None, spatial_radius=2, **opts):
     """The batched twin of filter_frame: host frames [N][H][W][14] through ONE pt_filter_run_frames call (a filter reserved
     for all N frames unless one is given).  Returns the frames after the in-place step, or (frames untouched, rgb
-    [N][H][W][3]) with out_of_place=True."""
+    [N][H][W][3]) with out_of_place=True.  spatial_below, spatial_radius: as filter_frame."""
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     n, h, w = frames.shape[:3]
-    ff = filt or FeatureFilter(w, h, max_frames=n, **opts)
+    ff = filt or FeatureFilter(w, h, max_frames=n, spatial_below=spatial_below or 0, spatial_radius=spatial_radius, **opts)
+    if filt and spatial_below is not None:
+        filt.set_spatial(spatial_below, spatial_radius)
     with _on_device(frames, n * h * w * 12 if out_of_place else None, owned=None if filt else ff) as (d_frames, d_rgb):
         ff.run_frames(d_frames.ptr, n, samples, d_rgb=_ptr(d_rgb))
         f = d_frames.download(np.float32, frames.shape)

@@ -4,8 +4,10 @@
 // No counterpart in the reference.  DENOISER.md, "Feature-guided filter", states the definition; tests/filter_model.py
 // restates it in NumPy.  TOLERANCED code like pt_fast.hip: FMA contraction in the tap loop, hardware exp2 / rcp.
 //
-// Two kernels, one lane per pixel, blockIdx.z = frame of the group:
+// Three kernels, one lane per pixel, blockIdx.z = frame of the group:
 //   prepare  frame -> state {ill.rgb, var} and the guides {n.xyz, z}, {alb.rgb, dz}: three float4 per pixel
+//   spatial  only with pt_filter_set_spatial: var <- fmax(var, spread of the (2R+1)^2 neighbours' luminances on the pixel's
+//            surface) for the pixels with fewer than `below` samples, window from LDS, state A -> state B
 //   atrous   25 taps at a run-time step (TILE 1, 2: at that step from LDS), state ping-pong; the LAST iteration multiplies the albedo back and writes the
 //            caller's frame (or d_rgb), so no iteration ever reads the caller's frame and in-place use is safe.
 // Per tap: three 16-byte loads, one sum of the four stops, ONE exp2.  Per pixel: the reciprocals of the luminance stop and of
@@ -43,6 +45,10 @@ struct Params {
 #pragma clang fp contract(off)
 
 __device__ __forceinline__ float lum(float x, float y, float z) { return 0.2126f * x + 0.7152f * y + 0.0722f * z; }
+
+// s + w x and s + w (d d), every operation rounded: the moments of spatial_kernel
+__device__ __forceinline__ float add_weighted(float s, float w, float x) { return s + w * x; }
+__device__ __forceinline__ float add_weighted_square(float s, float w, float d) { return s + w * (d * d); }
 
 // Set-up.  Rounded operation by operation like the float32 NumPy twin (divisions are IEEE).
 __global__ void __launch_bounds__(BX* BY) prepare_kernel(Params p, const float* __restrict__ frames, const uint32_t* __restrict__ counts,
@@ -170,6 +176,92 @@ __global__ void __launch_bounds__(BX* BY) atrous_kernel(Params p, int step, cons
     dst[base + i] = make_float4(ox, oy, oz, sv / (sw * sw));
   }
 }
+// The spatial variance estimate (DENOISER.md, "Spatial variance estimate"; tests/filter_spatial_model.py), between the set-up and
+// the first iteration: a pixel with fewer than `below` samples takes var <- fmax(var, v), v the weighted variance of L = lum(ill)
+// over the (2R+1)^2 window, weighted by the normal, albedo and depth stops of the iterations (step 1, no luminance stop, no
+// a-trous kernel).  Reads state A and the guides, writes the whole state {ill, new var} to state B: no lane stores into an image
+// another lane loads.  The workgroup stages what the taps need -- {n.xyz, z} and {alb.rgb, L} -- for its pixels and a halo of R,
+// clamped to the frame, as two planes of 16-byte entries: the lanes of a row read consecutive entries, which is conflict-free
+// for ds_read_b128 whatever the row length (a wave's second row is the other half-wave), where one 32-byte entry per pixel would
+// put lanes l and l + 8 of a group on one bank.  R = 3: 2 x 14 x 38 x 16 = 17024 bytes.
+// Contraction: this kernel lies in the file's contract(fast) region, so the exponent e may contract (toleranced: hardware exp2 /
+// rcp, log2(e) folded into the stop factors).  The two moment passes go through add_weighted / add_weighted_square, defined in
+// the contract(off) region above, row by row through the window, and m and v are IEEE quotients: with weights of exactly 0 or 1
+// they are the float32 model's bits.
+template <int R>
+__global__ void __launch_bounds__(BX* BY) spatial_kernel(Params p, uint32_t below, uint32_t samples, const uint32_t* __restrict__ counts,
+                                                         const float4* __restrict__ src, const float4* __restrict__ g0,
+                                                         const float4* __restrict__ g1, float4* __restrict__ dst) {
+  constexpr int TW = BX + 2 * R, TH = BY + 2 * R, D = 2 * R + 1;
+  __shared__ float4 tile[2][TH * TW];
+  const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+  const size_t base = (size_t)blockIdx.z * p.pixels;
+  src += base, g0 += base, g1 += base;
+  const uint32_t W = (uint32_t)p.width;
+  const int x0 = (int)(blockIdx.x * BX) - R, y0 = (int)(blockIdx.y * BY) - R;
+  for (int t = threadIdx.y * BX + threadIdx.x; t < TH * TW; t += BX * BY) {
+    const int gx = min(max(x0 + t % TW, 0), p.width - 1), gy = min(max(y0 + t / TW, 0), p.height - 1);
+    const uint32_t q = (uint32_t)gy * W + (uint32_t)gx;
+    const float4 s = src[q], a = g1[q];
+    tile[0][t] = g0[q], tile[1][t] = make_float4(a.x, a.y, a.z, lum(s.x, s.y, s.z));
+  }
+  __syncthreads();
+  if (x >= p.width || y >= p.height) return;
+  const uint32_t i = (uint32_t)y * W + (uint32_t)x;
+  const float4 sp = src[i];
+  const uint32_t n = counts ? counts[i] : samples;
+  if (n >= below) {  // enough samples: the set-up's state bit for bit
+    dst[base + i] = sp;
+    return;
+  }
+  const float4 *tn = tile[0], *ta = tile[1];
+  const int ti = (threadIdx.y + R) * TW + threadIdx.x + R;  // this pixel in the tile
+  const float4 np = tn[ti], ap = ta[ti];
+  constexpr float LOG2E = 1.4426950408889634f;
+  // depth stop: sigma_z dz d + 1e-3 |z| + 1e-20 for d = sqrt(i^2 + j^2), i^2 + j^2 in {1, 2, 4, 5, 8, 9, 10, 13, 18}
+  constexpr float ROOT[19] = {0.0f, 1.0f, 1.41421356237309505f, 0.0f, 2.0f, 2.23606797749978970f, 0.0f, 0.0f, 2.82842712474619010f, 3.0f,
+                              3.16227766016837933f, 0.0f, 0.0f, 3.60555127546398929f, 0.0f, 0.0f, 0.0f, 0.0f, 4.24264068711928515f};
+  const float zs = p.sz * g1[i].w, zc = 1e-3f * fabsf(np.w) + 1e-20f;
+  float rz[2 * R * R + 1];
+  rz[0] = 0.0f;
+#pragma unroll
+  for (int d2 = 1; d2 <= 2 * R * R; d2++) rz[d2] = ROOT[d2] != 0.0f ? LOG2E * __builtin_amdgcn_rcpf(zs * ROOT[d2] + zc) : 0.0f;
+
+  float w[D * D];
+  float sw = 0.0f, sl = 0.0f;
+#pragma unroll
+  for (int j = -R; j <= R; j++) {
+    const bool rowin = y + j >= 0 && y + j < p.height;
+#pragma unroll
+    for (int k = -R; k <= R; k++) {
+      const bool colin = x + k >= 0 && x + k < p.width;
+      // a tap outside the frame is skipped: it reads the pixel's own row / column instead, one of its own taps, at weight 0
+      const int tq = ti + (rowin ? j : 0) * TW + (colin ? k : 0);
+      const float4 nq = tn[tq], aq = ta[tq];
+      const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
+      const float dax = aq.x - ap.x, day = aq.y - ap.y, daz = aq.z - ap.z;
+      float e = (dnx * dnx + dny * dny + dnz * dnz) * p.cn + (dax * dax + day * day + daz * daz) * p.ca;
+      e += fabsf(nq.w - np.w) * rz[j * j + k * k];
+      const float wq = rowin && colin ? (j == 0 && k == 0 ? 1.0f : __builtin_amdgcn_exp2f(-e)) : 0.0f;
+      w[(j + R) * D + k + R] = wq;
+      sw = add_weighted(sw, wq, 1.0f);
+      sl = add_weighted(sl, wq, aq.w - ap.w);  // relative to the pixel's own L: the same v, and exactly 0 on a flat window
+    }
+  }
+  const float m = sl / sw;  // the mean of L_q - L_p.  IEEE divisions: sw >= 1 (the centre tap)
+  float sv = 0.0f;
+#pragma unroll
+  for (int j = -R; j <= R; j++) {
+    const bool rowin = y + j >= 0 && y + j < p.height;
+#pragma unroll
+    for (int k = -R; k <= R; k++) {
+      const bool colin = x + k >= 0 && x + k < p.width;
+      const int tq = ti + (rowin ? j : 0) * TW + (colin ? k : 0);
+      sv = add_weighted_square(sv, w[(j + R) * D + k + R], (ta[tq].w - ap.w) - m);
+    }
+  }
+  dst[base + i] = make_float4(sp.x, sp.y, sp.z, fmaxf(sp.w, sv / sw));  // fmax: a NaN v leaves var as it was
+}
 }  // namespace ptflt
 
 using namespace ptflt;
@@ -179,6 +271,7 @@ struct pt_filter {
   pt_filter_opts opts{};
   int max_frames = 1;
   bool tiled = true;  // steps 1 and 2 through the LDS tile (the lab library's pt_debug_filter_tiled switches it off for the A/B)
+  pt_filter_spatial_opts spatial{};  // below 0: off (pt_filter_set_spatial)
   float4* d_ws = nullptr;  // [4][max_frames x pixels]: state A, state B, guide 0, guide 1
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -200,15 +293,25 @@ static Params make_params(const pt_filter* f, size_t frame_stride, size_t out_st
   return p;
 }
 
-// One group of g <= max_frames frames: prepare, then the iterations (steps[0 .. n_steps)), the last one fused.  With `state`
+// One group of g <= max_frames frames: prepare, the spatial variance estimate if it is on and a pixel can qualify (a count image,
+// or the uniform `samples` below the threshold), then the iterations (steps[0 .. n_steps)), the last one fused.  With `state`
 // (the lab library's pt_debug_filter_state) no iteration is fused, nothing is written to `out`, and *state receives the
 // workspace image that holds the state after the last iteration.
-static int launch_group(const pt_filter* f, const Params& p, int g, const float* frames, float* out, const uint32_t* counts,
+static int launch_group(const pt_filter* f, const Params& p, int g, const float* frames, float* out, const uint32_t* counts, int samples,
                         const int* steps, int n_steps, hipStream_t s, const float4** state = nullptr) {
   const size_t n = (size_t)f->max_frames * p.pixels;
   float4 *a = f->d_ws, *b = f->d_ws + n, *g0 = f->d_ws + 2 * n, *g1 = f->d_ws + 3 * n;
   const dim3 block(BX, BY), grid((unsigned)((p.width + BX - 1) / BX), (unsigned)((p.height + BY - 1) / BY), (unsigned)g);
   hipLaunchKernelGGL(prepare_kernel, grid, block, 0, s, p, frames, counts, a, g0, g1);
+  const uint32_t below = f->spatial.below;
+  if (below > 0 && (counts || (uint32_t)samples < below)) {
+    using Spatial = void (*)(Params, uint32_t, uint32_t, const uint32_t*, const float4*, const float4*, const float4*, float4*);
+    static const Spatial spatial[3] = {spatial_kernel<1>, spatial_kernel<2>, spatial_kernel<3>};
+    hipLaunchKernelGGL(spatial[f->spatial.radius - 1], grid, block, 0, s, p, below, (uint32_t)samples, counts, (const float4*)a,
+                       (const float4*)g0, (const float4*)g1, b);
+    float4* t = a;
+    a = b, b = t;
+  }
   using Kernel = void (*)(Params, int, const float4*, const float4*, const float4*, float4*, float*);
   static const Kernel kernels[2][3] = {{atrous_kernel<false, 0>, atrous_kernel<false, 1>, atrous_kernel<false, 2>},
                                        {atrous_kernel<true, 0>, atrous_kernel<true, 1>, atrous_kernel<true, 2>}};
@@ -254,7 +357,7 @@ static int enqueue_frames(const char* who, pt_filter* f, int n_frames, float* d_
     const int g = n_frames - f0 < f->max_frames ? n_frames - f0 : f->max_frames;
     float* frames = d_frames + (size_t)f0 * frame_stride_floats;
     float* out = d_rgb ? d_rgb + (size_t)f0 * rgb_stride_floats : frames;
-    if ((rc = launch_group(f, p, g, frames, out, d_counts, steps, f->opts.iterations, s)) != PT_OK) return rc;
+    if ((rc = launch_group(f, p, g, frames, out, d_counts, samples, steps, f->opts.iterations, s)) != PT_OK) return rc;
   }
   return PT_OK;
 }
@@ -267,6 +370,35 @@ void pt_filter_opts_default(pt_filter_opts* opts) {
   opts->iterations = 5;
   opts->sigma_l = 4.0f, opts->sigma_n = 0.35f, opts->sigma_a = 0.1f, opts->sigma_z = 1.0f;
   opts->max_frames = 1;
+}
+
+void pt_filter_spatial_opts_default(pt_filter_spatial_opts* opts) {
+  if (!opts) return;
+  *opts = pt_filter_spatial_opts{};
+  opts->radius = PT_FILTER_SPATIAL_DEFAULT_RADIUS;
+}
+
+static int spatial_check(const char* who, const pt_filter_spatial_opts* opts) {
+  if (!opts) return pt_fail(PT_EINVAL, "%s: null opts", who);
+  if (opts->radius < 1 || opts->radius > 3) return pt_fail(PT_EINVAL, "%s: radius %d outside 1 .. 3", who, opts->radius);
+  for (int i = 0; i < 2; i++)
+    if (opts->reserved[i] != 0) return pt_fail(PT_EINVAL, "%s: reserved[%d] = %d must be 0", who, i, opts->reserved[i]);
+  return PT_OK;
+}
+
+int pt_filter_spatial_check(const pt_filter_spatial_opts* opts) { return spatial_check("pt_filter_spatial_check", opts); }
+
+int pt_filter_set_spatial(pt_filter* f, const pt_filter_spatial_opts* opts) {
+  pt_filter_spatial_opts o;
+  pt_filter_spatial_opts_default(&o);  // NULL: off
+  if (opts) {  // (the options first: a bad one is refused whatever the filter)
+    const int rc = spatial_check("pt_filter_set_spatial", opts);
+    if (rc != PT_OK) return rc;
+    o = *opts;
+  }
+  if (!f) return pt_fail(PT_EINVAL, "pt_filter_set_spatial: null filter");
+  f->spatial = o;
+  return PT_OK;
 }
 
 int pt_filter_destroy(pt_filter* f) {
@@ -369,7 +501,7 @@ int pt_debug_filter_step(pt_filter* f, float* d_frame, float* d_rgb, int samples
   if (rc != PT_OK) return rc;
   if (step < 1 || step > 4096) return pt_fail(PT_EINVAL, "pt_debug_filter_step: step %d outside 1 .. 4096", step);
   const Params p = make_params(f, pixels * 14, d_rgb ? pixels * 3 : pixels * 14, d_rgb ? 3 : 14, samples);
-  if ((rc = launch_group(f, p, 1, d_frame, d_rgb ? d_rgb : d_frame, d_counts, &step, 1, nullptr)) != PT_OK) return rc;
+  if ((rc = launch_group(f, p, 1, d_frame, d_rgb ? d_rgb : d_frame, d_counts, samples, &step, 1, nullptr)) != PT_OK) return rc;
   PT_HIP(hipDeviceSynchronize());
   return PT_OK;
 }
@@ -388,7 +520,7 @@ int pt_debug_filter_state(pt_filter* f, const float* d_frame, int samples, const
     return pt_fail(PT_EINVAL, "%s: null %s", who, !d_state ? "d_state" : !d_guide0 ? "d_guide0" : "d_guide1");
   const Params p = make_params(f, pixels * 14, pixels * 14, 14, samples);
   const float4* state = nullptr;
-  if ((rc = launch_group(f, p, 1, d_frame, nullptr, d_counts, steps, n_steps, nullptr, &state)) != PT_OK) return rc;
+  if ((rc = launch_group(f, p, 1, d_frame, nullptr, d_counts, samples, steps, n_steps, nullptr, &state)) != PT_OK) return rc;
   const size_t n = (size_t)f->max_frames * p.pixels, bytes = pixels * sizeof(float4);
   PT_HIP(hipMemcpy(d_state, state, bytes, hipMemcpyDeviceToDevice));
   PT_HIP(hipMemcpy(d_guide0, f->d_ws + 2 * n, bytes, hipMemcpyDeviceToDevice));

@@ -28,6 +28,16 @@ class FeatureFilter {
     gpuErrchk(pt_filter_create(width, height, &opts, &filter));
   }
   ~FeatureFilter() { (void)pt_filter_destroy(filter); }
+  // the spatial variance estimate (pt_filter_set_spatial): before the first iteration every pixel with fewer than `below`
+  // samples takes the larger of its own variance and the spread of its neighbours' luminances on the same surface, over the
+  // (2 radius + 1)^2 window.  below 0 switches it off, PT_FILTER_SPATIAL_ALL takes every pixel; it holds for every later
+  // call.  A bad value exits like every error.
+  void SetSpatial(unsigned int below, int radius = PT_FILTER_SPATIAL_DEFAULT_RADIUS) {
+    pt_filter_spatial_opts o;
+    pt_filter_spatial_opts_default(&o);
+    o.below = below, o.radius = radius;
+    gpuErrchk(pt_filter_set_spatial(filter, &o));
+  }
 
   // in place on the device frame rendered with `samples` samples per pixel (d_counts != NULL: the per-pixel counts of an
   // adaptive session instead); returns device-event milliseconds

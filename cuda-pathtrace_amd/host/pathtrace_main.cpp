@@ -21,6 +21,8 @@
 // after Render() and before --filter or -d; the filter then takes the accumulator's per-pixel counts),
 // --velocities FILE (with --frames / --poses: the spheres listed move at a constant velocity, the scene is uploaded before every
 // frame's Render(), and --temporal accumulates through pt_temporal_run_scene, which follows them),
+// --filter-spatial-below N (with --filter: the filter's spatial variance estimate, pt_filter_set_spatial, for pixels with fewer
+// than N samples),
 // --temporal-fast-cap X (with --temporal: the accumulator's responsive history, pt_temporal_set_antilag, against lagging light),
 // --tonemap CURVE (ToneMapper / pt_tonemap_*: every frame of the headless loop and every progressive pass goes through the
 // session after --temporal, --filter and -d, so that --tonemap-adapt acts as eye adaptation; the last frame's sRGB picture is
@@ -90,6 +92,9 @@ static void usage() {
                "  --filter                      denoise without weights: variance-guided a-trous filter on every frame\n"
                "  --filter-iterations arg       with --filter: a-trous iterations 1..8 (default 5)\n"
                "  --filter-sigma arg            with --filter: the four stops l,n,a,z (default 4,0.35,0.1,1)\n"
+               "  --filter-spatial-below arg    with --filter: pixels with fewer than arg samples (a number >= 1, or all) estimate their\n"
+               "                                variance from their neighbours on the same surface (default: off)\n"
+               "  --filter-spatial-radius arg   with --filter-spatial-below: the window is (2 arg + 1)^2 pixels, 1 .. 3 (default 2)\n"
                "  --temporal                    with --frames / --poses: reproject and accumulate every frame over the last ones\n"
                "  --temporal-cap arg            with --temporal: cap of the accumulated history in samples, >= 1 (default 256)\n"
                "  --temporal-fast-cap arg       with --temporal: responsive history: keep a second history of at most arg samples\n"
@@ -137,6 +142,11 @@ int main(int argc, const char** argv) {
   bool filtering = false, filterIterationsGiven = false, filterSigmaGiven = false;
   int filterIterations = 5;
   std::string filterSigma;
+  // --filter-spatial-below N [--filter-spatial-radius R]: the filter's spatial variance estimate (pt_filter_set_spatial)
+  bool spatialBelowGiven = false, spatialRadiusGiven = false;
+  std::string spatialBelow;
+  pt_filter_spatial_opts spatialOpts;
+  pt_filter_spatial_opts_default(&spatialOpts);
   // --temporal: the temporal accumulator (pt_temporal_*) in place after every Render() of the frame loop
   bool temporal = false, temporalCapGiven = false;
   double temporalCap = 256.0;
@@ -190,6 +200,8 @@ int main(int argc, const char** argv) {
     else if (a == "--filter") filtering = true;
     else if (a == "--filter-iterations") { filterIterations = atoi(value("--filter-iterations")); filterIterationsGiven = true; }
     else if (a == "--filter-sigma") { filterSigma = value("--filter-sigma"); filterSigmaGiven = true; }
+    else if (a == "--filter-spatial-below") { spatialBelow = value("--filter-spatial-below"); spatialBelowGiven = true; }
+    else if (a == "--filter-spatial-radius") { spatialOpts.radius = atoi(value("--filter-spatial-radius")); spatialRadiusGiven = true; }
     else if (a == "--temporal") temporal = true;
     else if (a == "--temporal-cap") { temporalCap = atof(value("--temporal-cap")); temporalCapGiven = true; }
     else if (a == "--temporal-fast-cap") { antilagOpts.fast_cap = (float)atof(value("--temporal-fast-cap")); fastCapGiven = true; }
@@ -265,6 +277,14 @@ int main(int argc, const char** argv) {
               << " needs --filter: it sets an option of the feature-guided filter" << std::endl;
     return 1;
   }
+  if (spatialBelowGiven && !filtering) {
+    std::cerr << "ERROR: --filter-spatial-below needs --filter: it is the filter's variance estimate for pixels with few samples" << std::endl;
+    return 1;
+  }
+  if (spatialRadiusGiven && !spatialBelowGiven) {
+    std::cerr << "ERROR: --filter-spatial-radius needs --filter-spatial-below: it sizes the window of the variance estimate" << std::endl;
+    return 1;
+  }
   if (filtering) {
     if (denoising) {
       std::cerr << "ERROR: --filter cannot be combined with -d: choose the filter or the network" << std::endl;
@@ -291,6 +311,25 @@ int main(int argc, const char** argv) {
         return 1;
       }
       filterOpts.sigma_l = v[0], filterOpts.sigma_n = v[1], filterOpts.sigma_a = v[2], filterOpts.sigma_z = v[3];
+    }
+    if (spatialBelowGiven) {  // the library's own host checks, before any device is touched
+      if (spatialBelow == "all") {
+        spatialOpts.below = PT_FILTER_SPATIAL_ALL;
+      } else {
+        char* end = NULL;
+        const unsigned long long v = strtoull(spatialBelow.c_str(), &end, 10);
+        const bool digits = !spatialBelow.empty() && spatialBelow.find_first_not_of("0123456789") == std::string::npos;
+        if (!digits || *end != '\0' || v < 1 || v > 0xFFFFFFFFull) {
+          std::cerr << "ERROR: --filter-spatial-below '" << spatialBelow << "': a sample count 1 .. 4294967295, or all (leave the option out for off)"
+                    << std::endl;
+          return 1;
+        }
+        spatialOpts.below = (unsigned int)v;
+      }
+      if (pt_filter_spatial_check(&spatialOpts) != PT_OK) {
+        std::cerr << "ERROR: --filter-spatial-radius: " << pt_last_error() << std::endl;
+        return 1;
+      }
     }
   }
   pt_temporal_opts temporalOpts;
@@ -508,6 +547,7 @@ int main(int argc, const char** argv) {
       denoising ? new DenoiseNet(width, height, denoiseWeights, 1, denoisePrecision == "half" ? PT_DENOISE_F16 : PT_DENOISE_F32) : NULL;
   // --filter: likewise on the first device, after the gather
   FeatureFilter* filter = filtering ? new FeatureFilter(width, height, filterOpts) : NULL;
+  if (filter && spatialBelowGiven) filter->SetSpatial(spatialOpts.below, spatialOpts.radius);
   // --temporal: likewise; with --filter its per-pixel counts replace the filter's uniform count
   TemporalAccumulator* accumulator = temporal ? new TemporalAccumulator(width, height, temporalOpts) : NULL;
   if (accumulator && fastCapGiven) accumulator->SetAntilag(antilagOpts.fast_cap, antilagOpts.clamp_sigma, antilagOpts.clamp_radius);

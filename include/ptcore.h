@@ -418,6 +418,39 @@ int pt_filter_enqueue_frames(pt_filter* f, int n_frames, float* d_frames, size_t
 int pt_filter_run_frames(pt_filter* f, int n_frames, float* d_frames, size_t frame_stride_floats, float* d_rgb,
                          size_t rgb_stride_floats, int samples, float* ms_out);
 
+/* -- spatial variance estimate: the variance of a pixel with few samples, from its neighbours (DENOISER.md, "Spatial variance
+ * estimate") --
+ * At 1 .. 4 samples the pixel's own variance above says little: most paths of a closed scene return 0 until one finds the
+ * light, so many pixels report a variance of exactly 0 and stop the luminance stop dead, and n = 1 has no variance at all.
+ * With the mode on, ONE more launch between the set-up and the first iteration gives every pixel p whose integer count n_p (its
+ * entry of d_counts, else `samples`) is below `below` the spread of its neighbours' means on the same surface, which estimates
+ * the same quantity var holds (SVGF does this where a pixel's history is short).  With L = lum(ill), over the taps q = p + (i, j),
+ * |i|, |j| <= radius, that lie inside the frame (restated in tests/filter_spatial_model.py):
+ *     e = |n_q - n_p|^2 / sigma_n^2 + |alb_q - alb_p|^2 / sigma_a^2 + |z_q - z_p| / (sigma_z dz_p sqrt(i^2 + j^2) + 1e-3 |z_p| + 1e-20)
+ *     w = exp(-e) (the centre: 1);   m = sum(w L_q) / sum(w);   v = sum(w (L_q - m)^2) / sum(w);   var_p = fmax(var_p, v)
+ * The sigmas are the filter's own; there is no luminance term.  v is taken in two passes, centred, on L_q - L_p (the same v; a
+ * window of equal luminances gives exactly 0), and fmax leaves var_p alone when v is NaN.  A pixel with n_p >= below keeps its var bit for bit, and the iterations are unchanged.  TOLERANCED code like the
+ * iterations in e and w; the two moment sums are rounded operation by operation, row by row through the window.
+ * Off (the default), every call keeps its bits and its launches; on, a call whose pixels cannot qualify (no count image and
+ * samples >= below) launches nothing extra either.  The workspace does not grow.  Limits: v is biased low by about
+ * sum(w^2) / sum(w)^2 (no Bessel correction), and a window that straddles a shadow edge on one surface reads it as noise. */
+typedef struct pt_filter_spatial_opts {
+  uint32_t below;      /* pixels with fewer samples than this take the estimate; 0 = off (default), PT_FILTER_SPATIAL_ALL = all */
+  int32_t radius;      /* R: the window is (2R+1)^2, 1 .. 3 (default 2)                                                      */
+  int32_t reserved[2]; /* must be 0                                                                                         */
+} pt_filter_spatial_opts;
+#define PT_FILTER_SPATIAL_ALL 0xFFFFFFFFu
+#define PT_FILTER_SPATIAL_DEFAULT_RADIUS 2
+void pt_filter_spatial_opts_default(pt_filter_spatial_opts* opts); /* below 0 (off), radius 2 */
+/* The host checks of pt_filter_set_spatial alone (no device, no filter): PT_EINVAL naming the field for a null opts, a radius
+ * outside 1 .. 3 (whatever `below` is) and a non-zero reserved word. */
+int pt_filter_spatial_check(const pt_filter_spatial_opts* opts);
+/* Switches the estimate of a filter on (below > 0) or off (below == 0, or opts == NULL).  Every value is checked before anything
+ * else (pt_filter_spatial_check); a refused call leaves the filter as it was.  Touches no device.  It holds for every later
+ * pt_filter_enqueue / _run / _enqueue_frames / _run_frames of the filter; a batch has no count image, so the uniform `samples`
+ * decides for all its frames, and it stays the loop of single calls bit for bit. */
+int pt_filter_set_spatial(pt_filter* f, const pt_filter_spatial_opts* opts);
+
 /* ---- temporal accumulation: reproject and blend the frames of a fly-through ------------------ */
 /* The temporal stage of SVGF in front of the filter above; no counterpart in the reference.  A session belongs to one frame
  * size and carries, from call to call, what the earlier frames accumulated: two history images used ping-pong, each three

@@ -154,7 +154,8 @@ int pt_debug_filter_tiled(pt_filter* f, int on);
 /* The set-up and n_steps (0 .. 8) UNFUSED iterations at steps[k] (1 .. 4096 each), through the tile or direct loads as
  * pt_debug_filter_tiled says; then the current state {ill.rgb, var} and the guides {n.xyz, z}, {alb.rgb, dz}, each
  * [H][W][4] float32, are copied to d_state, d_guide0 and d_guide1.  The frame is only read.  d_frame, samples and d_counts as
- * pt_filter_enqueue.  Synchronous. */
+ * pt_filter_enqueue.  Synchronous.  Both this call and pt_debug_filter_step honour pt_filter_set_spatial: the estimate runs
+ * after the set-up, so with n_steps = 0 d_state holds the new var. */
 int pt_debug_filter_state(pt_filter* f, const float* d_frame, int samples, const uint32_t* d_counts, const int* steps, int n_steps,
                           float* d_state, float* d_guide0, float* d_guide1);
 
