@@ -72,3 +72,11 @@ def errors(a, ref):
     """(max abs, rms) of a - ref."""
     e = np.asarray(a, dtype=np.float64) - np.asarray(ref, dtype=np.float64)
     return float(np.abs(e).max()), float(np.sqrt(np.mean(e * e)))
+
+
+def limits(model, ref):
+    """(max abs, rms) a GPU result may differ from the float64 `ref` by, from the model's own error Em = model - ref:
+    max |E| <= 3 max |Em| + 1e-4 and rms(E) <= 2 rms(Em) + 1e-5.  Kernel and model are two draws of the same rounding process
+    (fp32 instead of float64 sums flip individual fp16 roundings); a bf16-sized error (3 x and more in rms) fails."""
+    m_max, m_rms = errors(model, ref)
+    return 3 * m_max + 1e-4, 2 * m_rms + 1e-5

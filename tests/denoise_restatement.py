@@ -1,5 +1,7 @@
 """A float64 torch (CPU) restatement of the reference's denoising step, written from the specification in DENOISER.md
-(pre-processing of train.py:test, DenoiseCNN's eval-mode forward, modify_tensor), not from the reference's code.
+(pre-processing of train.py:test, DenoiseCNN's eval-mode forward, modify_tensor), not from the reference's code -- and held
+to what the reference's code computes, tensor by tensor, by tests/test_denoiser_reference_host.py (recordings of
+oracle/ref_denoise/record.py under tests/golden/).
 Test infrastructure: tests/test_denoiser_*.py and tools/denoise_time.py (its fp32 comparison point)."""
 import numpy as np
 import torch
@@ -41,31 +43,46 @@ def bn(x, sd, name):
     return (x - m) / torch.sqrt(v + BN_EPS) * g + b
 
 
-def resblock(x, sd, b):
-    """ResBlock: r = BN_res(ReLU(conv_s2_res(x))), y = BN2(ReLU(conv_s1(BN1(ReLU(conv_s2(x)))))), out = y + r."""
+def _tap(tap, name, t):
+    if tap is not None:
+        tap(name, t)
+    return t
+
+
+def resblock(x, sd, b, tap=None):
+    """ResBlock: r = BN_res(ReLU(conv_s2_res(x))), y = BN2(ReLU(conv_s1(BN1(ReLU(conv_s2(x)))))), out = y + r.  tap(name, tensor)
+    sees every module's output under the reference's module name."""
     p = f"block{b}."
-    r = bn(F.relu(conv(x, sd, p + "res_conv", 2, 1)), sd, p + "res_bn")
-    y = bn(F.relu(conv(x, sd, p + "conv1", 2, 1)), sd, p + "bn1")
-    y = bn(F.relu(conv(y, sd, p + "conv2", 1, 1)), sd, p + "bn2")
-    return y + r
+    r = _tap(tap, p + "res_conv", conv(x, sd, p + "res_conv", 2, 1))
+    r = _tap(tap, p + "res_bn", bn(F.relu(r), sd, p + "res_bn"))
+    y = _tap(tap, p + "conv1", conv(x, sd, p + "conv1", 2, 1))
+    y = _tap(tap, p + "bn1", bn(F.relu(y), sd, p + "bn1"))
+    y = _tap(tap, p + "conv2", conv(y, sd, p + "conv2", 1, 1))
+    y = _tap(tap, p + "bn2", bn(F.relu(y), sd, p + "bn2"))
+    return _tap(tap, f"block{b}", y + r)
 
 
-def upsample(x, size):
-    """F.upsample(mode='bilinear') of torch 0.2/0.3: align-corners semantics."""
-    return F.interpolate(x, size=tuple(size), mode="bilinear", align_corners=True)
+def upsample(x, size, align_corners=True):
+    """F.upsample(mode='bilinear') of torch 0.2/0.3: align-corners semantics (align_corners=False: what the same call means
+    to a torch of today, tests/test_denoiser_reference_host.py)."""
+    return F.interpolate(x, size=tuple(size), mode="bilinear", align_corners=align_corners)
 
 
-def forward(x, sd):
-    """The network on the pre-processed NCHW input x; returns clamp(rgb_conv(rep) * (0.00316 + x[:, 6:9]), 0, 1)."""
+def forward(x, sd, align_corners=True, tap=None):
+    """The network on the pre-processed NCHW input x; returns clamp(rgb_conv(rep) * (0.00316 + x[:, 6:9]), 0, 1).
+    tap(name, tensor): every module's output (convolutions before their ReLU), each upsample + lateral sum as
+    "upsample_add_k", the head times the albedo term as "preclamp" and the result as "final"."""
     raw = [x]
     for b in range(1, 7):
-        raw.append(resblock(raw[-1], sd, b))
-    rep = F.relu(conv(raw[6], sd, "lat_6", 1, 0))
+        raw.append(resblock(raw[-1], sd, b, tap))
+    rep = F.relu(_tap(tap, "lat_6", conv(raw[6], sd, "lat_6", 1, 0)))
     for k in range(5, -1, -1):
-        rep = F.relu(conv(rep, sd, f"backwards_{k + 1}{k}", 2, 1))
-        rep = upsample(rep, raw[k].shape[2:]) + F.relu(conv(raw[k], sd, f"lat_{k}", 1, 0))
-    out = conv(rep, sd, "rgb_conv", 1, 1)
-    return torch.clamp(out * (KEPS + x[:, 6:9]), 0, 1)
+        rep = F.relu(_tap(tap, f"backwards_{k + 1}{k}", conv(rep, sd, f"backwards_{k + 1}{k}", 2, 1)))
+        lat = F.relu(_tap(tap, f"lat_{k}", conv(raw[k], sd, f"lat_{k}", 1, 0)))
+        rep = _tap(tap, f"upsample_add_{k}", upsample(rep, raw[k].shape[2:], align_corners) + lat)
+    out = _tap(tap, "rgb_conv", conv(rep, sd, "rgb_conv", 1, 1))
+    pre = _tap(tap, "preclamp", out * (KEPS + x[:, 6:9]))
+    return _tap(tap, "final", torch.clamp(pre, 0, 1))
 
 
 def denoise(frame, sd, dtype=torch.float64):

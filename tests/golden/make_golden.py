@@ -13,7 +13,13 @@ PROVENANCE -- read before trusting these files:
     (a) the oracle is regression-pinned and (b) the GPU tests can compare the HIP kernel with
     stored vectors as well as with the live oracle.  They are oracle-generated, NOT
     reference-generated; parity stays "unpinned" in the sense of DESIGN.md.
-Run: python tests/golden/make_golden.py   (needs oracle/libpt_oracle.so; no GPU)."""
+  * ref_denoise_*.npz ARE reference-generated: what the reference's own denoiser code (denoise_cnn/model.py, train.py:test,
+    load_data.py:get_score, executed in place on the CPU) computed on synthetic inputs, recorded by
+    oracle/ref_denoise/record.py into oracle/_ref/denoise/ (build() runs it where the reference tree is mounted) and copied
+    from there by `python tests/golden/make_golden.py ref_denoise`.  Data only; tests/test_denoiser_reference_host.py records
+    again and demands equality wherever the reference is mounted.
+Run: python tests/golden/make_golden.py   (needs oracle/libpt_oracle.so; no GPU).
+     python tests/golden/make_golden.py ref_denoise   (only copies the recordings of the reference's denoiser)."""
 import json
 import math
 import os
@@ -28,7 +34,24 @@ import __graft_entry__ as ge  # noqa: E402
 
 
 
+def copy_ref_denoise():
+    """oracle/_ref/denoise/ref_denoise_*.npz -> tests/golden/ (the old ones are removed first: the recipe numbers its files)."""
+    import glob
+    import shutil
+
+    src = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "denoise", "ref_denoise_*.npz")))
+    if not src:
+        sys.exit("oracle/_ref/denoise/ is empty: run oracle/ref_denoise/record.py (needs the reference tree) first")
+    for old in glob.glob(os.path.join(HERE, "ref_denoise_*.npz")):
+        os.remove(old)
+    for path in src:
+        shutil.copy(path, HERE)
+    print("ref_denoise:", len(src), "files,", sum(os.path.getsize(p) for p in src), "bytes")
+
+
 def main():
+    if sys.argv[1:] == ["ref_denoise"]:
+        return copy_ref_denoise()
     O = ge.load_oracle()
     O.build()
     _generate(O)
