@@ -61,7 +61,14 @@ class RendererOpts(ctypes.Structure):
 
 
 VARIANT_FAST = 100
+VARIANT_MATERIALS = 101  # PT_VARIANT_MATERIALS: what kernel_info reports while a material table is set
 LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
+# sphere materials (pt_material, include/ptcore.h; EXACTNESS.md A.22)
+MATERIAL_DIFFUSE, MATERIAL_MIRROR, MATERIAL_GLOSSY, MATERIAL_GLASS = 0, 1, 2, 3
+MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("param", "<f4")])
+MATERIALS_MAX_SPHERES = 64
+# smallpt's Cornell box: sphere 6 a mirror ball, sphere 7 a glass ball, everything else diffuse
+SMALLPT_MATERIALS = [(MATERIAL_DIFFUSE, 0.0)] * 6 + [(MATERIAL_MIRROR, 0.0), (MATERIAL_GLASS, 1.5), (MATERIAL_DIFFUSE, 0.0)]
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER_COPY = 0, 1, 2
 
 
@@ -132,6 +139,8 @@ ABI = {
     "pt_renderer_get_rng_state": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "pt_renderer_set_rng_state": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "pt_renderer_kernel_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(KernelInfo)]),
+    "pt_material_check": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_renderer_set_materials": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "pt_mgpu_opts_default": (None, [ctypes.POINTER(MgpuOpts)]),
     "pt_mgpu_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(RendererOpts), ctypes.POINTER(MgpuOpts), ctypes.POINTER(_vp)]),
@@ -655,6 +664,37 @@ def upload_scene(spheres):
     return DeviceBuffer(max(spheres.nbytes, 4)).upload(spheres), len(spheres)
 
 
+class Material(tuple):
+    """One sphere's material: Material(kind, param=0.0), a (kind, param) pair like the entries of `materials=[...]`."""
+
+    def __new__(cls, kind, param=0.0):
+        return super().__new__(cls, (int(kind), float(param)))
+
+    kind = property(lambda self: self[0])
+    param = property(lambda self: self[1])
+
+
+def material_table(materials):
+    """[(kind, param), ...] (or Material objects, or a MATERIAL_DTYPE array) as the pt_material array the library takes."""
+    if isinstance(materials, np.ndarray) and materials.dtype == MATERIAL_DTYPE:
+        return np.ascontiguousarray(materials)
+    rows = [(m, 0.0) if np.isscalar(m) else tuple(m) for m in materials]
+    if any(len(r) != 2 for r in rows):
+        raise ValueError("materials: every entry is (kind, param)")
+    t = np.zeros(len(rows), dtype=MATERIAL_DTYPE)
+    for i, (kind, param) in enumerate(rows):
+        if int(kind) != kind:
+            raise ValueError(f"materials[{i}]: kind {kind!r} is not an integer")
+        t[i] = (int(kind), param)
+    return t
+
+
+def material_check(materials):
+    """pt_material_check: the host checks of Renderer.set_materials alone (no device); raises PtError naming the entry."""
+    t = material_table(materials)
+    check(lib.pt_material_check(t.ctypes.data if len(t) else None, len(t)))
+
+
 class Renderer(_Session):
     """ctypes view of pt_renderer (the reference's class Renderer, include/Renderer.h)."""
     _destroy = "pt_renderer_destroy"
@@ -713,6 +753,15 @@ class Renderer(_Session):
     def set_display(self, d_vertices):
         """Every frame also writes the display vertices (Denoiser::Denoise fused into the render); None switches it off."""
         check(lib.pt_renderer_set_display(self.handle, d_vertices))
+
+    def set_materials(self, materials):
+        """One (kind, param) per sphere: from now on every frame runs the materials kernel (kernel_info: VARIANT_MATERIALS).
+        None clears the table: the ordinary kernels again, bit for bit."""
+        if materials is None:
+            check(lib.pt_renderer_set_materials(self.handle, None, 0))
+            return
+        t = material_table(materials)
+        check(lib.pt_renderer_set_materials(self.handle, t.ctypes.data if len(t) else None, len(t)))
 
     def set_frame(self, frame):
         check(lib.pt_renderer_set_frame(self.handle, frame))
@@ -911,17 +960,21 @@ class MultiRenderer(_Session):
         return buf.value.decode()
 
 
-def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, **opts):
+def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, materials=None, **opts):
     """Convenience for tests: allocate, render rows [row_begin,row_end) on the GPU, download.
-    Returns (float32 [rows][width][14], kernel_ms)."""
+    Returns (float32 [rows][width][14], kernel_ms).  materials: [(kind, param), ...], one per sphere (Renderer.set_materials)."""
     if spheres is None:
         spheres = scene_cornell()
     if basis is None:
         basis = camera_basis(eye, width=width, height=height)
+    if materials is not None:
+        material_check(materials)  # before a renderer (a device) exists
     r = Renderer(width, height, spp, **opts)
     d_scene, n = upload_scene(spheres)
     d_out = DeviceBuffer(max(r.tile_floats * 4, 4))
     try:
+        if materials is not None:
+            r.set_materials(materials)
         ms = r.render(d_out.ptr, d_scene.ptr, n, basis, eye)
         img = d_out.download(np.float32, (r.rows, width, CHANNELS))
     finally:

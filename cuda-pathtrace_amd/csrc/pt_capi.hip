@@ -66,7 +66,13 @@ struct pt_renderer {
   hipEvent_t ev_last = nullptr;   // recorded after every launch on the stream it went to
   hipStream_t last_stream = nullptr;
   bool have_last = false;
+  // sphere materials (pt_renderer_set_materials, pt_materials.hip): while d_materials is set every launch is the materials kernel's
+  void* d_materials = nullptr;    // one 16-byte row per sphere
+  int n_materials = 0;
 };
+
+// the two kernels outside the variant table (pt_fast.hip, pt_materials.hip): no row to read, no chunking, no frame batches
+static bool outside_table(int variant) { return variant == PT_VARIANT_FAST || variant == PT_VARIANT_MATERIALS; }
 
 // the chunk count of the variant's chunk family (0: the variant belongs to none)
 static uint32_t chunks_of(const pt_renderer* r, int variant) {
@@ -150,6 +156,7 @@ static int cheapest_variant(int rng_mode, double w, int spp, int bounces, bool w
 
 static int effective_variant(pt_renderer* r, int n_spheres) {
   if (r->opts.fast_math) return PT_VARIANT_FAST;
+  if (r->d_materials) return PT_VARIANT_MATERIALS;  // (never with fast_math or an explicit variant: pt_renderer_set_materials)
   if (!r->auto_variant) return r->opts.variant;
   if (r->fail_pending && hipEventQuery(r->ev_fail) == hipSuccess) {
     r->fail_pending = false;
@@ -422,6 +429,7 @@ int pt_renderer_create(int width, int height, int samples_per_pixel, int threads
 int pt_renderer_destroy(pt_renderer* r) {
   if (!r) return PT_OK;
   if (r->d_state) (void)hipFree(r->d_state);  // Renderer.h:50
+  if (r->d_materials) (void)hipFree(r->d_materials);
   if (r->d_accel) (void)hipFree(r->d_accel);
   if (r->d_chunk) (void)hipFree(r->d_chunk);
   if (r->d_err) (void)hipFree(r->d_err);
@@ -489,7 +497,9 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
   if (n_spheres < 0 || (n_spheres > 0 && !d_spheres)) return pt_fail(PT_EINVAL, "render: bad scene (%d spheres)", n_spheres);
   if (!basis || !eye) return pt_fail(PT_EINVAL, "render: basis/eye is NULL");
   const int variant = effective_variant(r, n_spheres);
-  if (variant != PT_VARIANT_FAST && n_spheres > pt_kernel_max_spheres(variant))
+  if (variant == PT_VARIANT_MATERIALS && n_spheres != r->n_materials)
+    return pt_fail(PT_EINVAL, "render: n_spheres %d differs from the %d entries of the material table (pt_renderer_set_materials)", n_spheres, r->n_materials);
+  if (!outside_table(variant) && n_spheres > pt_kernel_max_spheres(variant))
     return pt_fail(PT_ELIMIT, "render: %d spheres exceed the LDS staging limit of %d", n_spheres,
                    pt_kernel_max_spheres(variant));
   a->fail_count = r->d_fail;
@@ -512,7 +522,7 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
   a->frame = r->frame;
   a->seed = r->opts.seed;
   // sample chunking: only for the kernels that chunk (reference configuration, variant 6), and only with a hand-over buffer
-  const bool chunking = variant != PT_VARIANT_FAST && chunk_buffer(r, variant, n_spheres);
+  const bool chunking = !outside_table(variant) && chunk_buffer(r, variant, n_spheres);
   a->chunks = chunking ? chunks_of(r, variant) : 0u;
   a->chunk_state = chunking ? r->d_chunk : nullptr;
   a->chunk_flag = chunking ? r->d_chunk + (size_t)PT_CHUNK_WORDS * r->tile_pixels : nullptr;
@@ -531,6 +541,7 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
 // OUTSIDE the event pair of pt_renderer_render so the returned kernel time is not distorted.
 static hipError_t launch(pt_renderer* r, const PixelKernelArgs& a, hipStream_t stream) {
   if (r->launch_variant == PT_VARIANT_FAST) return pt_launch_fast_kernel(a, r->opts.rng_mode, stream);
+  if (r->launch_variant == PT_VARIANT_MATERIALS) return pt_launch_materials_kernel(a, r->d_materials, r->opts.rng_mode, stream);
   return pt_launch_pixel_kernel(a, r->opts.rng_mode, r->launch_variant, stream);
 }
 
@@ -596,7 +607,7 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
   float* const saved_vertices = r->d_vertices;
   const size_t tile_floats = (size_t)r->tile_pixels * 14u, vtx_floats = (size_t)r->tile_pixels * 3u;
   const int variant = effective_variant(r, n_spheres);
-  const bool batched = n_frames >= 2 && r->tile_pixels > 0 && variant != PT_VARIANT_FAST &&
+  const bool batched = n_frames >= 2 && r->tile_pixels > 0 && !outside_table(variant) &&
                        pt_kernel_has_frames(variant, n_spheres, r->opts.max_bounces, r->opts.layout == PT_LAYOUT_PLANAR) &&
                        (r->opts.rng_mode != PT_RNG_XORWOW || r->d_state != nullptr) &&
                        out_stride_floats >= tile_floats && (d_vertices ? vtx_stride_floats >= vtx_floats : saved_vertices == nullptr);
@@ -740,6 +751,7 @@ int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
   char resume[64];
   variant_list(resume, &VariantInfo::resume);
   if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants %s)", resume);
+  if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
   if (!r->auto_variant && !pt_kernel_has_resume(r->opts.variant))
     return pt_fail(PT_EINVAL, "pt_progressive_create: kernel variant %d has no progressive passes (resume builds: variants %s)", r->opts.variant, resume);
   pt_progressive* p = new (std::nothrow) pt_progressive();
@@ -814,6 +826,7 @@ static int progressive_args(pt_progressive* p, int spp, float* d_out, const pt_s
   if (p->samples > 0 && (memcmp(p->cam, basis, 12 * sizeof(float)) != 0 || memcmp(p->cam + 12, eye, 3 * sizeof(float)) != 0 ||
                          p->spheres != d_spheres || p->n_spheres != n_spheres))
     return pt_fail(PT_EINVAL, "pt_progressive: camera or scene differs from the session's first pass: reset the session");
+  if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
   const int v = session_variant(r, n_spheres);
   if (!pt_kernel_has_resume(v)) return pt_fail(PT_EINVAL, "pt_progressive: kernel variant %d has no progressive passes", v);
   if (n_spheres > pt_kernel_max_spheres(v))
@@ -1069,6 +1082,61 @@ int pt_renderer_set_display(pt_renderer* r, float* d_vertices) {
   return PT_OK;
 }
 
+// ---- sphere materials (include/ptcore.h; the kernel: pt_materials.hip) -------------------------------------------------------
+int pt_material_check(const pt_material* table, int n) {
+  if (!table) return pt_fail(PT_EINVAL, "pt_material_check: table is NULL");
+  if (n < 1) return pt_fail(PT_EINVAL, "pt_material_check: n %d (a table has one entry per sphere; NULL, 0 clears a renderer's)", n);
+  if (n > PT_MATERIALS_MAX_SPHERES)
+    return pt_fail(PT_ELIMIT, "pt_material_check: n %d exceeds the %d spheres the materials kernel stages", n, PT_MATERIALS_MAX_SPHERES);
+  for (int i = 0; i < n; i++) {
+    const int kind = table[i].kind;
+    const float p = table[i].param;
+    if (kind < PT_MATERIAL_DIFFUSE || kind > PT_MATERIAL_GLASS) return pt_fail(PT_EINVAL, "pt_material_check: table[%d].kind %d (0 .. 3)", i, kind);
+    if (!isfinite(p)) return pt_fail(PT_EINVAL, "pt_material_check: table[%d].param is not finite", i);
+    if ((kind == PT_MATERIAL_DIFFUSE || kind == PT_MATERIAL_MIRROR) && p != 0.0f)
+      return pt_fail(PT_EINVAL, "pt_material_check: table[%d].param %g (%s takes 0)", i, (double)p, kind == PT_MATERIAL_DIFFUSE ? "DIFFUSE" : "MIRROR");
+    if (kind == PT_MATERIAL_GLOSSY && !(p > 0.0f && p < 1.0f))
+      return pt_fail(PT_EINVAL, "pt_material_check: table[%d].param %g (GLOSSY roughness: 0 < rho < 1)", i, (double)p);
+    if (kind == PT_MATERIAL_GLASS && !(p > 1.0f && p <= 4.0f))
+      return pt_fail(PT_EINVAL, "pt_material_check: table[%d].param %g (GLASS index of refraction: 1 < eta <= 4)", i, (double)p);
+  }
+  return PT_OK;
+}
+
+int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int n) {
+  if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_materials: renderer is NULL");
+  const bool clear = !host_table && n == 0;
+  if (!clear) {
+    if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_renderer_set_materials: a fast_math renderer has no materials");
+    if (!r->auto_variant)
+      return pt_fail(PT_EINVAL, "pt_renderer_set_materials: the renderer has an explicit kernel variant (%d); the materials kernel is none of the table's: leave variant at -1", r->opts.variant);
+    const int rc = pt_material_check(host_table, n);
+    if (rc != PT_OK) return rc;
+  }
+  PT_HIP(hipDeviceSynchronize());  // no frame in flight reads the table that goes
+  if (r->d_materials) {
+    void* old = r->d_materials;
+    r->d_materials = nullptr;
+    r->n_materials = 0;
+    PT_HIP(hipFree(old));
+  }
+  if (clear) return PT_OK;
+  unsigned char* rows = new (std::nothrow) unsigned char[(size_t)n * 16];
+  if (!rows) return pt_fail(PT_ENOMEM, "pt_renderer_set_materials: out of host memory");
+  for (int i = 0; i < n; i++) pt_materials_device_row(host_table + i, rows + (size_t)i * 16);
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, (size_t)n * 16);
+  if (e == hipSuccess) e = hipMemcpy(d, rows, (size_t)n * 16, hipMemcpyHostToDevice);
+  delete[] rows;
+  if (e != hipSuccess) {
+    if (d) (void)hipFree(d);
+    return pt_fail(PT_EHIP, "pt_renderer_set_materials: %s", hipGetErrorString(e));
+  }
+  r->d_materials = d;
+  r->n_materials = n;
+  return PT_OK;
+}
+
 int pt_renderer_set_frame(pt_renderer* r, uint32_t frame) {
   if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_frame: renderer is NULL");
   r->frame = frame;
@@ -1101,6 +1169,18 @@ int pt_renderer_kernel_info(pt_renderer* r, int n_spheres, pt_kernel_info* info)
   if (!r || !info) return pt_fail(PT_EINVAL, "pt_renderer_kernel_info: NULL argument");
   hipFuncAttributes fa;
   const int variant = effective_variant(r, n_spheres);
+  if (variant == PT_VARIANT_MATERIALS) {
+    PT_HIP(hipFuncGetAttributes(&fa, pt_materials_kernel_symbol(r->opts.rng_mode)));
+    info->block_threads = PT_BLOCK_THREADS;
+    info->grid_blocks = (int)(((uint64_t)r->tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
+    info->lds_bytes = (int)pt_materials_kernel_lds_bytes(n_spheres < 0 ? 0 : (n_spheres > PT_MATERIALS_MAX_SPHERES ? PT_MATERIALS_MAX_SPHERES : n_spheres));
+    info->variant = variant;
+    info->num_vgprs = fa.numRegs;
+    info->reserved0 = 0;
+    info->scratch_bytes = (int)fa.localSizeBytes;
+    info->max_spheres = PT_MATERIALS_MAX_SPHERES;
+    return PT_OK;
+  }
   const bool fast = variant == PT_VARIANT_FAST;
   PT_HIP(hipFuncGetAttributes(&fa, fast ? pt_fast_kernel_symbol(r->opts.rng_mode, n_spheres, r->opts.max_bounces)
                                         : pt_kernel_symbol(r->opts.rng_mode, variant, n_spheres, r->opts.max_bounces,

@@ -310,6 +310,12 @@ hipError_t pt_launch_setup_random(uint32_t* state, int width, int row_begin, uin
 const void* pt_fast_kernel_symbol(int rng_mode, int n_spheres, int max_bounces);
 size_t pt_fast_kernel_lds_bytes(int n_spheres);
 hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStream_t stream);
+// sphere materials (pt_materials.hip): one kernel family outside the variant table and the launch census.  d_table: one 16-byte
+// row per sphere, formed from a pt_material by pt_materials_device_row
+const void* pt_materials_kernel_symbol(int rng_mode);
+size_t pt_materials_kernel_lds_bytes(int n_spheres);
+void pt_materials_device_row(const pt_material* m, void* row16);
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, hipStream_t stream);
 
 // The launch census (lab library only; include/ptcore_lab.h, pt_debug_launch_census): every launcher of a pixel kernel ends in
 // PT_LAUNCHED(fn, modes) -- the launch's status, and in the lab library a count under the function it handed to

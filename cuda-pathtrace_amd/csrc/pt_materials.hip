@@ -1,0 +1,277 @@
+// pt_materials.hip -- per-sphere materials (pt_renderer_set_materials): DIFFUSE, MIRROR, GLOSSY and GLASS in one exact kernel.
+//
+// EXACT code like the pixel kernels and pt_temporal.hip: contraction off, every operation rounded once, IEEE divisions and
+// square roots, in the order EXACTNESS.md A.22 fixes; tests/materials_model.py is the same definition in NumPy float32 and the
+// kernel equals it bit for bit.  With an all-diffuse table the frame is the oracle's (the anchor: every line a diffuse bounce
+// executes is one of trace_ray's, pt_trace.h).
+//
+// The family stands OUTSIDE the variant table (kVariants, pt_kernel.hip) and the launch census: it has no row, its launches do
+// not go through PT_LAUNCHED, pt_debug_kernel_builds does not list it.  pt_renderer_kernel_info reports PT_VARIANT_MATERIALS.
+//
+// Nearest hit: tracer level 6 WITHOUT its three origin-dependent shortcuts (intersect_scene<6, PRIMARY = false, LAST = false,
+// WALLS = false>, pt_intersect.h).  What is left rests on A.1, A.2 and A.8 alone -- the screen ranks the contract's own floats
+// and every doubtful lane runs the literal loop -- and none of those arguments looks at where a ray starts.  The shortcuts that
+// do (the staged eye terms and pixel footprints of primary rays, A.7; the wall certificate, which assumes an origin inside the
+// box; the uniform grid's admission radius, A.6) are not instantiated: a refracted ray starts 0.05 INSIDE a sphere.
+//
+// Divergence: the four kinds meet inside a wave64.  The pieces are computed once and selected -- the cosine direction serves
+// DIFFUSE and GLOSSY, the mirror direction MIRROR, GLOSSY and both reflecting arms of GLASS -- under two wave-uniform skips
+// (no lane of the wave on a non-diffuse sphere; no lane on glass), so a wave that sees only diffuse surfaces runs trace_ray's
+// instructions and nothing else.
+#include <cstring>
+
+#include "pt_intersect.h"
+#include "pt_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace pt {
+namespace materials {
+
+// one row of the device table: what pt_renderer_set_materials forms on the host from a pt_material, in float32
+struct Row {
+  int32_t kind;  // PT_MATERIAL_*
+  float param;   // GLOSSY: rho; GLASS: eta
+  float inv;     // GLASS: 1.0f / eta
+  float r0;      // GLASS: ((eta - 1)(eta - 1)) / ((eta + 1)(eta + 1))
+};
+static_assert(sizeof(Row) == sizeof(float4), "one LDS slot per sphere");
+
+struct Step {
+  F3 normal;  // nl: the first-hit feature
+  F3 o, d;    // next ray
+  float w;    // factor on the mask after the colour (1 where the definition has none: x * 1.0f is x)
+};
+
+// everything of a bounce after the search and the draws (EXACTNESS.md A.22).  FAST: the cheap sequences of the level-6 tracer
+// (A.3: identical bits inside their verified domains; outside, `bad` is raised and the caller redoes the step with FAST = false)
+template <bool FAST>
+__device__ __forceinline__ Step bounce_step(F3 o, F3 d, float t, F3 centre, float u_az, float u_el, const Row m, bool& bad,
+                                            const float* unit_tab, uint32_t absmask) {
+  Step out;
+  // today's lines (bounce_geometry, pt_device.h): pos, nl, o' = pos + nl * 0.05f, the cosine-weighted direction
+  bool bad_d = false;
+  const BounceGeom bg = bounce_geometry<FAST, FAST>(o, d, t, centre, u_az, u_el, bad_d, unit_tab, absmask);
+  bad = bad | bad_d;
+  out.normal = bg.normal;
+  out.o = bg.o;
+  out.d = bg.d;
+  out.w = 1.0f;
+  const int kind = m.kind;
+  if (__builtin_amdgcn_ballot_w64(kind != PT_MATERIAL_DIFFUSE) == 0ull) return out;  // wave-uniform
+
+  // the same pos and geometric normal again (the same operations on the same operands: the compiler keeps one copy)
+  bool bad_m = false;
+  const F3 pos = o + d * t;
+  F3 nr = pos - centre;
+  if constexpr (FAST) nr = normalize_nb(nr, bad_m); else nr = normalize(nr);
+  const bool front = dot(nr, d) < 0.0f;
+  const F3 nl = bg.normal;  // front ? nr : nr * -1.0f
+  auto unit = [&](F3 v, bool& flag) { if constexpr (FAST) return normalize_nb(v, flag); else return normalize(v); };
+  const F3 du = unit(d, bad_m);  // a primary ray is not of unit length
+  const float ddn = dot(nl, du);
+  const F3 mir = unit(du - nl * (2.0f * ddn), bad_m);
+  const F3 gl = unit(mir + (bg.d - mir) * m.param, bad_m);  // GLOSSY: no pdf weight (the diffuse bounce has none either)
+  F3 dn = kind == PT_MATERIAL_GLOSSY ? gl : mir;
+  F3 on = bg.o;
+  float w = 1.0f;
+  if (__builtin_amdgcn_ballot_w64(kind == PT_MATERIAL_GLASS) != 0ull) {  // wave-uniform
+    bool bad_g = false;
+    const float nnt = front ? m.inv : m.param;
+    const float k = 1.0f - (nnt * nnt) * (1.0f - ddn * ddn);
+    const bool tir = !(k >= 0.0f);  // total internal reflection, and what a NaN takes: the MIRROR step, no weight
+    float s;
+    if constexpr (FAST) s = sqrt_cr_f32_nb(k, bad_g); else s = sqrtf(k);
+    const F3 td = unit(du * nnt - nl * (ddn * nnt + s), bad_g);
+    const float cx = front ? -ddn : dot(td, nr);
+    const float c1 = 1.0f - cx;
+    const float c5 = ((c1 * c1) * (c1 * c1)) * c1;
+    const float re = m.r0 + (1.0f - m.r0) * c5;
+    const float p = 0.25f + 0.5f * re;
+    const bool reflect = u_az < p;
+    const float wr = re / p, wt = (1.0f - re) / (1.0f - p);
+    const bool glass = kind == PT_MATERIAL_GLASS;
+    const bool through = glass & !tir & !reflect;
+    if (glass & !tir) w = reflect ? wr : wt;
+    const F3 oi = pos - nl * 0.05f;  // pushed through the surface
+    if (through) {
+      dn = td;
+      on = oi;
+    }
+    bad_m = bad_m | (glass & !tir & bad_g);
+  }
+  if (kind != PT_MATERIAL_DIFFUSE) {
+    out.o = on;
+    out.d = dn;
+    out.w = w;
+    bad = bad | bad_m;
+  }
+  return out;
+}
+
+#ifndef PT_MATERIALS_MIN_WAVES
+#define PT_MATERIALS_MIN_WAVES 4  // <= 128 VGPRs
+#endif
+template <int RNG>
+__global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixel_kernel_materials(PixelKernelArgs a, const Row* __restrict__ table) {
+  extern __shared__ float4 lds_scene[];
+  // the table is staged beside the scene image: one slot per sphere after the small tables; stage_scene's barrier covers it
+  Row* mtab = reinterpret_cast<Row*>(lds_scene + 4 * a.n_spheres + kTablesF4);
+  for (int i = threadIdx.x; i < a.n_spheres; i += blockDim.x) mtab[i] = table[i];
+  SceneLds sc = stage_scene<false>(a.spheres, a.n_spheres, lds_scene, false, mk3(a.eye[0], a.eye[1], a.eye[2]), a.spp);
+
+  const uint32_t tp = blockIdx.x * PT_BLOCK_THREADS + threadIdx.x;
+  const bool active = tp < a.tile_pixels;  // lanes past the tile stay for the cooperative parts
+  const int row = a.row_begin + (int)(tp / (uint32_t)a.width);
+  const int col = (int)(tp % (uint32_t)a.width);
+  const uint32_t id = (uint32_t)row * (uint32_t)a.width + (uint32_t)col;  // :206
+
+  Rng<RNG> rng;
+  if constexpr (RNG == PT_RNG_XORWOW) {
+    if (a.rng_state && active) {  // :212
+      const uint32_t* s = a.rng_state + (size_t)tp * 6;
+      rng.st = Xorwow{s[0], s[1], s[2], s[3], s[4], s[5]};
+    } else {
+      xorwow_init(rng.st, (uint64_t)id + a.seed);  // :265
+    }
+  } else {
+    rng.k0 = (uint32_t)a.seed;
+    rng.k1 = (uint32_t)(a.seed >> 32) ^ a.frame;
+    rng.pix = id;
+  }
+  const F3 B0 = mk3(a.basis[0], a.basis[1], a.basis[2]), B1 = mk3(a.basis[3], a.basis[4], a.basis[5]);
+  const F3 B2 = mk3(a.basis[6], a.basis[7], a.basis[8]), B3 = mk3(a.basis[9], a.basis[10], a.basis[11]);
+  const F3 eye = mk3(a.eye[0], a.eye[1], a.eye[2]);
+
+  Welford var[4] = {{0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}, {0, 0.0f, 0.0f}};
+  TraceOutput L{mk3(0, 0, 0), mk3(0, 0, 0), mk3(0, 0, 0), 0.0f};
+
+  const int spp = active ? a.spp : 0;
+  for (int i = 0; i < spp; i++) {  // :219
+    rng.begin_sample((uint32_t)i);
+    float sx = (float)row, sy = (float)col;  // :221-229
+    if (a.spp != 1) {
+      float jx, jy;
+      rng.jitter(jx, jy);
+      sx += jx * 1.0f - 0.5f;
+      sy += jy * 1.0f - 0.5f;
+    }
+    sx /= (float)a.height;  // contract C7
+    sy /= (float)a.width;
+    F3 d = lerp(lerp(B0, B1, sy), lerp(B2, B3, sy), 1.0f - sx);
+    F3 o = eye;
+    F3 color = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
+    bool escaped = false;
+    for (int n = 0; n < a.max_bounces; n++) {  // :155
+      float t = 0.0f;
+      int idx = 0;
+      if (!intersect_scene<6, false, false, false>(sc, a.n_spheres, o, d, t, idx)) {  // :157-161
+        escaped = true;
+        break;
+      }
+      const float4 g = sc.geom_lane(idx);
+      F3 emis, scol;
+      float lum_col = 0.0f;
+      fetch_material(sc, idx, emis, scol, n == 0 ? &lum_col : nullptr);
+      const Row m = mtab[idx];
+      float u_az, u_el;
+      rng.bounce(n, u_az, u_el);  // for every kind, used or not: the generator's position depends on the bounce number alone
+      const F3 centre = mk3(g.x, g.y, g.z);
+      bool bad = false;
+      Step st = bounce_step<true>(o, d, t, centre, u_az, u_el, m, bad, sc.inv1, sc.absmask);
+      if (__builtin_expect(bad, 0)) st = bounce_step<false>(o, d, t, centre, u_az, u_el, m, bad, nullptr, sc.absmask);
+      const F3 me = mask * emis;
+      if (n == 0)  // :171-172
+        color = color + mk3(clampf(me.x, 0.0f, 1.0f), clampf(me.y, 0.0f, 1.0f), clampf(me.z, 0.0f, 1.0f));
+      else  // :174
+        color = color + me;
+      mask = mask * scol;  // :175
+      mask = mask * st.w;  // GLASS: Re / P or (1 - Re) / (1 - P), after the colour
+      if (n == 0) {        // :187-195, from nl, the sphere's colour and t
+        L.normal = L.normal + st.normal;
+        L.albedo = L.albedo + scol;
+        L.depth += t;
+        welford_update3(var[1], var[2], var[3], luminance(st.normal), lum_col, t, sc.rcpn);
+      }
+      o = st.o;
+      d = st.d;
+    }
+    L.color = L.color + color;  // :159 / :198
+    if (!escaped) welford_update(var[0], luminance(color), sc.rcpn);  // :200
+  }
+
+  float px[14];
+  frame_values(L, var, (float)a.spp, px);  // :234-254
+  if (a.vertices && active) store_display_vertex(a.vertices + (size_t)tp * 3, a.width, row, col, px[0], px[1], px[2]);
+  if (a.planar) {
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < 14; c++) a.out[(size_t)c * a.tile_pixels + tp] = px[c];
+    }
+  } else {
+    // a full wave's 64 pixels are one contiguous 3584-byte span: transpose through the wave's LDS slice, 16-byte stores
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool wave_full = (__builtin_amdgcn_ballot_w64(active) == ~0ull) && ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0u);
+    if (wave_full) {
+      float* wl = reinterpret_cast<float*>(lds_scene + a.scene_lds_f4) + wave * (64 * 14);
+#pragma unroll
+      for (int c = 0; c < 14; c++) wl[lane * 14 + c] = px[c];
+      __builtin_amdgcn_wave_barrier();
+      const float4* src = reinterpret_cast<const float4*>(wl);
+      float4* dst = reinterpret_cast<float4*>(a.out + (size_t)(tp - (uint32_t)lane) * 14);
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int q = lane + 64 * k;
+        if (q < 224) dst[q] = src[q];
+      }
+    } else if (active) {
+      float* op = a.out + (size_t)tp * 14;
+#pragma unroll
+      for (int c = 0; c < 14; c++) op[c] = px[c];
+    }
+  }
+  if constexpr (RNG == PT_RNG_XORWOW) {
+    if (a.rng_state && active) {  // :256
+      uint32_t* s = a.rng_state + (size_t)tp * 6;
+      s[0] = rng.st.d; s[1] = rng.st.v0; s[2] = rng.st.v1; s[3] = rng.st.v2; s[4] = rng.st.v3; s[5] = rng.st.v4;
+    }
+  }
+}
+
+}  // namespace materials
+}  // namespace pt
+
+typedef void (*materials_kernel_fn)(PixelKernelArgs, const pt::materials::Row*);
+
+static materials_kernel_fn select_materials(int rng_mode) {
+  return rng_mode == PT_RNG_PHILOX ? pt::materials::pixel_kernel_materials<PT_RNG_PHILOX> : pt::materials::pixel_kernel_materials<PT_RNG_XORWOW>;
+}
+
+const void* pt_materials_kernel_symbol(int rng_mode) { return (const void*)select_materials(rng_mode); }
+
+static uint32_t materials_scene_f4(int n_spheres) { return (uint32_t)n_spheres * 5u + (uint32_t)pt::kTablesF4; }  // scene image, small tables, table
+
+size_t pt_materials_kernel_lds_bytes(int n_spheres) {
+  return (size_t)materials_scene_f4(n_spheres) * sizeof(float4) + (PT_BLOCK_THREADS / 64) * 64 * 14 * sizeof(float);
+}
+
+// a pt_material as the kernel reads it; 1 / eta and R0 are formed here, in float32, one rounding per operation
+void pt_materials_device_row(const pt_material* m, void* row16) {
+  pt::materials::Row r{m->kind, m->param, 0.0f, 0.0f};
+  if (m->kind == PT_MATERIAL_GLASS) {
+    const float eta = m->param;
+    const float em = eta - 1.0f, ep = eta + 1.0f;
+    r.inv = 1.0f / eta;
+    r.r0 = (em * em) / (ep * ep);
+  }
+  memcpy(row16, &r, sizeof(r));
+}
+
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, hipStream_t stream) {
+  PixelKernelArgs b = a;
+  b.scene_lds_f4 = materials_scene_f4(a.n_spheres);
+  const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
+  hipLaunchKernelGGL(select_materials(rng_mode), dim3(grid), dim3(PT_BLOCK_THREADS), pt_materials_kernel_lds_bytes(a.n_spheres), stream, b,
+                     (const pt::materials::Row*)d_table);
+  return hipGetLastError();  // (outside the launch census: no PT_LAUNCHED)
+}

@@ -37,6 +37,12 @@ class Renderer {
   ~Renderer() { (void)pt_renderer_destroy(impl); }  // Renderer.h:48-53
   pt_renderer* Handle() const { return impl; }  // extension: the C ABI object (ProgressiveRenderer.h)
 
+  // Extension (the reference renders diffuse surfaces only): one material per sphere of the scenes this renderer will be given
+  // (Material.h, pt_renderer_set_materials); from now on every Render runs the materials kernel.  An empty table clears it.
+  void SetMaterials(const std::vector<pt_material>& table) {
+    gpuErrchk(pt_renderer_set_materials(impl, table.empty() ? NULL : table.data(), (int)table.size()));
+  }
+
   // Renderer.h:55-76: synchronous, returns kernel-only milliseconds.
   float Render(OutputBuffer d_buffer, const Scene& d_scene, const Camera& camera) {
     float3 eyeRayBasis[4];

@@ -29,7 +29,9 @@
 // written to <output>_tm.ppm; the frame itself, hence the EXR, the bitmaps and --preview, keeps its bytes),
 // --compare REF.exr (FrameCompare / pt_compare_*: the final colour of every frame of the headless loop and of every progressive
 // pass is compared on the device with the colour of REF, an EXR of the same size read by ExrReader.h, after --temporal, --filter
-// and -d and before --tonemap; one "compare:" line per frame or pass).
+// and -d and before --tonemap; one "compare:" line per frame or pass),
+// --materials FILE | smallpt (Material.h, pt_renderer_set_materials: a material per sphere -- mirror, glossy, glass -- for the
+// single frame and the headless loop; every stage behind Render() only sees frames.  Not with --progressive, --batch or --gpus).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -48,6 +50,7 @@
 #include "ExrReader.h"
 #include "FeatureFilter.h"
 #include "FrameCompare.h"
+#include "Material.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
 #include "ProgressiveRenderer.h"
@@ -105,6 +108,8 @@ static void usage() {
                "  --temporal-clamp-radius arg   with --temporal-fast-cap: the window is (2 arg + 1)^2 pixels, 1 .. 3 (default 1)\n"
                "  --velocities arg              with --frames / --poses: file of 'index vx vy vz' lines; sphere index moves by v per frame\n"
                "                                (with --temporal every pixel follows the sphere it shows)\n"
+               "  --materials arg               file of 'index kind [param]' lines (kind: diffuse | mirror | glossy rho | glass eta), or\n"
+               "                                'smallpt': sphere 6 a mirror, sphere 7 glass of index 1.5; unlisted spheres are diffuse\n"
                "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
                "  --exposure arg                with --tonemap: auto (default, metered on the device) or a number > 0\n"
                "  --tonemap-key arg             with --tonemap: luminance the metered mean is mapped to (default 0.18)\n"
@@ -127,7 +132,7 @@ int main(int argc, const char** argv) {
   std::string outputName = "output/out";
   std::string rng = "xorwow";
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
-  std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile;
+  std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile, materialsArg;
   bool denoisePrecisionGiven = false;
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
@@ -216,6 +221,7 @@ int main(int argc, const char** argv) {
     else if (a == "--compare") compareFile = value("--compare");
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--velocities") velocitiesFile = value("--velocities");
+    else if (a == "--materials") materialsArg = value("--materials");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
     else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
@@ -402,6 +408,22 @@ int main(int argc, const char** argv) {
       return 1;
     }
   }
+  // --materials: the table on the host, checked by the library's own host checks (before any device is touched)
+  std::vector<pt_material> materials;
+  if (!materialsArg.empty()) {
+    const char* other = progressiveGiven ? "--progressive" : batch ? "--batch" : multi ? "--gpus" : NULL;
+    if (other) {
+      std::cerr << "ERROR: --materials cannot be combined with " << other
+                << ": the materials kernel renders single frames on one device (no progressive passes, no frame batches)" << std::endl;
+      return 1;
+    }
+    const int count = nSpheres > 0 ? nSpheres : 9;
+    std::string why;
+    if (!(materialsArg == "smallpt" ? SmallptMaterials(count, materials, why) : ParseMaterials(materialsArg, count, materials, why))) {
+      std::cerr << "ERROR: --materials: " << why << std::endl;
+      return 1;
+    }
+  }
   pt_tonemap_opts tonemapOpts;
   pt_tonemap_opts_default(&tonemapOpts);
   if (tonemapOption && !tonemapGiven) {  // (before any device is touched)
@@ -541,6 +563,7 @@ int main(int argc, const char** argv) {
     std::cout << "Exchange: " << tiled->Backend() << std::endl;
   } else {
     single = new Renderer(width, height, samplesPerPixel, threadsPerBlock, opts);
+    if (!materials.empty()) single->SetMaterials(materials);
   }
   // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
   DenoiseNet* net =

@@ -212,6 +212,38 @@ typedef struct pt_kernel_info {
 } pt_kernel_info;
 int pt_renderer_kernel_info(pt_renderer* r, int n_spheres, pt_kernel_info* info);
 
+/* ---- sphere materials (opt-in; csrc/pt_materials.hip, EXACTNESS.md A.22) --------------------- */
+/* The reference renders diffuse surfaces only.  A material table gives every sphere one of four kinds; a renderer without a
+ * table is exactly what it was.  EXACT code: the frame equals tests/materials_model.py, the definition in NumPy float32, bit
+ * for bit, and with an all-diffuse table it equals the oracle's frame.  Every kind takes the two generator draws of a bounce,
+ * so both generators serve as they are. */
+enum {
+  PT_MATERIAL_DIFFUSE = 0, /* the reference's bounce; param 0                                                    */
+  PT_MATERIAL_MIRROR = 1,  /* a perfect mirror; param 0                                                          */
+  PT_MATERIAL_GLOSSY = 2,  /* the mirror direction blended towards the diffuse one by param = roughness, 0 < rho < 1 */
+  PT_MATERIAL_GLASS = 3    /* smallpt's dielectric with Schlick's Fresnel term; param = index of refraction, 1 < eta <= 4 */
+};
+typedef struct pt_material {
+  int32_t kind; /* PT_MATERIAL_* */
+  float param;
+} pt_material;
+#define PT_MATERIALS_MAX_SPHERES 64 /* a scene with a table is staged whole: more spheres are PT_ELIMIT */
+#define PT_VARIANT_MATERIALS 101    /* pt_kernel_info.variant while a table is set (a pseudo-variant like the fast mode's 100: no
+                                     * row of the variant table, no value of pt_renderer_opts.variant) */
+/* The host checks of pt_renderer_set_materials alone (no device, no renderer): PT_EINVAL naming the entry for a null table,
+ * n < 1, a kind outside 0..3, a param that is not finite or outside its kind's range, a non-zero param for DIFFUSE or MIRROR;
+ * PT_ELIMIT for n > PT_MATERIALS_MAX_SPHERES. */
+int pt_material_check(const pt_material* table, int n);
+/* One material per sphere, in sphere order (host array, copied to the device before the call returns; it synchronises the
+ * device first, so no frame in flight reads a table that is being replaced).  While a table is set EVERY render / enqueue of the
+ * renderer runs the materials kernel -- an all-diffuse table too: no silent fallback -- and pt_renderer_kernel_info reports
+ * PT_VARIANT_MATERIALS; a render whose n_spheres differs from n is PT_EINVAL and launches nothing, pt_renderer_enqueue_frames is
+ * the loop of single enqueues, and pt_progressive_create / a session's passes are refused.  (NULL, 0) clears the table: the
+ * renderer runs the ordinary kernels again, bit for bit as before.  Refused (PT_EINVAL, before a device is touched): whatever
+ * pt_material_check refuses, a fast_math renderer, a renderer with an explicit kernel variant.  Both output layouts and the
+ * display vertices of pt_renderer_set_display are supported.  pt_mgpu has no materials. */
+int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int n);
+
 /* ---- one frame over several GPUs of one node ------------------------------------------------- */
 /* The reference selects ONE device per process (cudaSetDevice(cudaDevice), src/main.cu:86) and its
  * Renderer covers the whole image with one launch (Renderer.h:29-33,69).  pt_mgpu_* is the same
