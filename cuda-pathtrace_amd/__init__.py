@@ -62,6 +62,7 @@ class RendererOpts(ctypes.Structure):
 
 VARIANT_FAST = 100
 VARIANT_MATERIALS = 101  # PT_VARIANT_MATERIALS: what kernel_info reports while a material table is set
+VARIANT_MATERIALS_LIGHTS = 102  # PT_VARIANT_MATERIALS_LIGHTS: ... while direct light sampling is on (Renderer.set_light_sampling)
 LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
 # sphere materials (pt_material, include/ptcore.h; EXACTNESS.md A.22)
 MATERIAL_DIFFUSE, MATERIAL_MIRROR, MATERIAL_GLOSSY, MATERIAL_GLASS = 0, 1, 2, 3
@@ -141,6 +142,7 @@ ABI = {
     "pt_renderer_kernel_info": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(KernelInfo)]),
     "pt_material_check": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_renderer_set_materials": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "pt_renderer_set_light_sampling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_mgpu_opts_default": (None, [ctypes.POINTER(MgpuOpts)]),
     "pt_mgpu_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(RendererOpts), ctypes.POINTER(MgpuOpts), ctypes.POINTER(_vp)]),
@@ -763,6 +765,12 @@ class Renderer(_Session):
         t = material_table(materials)
         check(lib.pt_renderer_set_materials(self.handle, t.ctypes.data if len(t) else None, len(t)))
 
+    def set_light_sampling(self, on):
+        """Direct light sampling (next-event estimation, EXACTNESS.md A.23): every DIFFUSE hit but the last bounce's samples each
+        emitting sphere (kernel_info: VARIANT_MATERIALS_LIGHTS), with or without a material table.  False: exactly what the
+        renderer was before."""
+        check(lib.pt_renderer_set_light_sampling(self.handle, 1 if on else 0))
+
     def set_frame(self, frame):
         check(lib.pt_renderer_set_frame(self.handle, frame))
 
@@ -960,9 +968,10 @@ class MultiRenderer(_Session):
         return buf.value.decode()
 
 
-def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, materials=None, **opts):
+def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, materials=None, light_sampling=False, **opts):
     """Convenience for tests: allocate, render rows [row_begin,row_end) on the GPU, download.
-    Returns (float32 [rows][width][14], kernel_ms).  materials: [(kind, param), ...], one per sphere (Renderer.set_materials)."""
+    Returns (float32 [rows][width][14], kernel_ms).  materials: [(kind, param), ...], one per sphere (Renderer.set_materials);
+    light_sampling: Renderer.set_light_sampling."""
     if spheres is None:
         spheres = scene_cornell()
     if basis is None:
@@ -975,6 +984,8 @@ def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, 
     try:
         if materials is not None:
             r.set_materials(materials)
+        if light_sampling:
+            r.set_light_sampling(True)
         ms = r.render(d_out.ptr, d_scene.ptr, n, basis, eye)
         img = d_out.download(np.float32, (r.rows, width, CHANNELS))
     finally:

@@ -69,10 +69,15 @@ struct pt_renderer {
   // sphere materials (pt_renderer_set_materials, pt_materials.hip): while d_materials is set every launch is the materials kernel's
   void* d_materials = nullptr;    // one 16-byte row per sphere
   int n_materials = 0;
+  // direct light sampling (pt_renderer_set_light_sampling): every launch is the materials kernel's LIGHTS build, on d_materials
+  // or, without a table, on d_all_diffuse (PT_MATERIALS_MAX_SPHERES zeroed rows: kind DIFFUSE, param 0)
+  bool light_sampling = false;
+  void* d_all_diffuse = nullptr;
 };
 
-// the two kernels outside the variant table (pt_fast.hip, pt_materials.hip): no row to read, no chunking, no frame batches
-static bool outside_table(int variant) { return variant == PT_VARIANT_FAST || variant == PT_VARIANT_MATERIALS; }
+// the kernels outside the variant table (pt_fast.hip, pt_materials.hip): no row to read, no chunking, no frame batches
+static bool materials_variant(int variant) { return variant == PT_VARIANT_MATERIALS || variant == PT_VARIANT_MATERIALS_LIGHTS; }
+static bool outside_table(int variant) { return variant == PT_VARIANT_FAST || materials_variant(variant); }
 
 // the chunk count of the variant's chunk family (0: the variant belongs to none)
 static uint32_t chunks_of(const pt_renderer* r, int variant) {
@@ -156,6 +161,7 @@ static int cheapest_variant(int rng_mode, double w, int spp, int bounces, bool w
 
 static int effective_variant(pt_renderer* r, int n_spheres) {
   if (r->opts.fast_math) return PT_VARIANT_FAST;
+  if (r->light_sampling) return PT_VARIANT_MATERIALS_LIGHTS;  // (never with fast_math or an explicit variant either)
   if (r->d_materials) return PT_VARIANT_MATERIALS;  // (never with fast_math or an explicit variant: pt_renderer_set_materials)
   if (!r->auto_variant) return r->opts.variant;
   if (r->fail_pending && hipEventQuery(r->ev_fail) == hipSuccess) {
@@ -430,6 +436,7 @@ int pt_renderer_destroy(pt_renderer* r) {
   if (!r) return PT_OK;
   if (r->d_state) (void)hipFree(r->d_state);  // Renderer.h:50
   if (r->d_materials) (void)hipFree(r->d_materials);
+  if (r->d_all_diffuse) (void)hipFree(r->d_all_diffuse);
   if (r->d_accel) (void)hipFree(r->d_accel);
   if (r->d_chunk) (void)hipFree(r->d_chunk);
   if (r->d_err) (void)hipFree(r->d_err);
@@ -497,8 +504,11 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
   if (n_spheres < 0 || (n_spheres > 0 && !d_spheres)) return pt_fail(PT_EINVAL, "render: bad scene (%d spheres)", n_spheres);
   if (!basis || !eye) return pt_fail(PT_EINVAL, "render: basis/eye is NULL");
   const int variant = effective_variant(r, n_spheres);
-  if (variant == PT_VARIANT_MATERIALS && n_spheres != r->n_materials)
+  if (materials_variant(variant) && r->d_materials && n_spheres != r->n_materials)
     return pt_fail(PT_EINVAL, "render: n_spheres %d differs from the %d entries of the material table (pt_renderer_set_materials)", n_spheres, r->n_materials);
+  if (variant == PT_VARIANT_MATERIALS_LIGHTS && !r->d_materials && n_spheres > PT_MATERIALS_MAX_SPHERES)
+    return pt_fail(PT_ELIMIT, "render: %d spheres exceed the %d spheres (PT_MATERIALS_MAX_SPHERES) the light-sampling kernel stages (pt_renderer_set_light_sampling)",
+                   n_spheres, PT_MATERIALS_MAX_SPHERES);
   if (!outside_table(variant) && n_spheres > pt_kernel_max_spheres(variant))
     return pt_fail(PT_ELIMIT, "render: %d spheres exceed the LDS staging limit of %d", n_spheres,
                    pt_kernel_max_spheres(variant));
@@ -541,7 +551,9 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
 // OUTSIDE the event pair of pt_renderer_render so the returned kernel time is not distorted.
 static hipError_t launch(pt_renderer* r, const PixelKernelArgs& a, hipStream_t stream) {
   if (r->launch_variant == PT_VARIANT_FAST) return pt_launch_fast_kernel(a, r->opts.rng_mode, stream);
-  if (r->launch_variant == PT_VARIANT_MATERIALS) return pt_launch_materials_kernel(a, r->d_materials, r->opts.rng_mode, stream);
+  if (r->launch_variant == PT_VARIANT_MATERIALS) return pt_launch_materials_kernel(a, r->d_materials, r->opts.rng_mode, false, stream);
+  if (r->launch_variant == PT_VARIANT_MATERIALS_LIGHTS)
+    return pt_launch_materials_kernel(a, r->d_materials ? r->d_materials : r->d_all_diffuse, r->opts.rng_mode, true, stream);
   return pt_launch_pixel_kernel(a, r->opts.rng_mode, r->launch_variant, stream);
 }
 
@@ -603,6 +615,8 @@ int pt_renderer_enqueue_frames(pt_renderer* r, int n_frames, float* d_out, size_
                                const float* eyes, void* hip_stream) {
   if (!r) return pt_fail(PT_EINVAL, "pt_renderer_enqueue_frames: renderer is NULL");
   if (n_frames < 0 || (n_frames > 0 && (!bases || !eyes))) return pt_fail(PT_EINVAL, "pt_renderer_enqueue_frames: bad arguments");
+  if (r->light_sampling)
+    return pt_fail(PT_EINVAL, "pt_renderer_enqueue_frames: the renderer samples its lights directly (pt_renderer_set_light_sampling); the light-sampling kernel has no frame batches");
   if (n_frames == 0) return PT_OK;
   float* const saved_vertices = r->d_vertices;
   const size_t tile_floats = (size_t)r->tile_pixels * 14u, vtx_floats = (size_t)r->tile_pixels * 3u;
@@ -752,6 +766,8 @@ int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
   variant_list(resume, &VariantInfo::resume);
   if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants %s)", resume);
   if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
+  if (r->light_sampling)
+    return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer samples its lights directly (pt_renderer_set_light_sampling); the light-sampling kernel has no progressive passes");
   if (!r->auto_variant && !pt_kernel_has_resume(r->opts.variant))
     return pt_fail(PT_EINVAL, "pt_progressive_create: kernel variant %d has no progressive passes (resume builds: variants %s)", r->opts.variant, resume);
   pt_progressive* p = new (std::nothrow) pt_progressive();
@@ -827,6 +843,8 @@ static int progressive_args(pt_progressive* p, int spp, float* d_out, const pt_s
                          p->spheres != d_spheres || p->n_spheres != n_spheres))
     return pt_fail(PT_EINVAL, "pt_progressive: camera or scene differs from the session's first pass: reset the session");
   if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
+  if (r->light_sampling)
+    return pt_fail(PT_EINVAL, "pt_progressive: the renderer samples its lights directly (pt_renderer_set_light_sampling); the light-sampling kernel has no progressive passes");
   const int v = session_variant(r, n_spheres);
   if (!pt_kernel_has_resume(v)) return pt_fail(PT_EINVAL, "pt_progressive: kernel variant %d has no progressive passes", v);
   if (n_spheres > pt_kernel_max_spheres(v))
@@ -1137,6 +1155,30 @@ int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int
   return PT_OK;
 }
 
+int pt_renderer_set_light_sampling(pt_renderer* r, int on) {
+  if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: renderer is NULL");
+  if (!on) {
+    r->light_sampling = false;  // the table, if any, stays: PT_VARIANT_MATERIALS with one, the ordinary kernels without
+    return PT_OK;
+  }
+  if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: a fast_math renderer has no light sampling");
+  if (!r->auto_variant)
+    return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: the renderer has an explicit kernel variant (%d); the light-sampling kernel is none of the table's: leave variant at -1", r->opts.variant);
+  if (!r->d_all_diffuse) {  // the table of a renderer without one: every sphere DIFFUSE (kind 0, param 0: zeroed rows)
+    static const unsigned char zeros[PT_MATERIALS_MAX_SPHERES * 16] = {};
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(zeros));
+    if (e == hipSuccess) e = hipMemcpy(d, zeros, sizeof(zeros), hipMemcpyHostToDevice);  // blocking, like set_materials' upload
+    if (e != hipSuccess) {
+      if (d) (void)hipFree(d);
+      return pt_fail(PT_EHIP, "pt_renderer_set_light_sampling: %s", hipGetErrorString(e));
+    }
+    r->d_all_diffuse = d;
+  }
+  r->light_sampling = true;
+  return PT_OK;
+}
+
 int pt_renderer_set_frame(pt_renderer* r, uint32_t frame) {
   if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_frame: renderer is NULL");
   r->frame = frame;
@@ -1169,8 +1211,8 @@ int pt_renderer_kernel_info(pt_renderer* r, int n_spheres, pt_kernel_info* info)
   if (!r || !info) return pt_fail(PT_EINVAL, "pt_renderer_kernel_info: NULL argument");
   hipFuncAttributes fa;
   const int variant = effective_variant(r, n_spheres);
-  if (variant == PT_VARIANT_MATERIALS) {
-    PT_HIP(hipFuncGetAttributes(&fa, pt_materials_kernel_symbol(r->opts.rng_mode)));
+  if (materials_variant(variant)) {
+    PT_HIP(hipFuncGetAttributes(&fa, pt_materials_kernel_symbol(r->opts.rng_mode, variant == PT_VARIANT_MATERIALS_LIGHTS)));
     info->block_threads = PT_BLOCK_THREADS;
     info->grid_blocks = (int)(((uint64_t)r->tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
     info->lds_bytes = (int)pt_materials_kernel_lds_bytes(n_spheres < 0 ? 0 : (n_spheres > PT_MATERIALS_MAX_SPHERES ? PT_MATERIALS_MAX_SPHERES : n_spheres));

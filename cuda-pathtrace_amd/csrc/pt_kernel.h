@@ -312,10 +312,11 @@ size_t pt_fast_kernel_lds_bytes(int n_spheres);
 hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStream_t stream);
 // sphere materials (pt_materials.hip): one kernel family outside the variant table and the launch census.  d_table: one 16-byte
 // row per sphere, formed from a pt_material by pt_materials_device_row
-const void* pt_materials_kernel_symbol(int rng_mode);
+// lights: the build with direct light sampling (pt_renderer_set_light_sampling, PT_VARIANT_MATERIALS_LIGHTS)
+const void* pt_materials_kernel_symbol(int rng_mode, bool lights);
 size_t pt_materials_kernel_lds_bytes(int n_spheres);
 void pt_materials_device_row(const pt_material* m, void* row16);
-hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, hipStream_t stream);
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, hipStream_t stream);
 
 // The launch census (lab library only; include/ptcore_lab.h, pt_debug_launch_census): every launcher of a pixel kernel ends in
 // PT_LAUNCHED(fn, modes) -- the launch's status, and in the lab library a count under the function it handed to

@@ -18,6 +18,15 @@
 // DIFFUSE and GLOSSY, the mirror direction MIRROR, GLOSSY and both reflecting arms of GLASS -- under two wave-uniform skips
 // (no lane of the wave on a non-diffuse sphere; no lane on glass), so a wave that sees only diffuse surfaces runs trace_ray's
 // instructions and nothing else.
+//
+// LIGHTS (pt_renderer_set_light_sampling, PT_VARIANT_MATERIALS_LIGHTS; EXACTNESS.md A.23, tests/lights_model.py): the second template
+// parameter adds direct light sampling, everything of it under `if constexpr (LIGHTS)` -- with LIGHTS = false the instruction stream
+// is the family's as it was.  Per DIFFUSE hit but the last bounce's and per emitting sphere: one direction inside the cone the
+// sphere subtends, one shadow ray by the same search, and a 64-bit set per path of the lights so accounted for, whose emission the
+// next hit leaves out.  The loop over lights is scalar (the list is one ballot over the staged spheres); the shadow search runs
+// with every lane of the bounce loop in step, a lane without a sample following its own next ray with its result dropped, and is
+// skipped when no lane of the wave has a sample.  The shadow ray is unbounded: "the nearest hit is sphere s" is what the search
+// returns.  122 / 127 VGPRs, no scratch: the family's launch bound holds (profiles/lights/README.md).
 #include <cstring>
 
 #include "pt_intersect.h"
@@ -109,16 +118,81 @@ __device__ __forceinline__ Step bounce_step(F3 o, F3 d, float t, F3 centre, floa
   return out;
 }
 
+// ---- direct light sampling (EXACTNESS.md A.23; tests/lights_model.py is the same definition) -------------------------------------
+// the two draws of light j at bounce n, after the bounce's own
+template <int RNG>
+__device__ __forceinline__ void light_draws(Rng<RNG>& rng, int n, int j, uint4& blk, float& u0, float& u1) {
+  if constexpr (RNG == PT_RNG_XORWOW) {
+    u0 = uniform_from_u32(xorwow_next(rng.st));
+    u1 = uniform_from_u32(xorwow_next(rng.st));
+  } else {
+    // counter (pixel, sample, n, 1 + (j >> 1)): the path's own blocks all have word 3 = 0
+    if ((j & 1) == 0) blk = philox4x32_10(make_uint4(rng.pix, rng.sample, (uint32_t)n, 1u + ((uint32_t)j >> 1)), rng.k0, rng.k1);
+    u0 = uniform_from_u32((j & 1) ? blk.z : blk.x);
+    u1 = uniform_from_u32((j & 1) ? blk.w : blk.y);
+  }
+}
+
+struct LightSample {
+  F3 l;          // direction of the shadow ray
+  float cosl;    // dot(l, nl)
+  float factor;  // cosl * (2 * vers) = cosl * Omega / pi
+  bool outside;  // d2 > r2: the point is outside the light (false also for a NaN)
+};
+
+// one sample of the cone the light sphere g = {centre, r * r} subtends at x.  FAST: as in bounce_step
+template <bool FAST>
+__device__ __forceinline__ LightSample light_sample(F3 x, F3 nl, float4 g, float u0, float u1, bool& bad, uint32_t absmask) {
+  LightSample out;
+  auto unit = [&](F3 v) { if constexpr (FAST) return normalize_nb(v, bad); else return normalize(v); };
+  auto root = [&](float v) { if constexpr (FAST) return sqrt_cr_f32_nb(v, bad); else return sqrtf(v); };
+  const F3 sw = mk3(g.x - x.x, g.y - x.y, g.z - x.z);
+  const float d2 = dot(sw, sw);
+  out.outside = d2 > g.w;
+  const float q = g.w / d2;
+  const float cmax = root(1.0f - q);
+  const float vers = q / (1.0f + cmax);  // 1 - cmax without the cancellation a small lamp would suffer
+  const float h = u1 * vers;
+  const float cos_a = 1.0f - h;
+  const float sin_a = root(h * (2.0f - h));
+  // getCosineWeightedNormal's frame (:126-129) around sw
+  const F3 dir = unit(sw);
+  const F3 o1 = unit(ortho_vector(dir));
+  const F3 o2 = unit(cross(dir, o1));
+  const float rx = FAST ? u0 * (2.0f * 3.141592654f) : u0 * 2.0f * 3.141592654f;  // doubling is exact (bounce_geometry)
+  float sn, cs;
+  pt_sincos(rx, sn, cs, absmask);
+  const F3 a = o1 * (cs * sin_a);
+  const F3 b = o2 * (sn * sin_a);
+  const F3 c = dir * cos_a;
+  out.l = unit((a + b) + c);
+  out.cosl = dot(out.l, nl);
+  out.factor = out.cosl * (2.0f * vers);
+  return out;
+}
+
 #ifndef PT_MATERIALS_MIN_WAVES
 #define PT_MATERIALS_MIN_WAVES 4  // <= 128 VGPRs
 #endif
-template <int RNG>
+template <int RNG, bool LIGHTS>  // (the LIGHTS builds hold the same bound: 122 / 127 VGPRs, no scratch)
 __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixel_kernel_materials(PixelKernelArgs a, const Row* __restrict__ table) {
   extern __shared__ float4 lds_scene[];
   // the table is staged beside the scene image: one slot per sphere after the small tables; stage_scene's barrier covers it
   Row* mtab = reinterpret_cast<Row*>(lds_scene + 4 * a.n_spheres + kTablesF4);
   for (int i = threadIdx.x; i < a.n_spheres; i += blockDim.x) mtab[i] = table[i];
   SceneLds sc = stage_scene<false>(a.spheres, a.n_spheres, lds_scene, false, mk3(a.eye[0], a.eye[1], a.eye[2]), a.spp);
+  // the light list: bit i = sphere i emits (any component > 0).  One ballot of the wave over the <= 64 staged spheres, so the
+  // list is wave-uniform and lives in scalar registers; light j is its j-th set bit
+  uint64_t lights = 0ull;
+  if constexpr (LIGHTS) {
+    const int li = threadIdx.x & 63;
+    bool emits = false;
+    if (li < a.n_spheres) {
+      const float4 e = sc.mat0[li];
+      emits = (e.x > 0.0f) | (e.y > 0.0f) | (e.z > 0.0f);
+    }
+    lights = __builtin_amdgcn_ballot_w64(emits);
+  }
 
   const uint32_t tp = blockIdx.x * PT_BLOCK_THREADS + threadIdx.x;
   const bool active = tp < a.tile_pixels;  // lanes past the tile stay for the cooperative parts
@@ -162,6 +236,7 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
     F3 o = eye;
     F3 color = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
     bool escaped = false;
+    uint64_t marked = 0ull;  // LIGHTS: bit i = light sphere i was sampled at the previous hit: its emission there is accounted for
     for (int n = 0; n < a.max_bounces; n++) {  // :155
       float t = 0.0f;
       int idx = 0;
@@ -181,12 +256,49 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
       Step st = bounce_step<true>(o, d, t, centre, u_az, u_el, m, bad, sc.inv1, sc.absmask);
       if (__builtin_expect(bad, 0)) st = bounce_step<false>(o, d, t, centre, u_az, u_el, m, bad, nullptr, sc.absmask);
       const F3 me = mask * emis;
+      F3 lit = color;
       if (n == 0)  // :171-172
-        color = color + mk3(clampf(me.x, 0.0f, 1.0f), clampf(me.y, 0.0f, 1.0f), clampf(me.z, 0.0f, 1.0f));
+        lit = color + mk3(clampf(me.x, 0.0f, 1.0f), clampf(me.y, 0.0f, 1.0f), clampf(me.z, 0.0f, 1.0f));
       else  // :174
-        color = color + me;
+        lit = color + me;
+      if constexpr (LIGHTS) {
+        if (!((marked >> idx) & 1ull)) color = lit;
+      } else {
+        color = lit;
+      }
       mask = mask * scol;  // :175
       mask = mask * st.w;  // GLASS: Re / P or (1 - Re) / (1 - P), after the colour
+      if constexpr (LIGHTS) {
+        marked = 0ull;
+        if (lights != 0ull && n < a.max_bounces - 1) {  // wave-uniform; the last bounce does not sample
+          const bool diffuse = m.kind == PT_MATERIAL_DIFFUSE;
+          uint4 lblk = make_uint4(0u, 0u, 0u, 0u);
+          int j = 0;
+          for (uint64_t rest = lights; rest != 0ull; rest &= rest - 1ull, j++) {  // a scalar loop
+            const int s = __builtin_ctzll(rest);
+            float u0, u1;
+            light_draws<RNG>(rng, n, j, lblk, u0, u1);  // every path that hit something, whatever the kind
+            const float4 lg = sc.geom[s];
+            bool lbad = false;
+            LightSample ls = light_sample<true>(st.o, st.normal, lg, u0, u1, lbad, sc.absmask);
+            bool formed = diffuse & (idx != s) & ls.outside;
+            if (__builtin_amdgcn_ballot_w64(formed) == 0ull) continue;
+            if (__builtin_expect(formed & lbad, 0)) ls = light_sample<false>(st.o, st.normal, lg, u0, u1, lbad, sc.absmask);
+            if (formed) marked |= 1ull << s;  // reached, shadowed or below the horizon: accounted for
+            const bool want = formed & (ls.cosl > 0.0f);
+            if (__builtin_amdgcn_ballot_w64(want) == 0ull) continue;
+            // the same search, the wave converged; a lane without a sample follows its own next ray and its result is dropped
+            const F3 sd = want ? ls.l : st.d;
+            float shadow_t = 0.0f;
+            int shadow_idx = 0;
+            const bool shadow_hit = intersect_scene<6, false, false, false>(sc, a.n_spheres, st.o, sd, shadow_t, shadow_idx);
+            if (want & shadow_hit & (shadow_idx == s)) {
+              const float4 le = sc.mat0[s];
+              color = color + (mask * mk3(le.x, le.y, le.z)) * ls.factor;
+            }
+          }
+        }
+      }
       if (n == 0) {        // :187-195, from nl, the sphere's colour and t
         L.normal = L.normal + st.normal;
         L.albedo = L.albedo + scol;
@@ -243,11 +355,13 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
 
 typedef void (*materials_kernel_fn)(PixelKernelArgs, const pt::materials::Row*);
 
-static materials_kernel_fn select_materials(int rng_mode) {
-  return rng_mode == PT_RNG_PHILOX ? pt::materials::pixel_kernel_materials<PT_RNG_PHILOX> : pt::materials::pixel_kernel_materials<PT_RNG_XORWOW>;
+static materials_kernel_fn select_materials(int rng_mode, bool lights) {
+  using namespace pt::materials;
+  if (lights) return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, true> : pixel_kernel_materials<PT_RNG_XORWOW, true>;
+  return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, false> : pixel_kernel_materials<PT_RNG_XORWOW, false>;
 }
 
-const void* pt_materials_kernel_symbol(int rng_mode) { return (const void*)select_materials(rng_mode); }
+const void* pt_materials_kernel_symbol(int rng_mode, bool lights) { return (const void*)select_materials(rng_mode, lights); }
 
 static uint32_t materials_scene_f4(int n_spheres) { return (uint32_t)n_spheres * 5u + (uint32_t)pt::kTablesF4; }  // scene image, small tables, table
 
@@ -267,11 +381,11 @@ void pt_materials_device_row(const pt_material* m, void* row16) {
   memcpy(row16, &r, sizeof(r));
 }
 
-hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, hipStream_t stream) {
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, hipStream_t stream) {
   PixelKernelArgs b = a;
   b.scene_lds_f4 = materials_scene_f4(a.n_spheres);
   const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
-  hipLaunchKernelGGL(select_materials(rng_mode), dim3(grid), dim3(PT_BLOCK_THREADS), pt_materials_kernel_lds_bytes(a.n_spheres), stream, b,
+  hipLaunchKernelGGL(select_materials(rng_mode, lights), dim3(grid), dim3(PT_BLOCK_THREADS), pt_materials_kernel_lds_bytes(a.n_spheres), stream, b,
                      (const pt::materials::Row*)d_table);
   return hipGetLastError();  // (outside the launch census: no PT_LAUNCHED)
 }

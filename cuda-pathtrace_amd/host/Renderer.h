@@ -42,6 +42,9 @@ class Renderer {
   void SetMaterials(const std::vector<pt_material>& table) {
     gpuErrchk(pt_renderer_set_materials(impl, table.empty() ? NULL : table.data(), (int)table.size()));
   }
+  // Extension (the reference adds emission only where a bounce lands on an emitter): every diffuse hit but the last bounce's
+  // also samples each emitting sphere directly (pt_renderer_set_light_sampling), with or without a material table.
+  void SetLightSampling(bool on) { gpuErrchk(pt_renderer_set_light_sampling(impl, on ? 1 : 0)); }
 
   // Renderer.h:55-76: synchronous, returns kernel-only milliseconds.
   float Render(OutputBuffer d_buffer, const Scene& d_scene, const Camera& camera) {

@@ -31,7 +31,9 @@
 // pass is compared on the device with the colour of REF, an EXR of the same size read by ExrReader.h, after --temporal, --filter
 // and -d and before --tonemap; one "compare:" line per frame or pass),
 // --materials FILE | smallpt (Material.h, pt_renderer_set_materials: a material per sphere -- mirror, glossy, glass -- for the
-// single frame and the headless loop; every stage behind Render() only sees frames.  Not with --progressive, --batch or --gpus).
+// single frame and the headless loop; every stage behind Render() only sees frames.  Not with --progressive, --batch or --gpus),
+// --direct-light (pt_renderer_set_light_sampling: every diffuse hit also samples the emitting spheres; alone or with --materials,
+// in the single frame and the headless loop, every stage behind Render() as before.  Not with --progressive, --batch or --gpus).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -110,6 +112,8 @@ static void usage() {
                "                                (with --temporal every pixel follows the sphere it shows)\n"
                "  --materials arg               file of 'index kind [param]' lines (kind: diffuse | mirror | glossy rho | glass eta), or\n"
                "                                'smallpt': sphere 6 a mirror, sphere 7 glass of index 1.5; unlisted spheres are diffuse\n"
+               "  --direct-light                sample the emitting spheres at every diffuse hit (next-event estimation); alone or with\n"
+               "                                --materials; not with --progressive, --batch or --gpus\n"
                "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
                "  --exposure arg                with --tonemap: auto (default, metered on the device) or a number > 0\n"
                "  --tonemap-key arg             with --tonemap: luminance the metered mean is mapped to (default 0.18)\n"
@@ -134,6 +138,7 @@ int main(int argc, const char** argv) {
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
   std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile, materialsArg;
   bool denoisePrecisionGiven = false;
+  bool directLight = false;  // --direct-light: Renderer::SetLightSampling
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
   int progressive = 0;       // --progressive N: N passes of samplesPerPixel samples into one frame (0 = off)
   bool progressiveGiven = false, framesGiven = false, gpusGiven = false;
@@ -222,6 +227,7 @@ int main(int argc, const char** argv) {
     else if (a == "--poses") posesFile = value("--poses");
     else if (a == "--velocities") velocitiesFile = value("--velocities");
     else if (a == "--materials") materialsArg = value("--materials");
+    else if (a == "--direct-light") directLight = true;
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
     else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
@@ -424,6 +430,14 @@ int main(int argc, const char** argv) {
       return 1;
     }
   }
+  if (directLight) {  // (before any device is touched)
+    const char* other = progressiveGiven ? "--progressive" : batch ? "--batch" : multi ? "--gpus" : NULL;
+    if (other) {
+      std::cerr << "ERROR: --direct-light cannot be combined with " << other
+                << ": the light-sampling kernel renders single frames on one device (no progressive passes, no frame batches)" << std::endl;
+      return 1;
+    }
+  }
   pt_tonemap_opts tonemapOpts;
   pt_tonemap_opts_default(&tonemapOpts);
   if (tonemapOption && !tonemapGiven) {  // (before any device is touched)
@@ -564,6 +578,7 @@ int main(int argc, const char** argv) {
   } else {
     single = new Renderer(width, height, samplesPerPixel, threadsPerBlock, opts);
     if (!materials.empty()) single->SetMaterials(materials);
+    if (directLight) single->SetLightSampling(true);
   }
   // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
   DenoiseNet* net =

@@ -244,6 +244,21 @@ int pt_material_check(const pt_material* table, int n);
  * display vertices of pt_renderer_set_display are supported.  pt_mgpu has no materials. */
 int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int n);
 
+/* ---- direct light sampling (opt-in; csrc/pt_materials.hip, EXACTNESS.md A.23) ----------------- */
+/* Departs from src/pathtrace.cu's emission-only accumulation (:171-174: a path gains light only when a bounce happens to land
+ * on an emitter).  With the option on, every DIFFUSE hit but the last bounce's also draws one direction inside the cone each
+ * emitting sphere subtends, traces a shadow ray, and adds that light's direct contribution; the next hit leaves out the
+ * emission of the lights so accounted for.  The frame's expectation is that of the frame without the option at the same
+ * max_bounces: the noise changes, not the picture.  EXACT code: the frame equals tests/lights_model.py bit for bit.
+ * on != 0: every render / enqueue runs the materials kernel's light-sampling build and pt_renderer_kernel_info reports
+ * PT_VARIANT_MATERIALS_LIGHTS -- with the renderer's material table, or, without one, with every sphere DIFFUSE (a scene above
+ * PT_MATERIALS_MAX_SPHERES is then PT_ELIMIT and nothing is launched).  on == 0: the renderer is exactly what it was
+ * (PT_VARIANT_MATERIALS with a table, the ordinary kernels without).  The order of pt_renderer_set_materials and this call does
+ * not matter.  Refused (PT_EINVAL): a NULL renderer, a fast_math renderer, a renderer with an explicit kernel variant; while it
+ * is on, pt_progressive_create, a session's passes and pt_renderer_enqueue_frames are refused.  pt_mgpu has no light sampling. */
+#define PT_VARIANT_MATERIALS_LIGHTS 102 /* a pseudo-variant like PT_VARIANT_MATERIALS */
+int pt_renderer_set_light_sampling(pt_renderer* r, int on);
+
 /* ---- one frame over several GPUs of one node ------------------------------------------------- */
 /* The reference selects ONE device per process (cudaSetDevice(cudaDevice), src/main.cu:86) and its
  * Renderer covers the whole image with one launch (Renderer.h:29-33,69).  pt_mgpu_* is the same
