@@ -261,6 +261,9 @@ LAB_ABI = {
     "pt_debug_grid_header": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
     "pt_debug_grid_image": (ctypes.c_int, [_vp, ctypes.c_int, _fp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_uint64)]),
+    "pt_debug_primary_masks": (ctypes.c_int, [_vp, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "pt_debug_primary_lists": (ctypes.c_int, [_vp, ctypes.c_int, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              _vp, ctypes.POINTER(ctypes.c_uint32)]),
     "pt_debug_policy_ms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pt_debug_policy_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "pt_debug_renderer_batch_launches": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
@@ -636,7 +639,7 @@ def grid_image(spheres, eye=None, threads=512):
     hdr = {"valid": int(u[0]), "dims": (int(u[1]), int(u[2]), int(u[3])), "origin": (float(f[4]), float(f[5]), float(f[6])),
            "cell_size": float(f[7]), "slack": float(f[9]), "centre": (float(f[10]), float(f[11]), float(f[12])), "far2": float(f[13]),
            "n_big": int(u[14]) & 0xFFFF, "n_entries": int(u[14]) >> 16, "n_items": int(u[15]), "r_small": float(f[16]),
-           "r_big": float(f[17]), "max_entries": int(lay[7])}
+           "r_big": float(f[17]), "prim_base": int(u[18]), "n_emis": int(u[19]), "max_entries": int(lay[7])}
     if not hdr["valid"]:
         return hdr
     ncells = hdr["dims"][0] * hdr["dims"][1] * hdr["dims"][2]
@@ -659,6 +662,85 @@ def grid_image(spheres, eye=None, threads=512):
         pooled.append(np.asarray(got, dtype=np.int64))
     hdr["pooled"] = pooled
     return hdr
+
+
+GUARD_WORDS = 64  # sentinel words on either side of every output of the two dumps below
+_GUARD = 0xA5A5A5A5
+
+
+class _Guarded:
+    """A device output of `words` 32-bit words between two runs of GUARD_WORDS sentinel words, itself filled with the sentinel."""
+
+    def __init__(self, words):
+        self.words = words
+        self.buf = DeviceBuffer(4 * (words + 2 * GUARD_WORDS)).upload(np.full(words + 2 * GUARD_WORDS, _GUARD, dtype=np.uint32))
+        self.ptr = self.buf.ptr + 4 * GUARD_WORDS
+
+    def finish(self, what):
+        """The output words; RuntimeError if a guard word on either side changed."""
+        raw = self.buf.download(np.uint32, (self.words + 2 * GUARD_WORDS,))
+        if (raw[:GUARD_WORDS] != _GUARD).any() or (raw[GUARD_WORDS + self.words:] != _GUARD).any():
+            raise RuntimeError(f"{what}: the guard words around the output were written")
+        return raw[GUARD_WORDS:GUARD_WORDS + self.words].copy()
+
+
+def _primary_dump(spheres, eye, basis, call, outputs):
+    """Shared by primary_masks / primary_lists: upload, call(d_scene, n, eye_c, basis_c, *guarded outputs), check the guards and
+    that the sphere buffer is what was uploaded."""
+    spheres = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+    d_scene, n = upload_scene(spheres)
+    eye_c = (ctypes.c_float * 3)(*[float(np.float32(v)) for v in eye])
+    basis_c = (ctypes.c_float * 12)(*[float(v) for v in np.asarray(basis, dtype=np.float32).reshape(12)])
+    bufs = [_Guarded(w) if w else None for w in outputs]
+    try:
+        check(call(d_scene.ptr, n, eye_c, basis_c, *[b.ptr if b else None for b in bufs]))
+        got = [b.finish(call.__name__) if b else None for b in bufs]
+        if d_scene.download(np.uint8, (spheres.nbytes,)).tobytes() != spheres.tobytes():
+            raise RuntimeError(f"{call.__name__}: the sphere buffer changed")
+        return got
+    finally:
+        d_scene.free()
+        for b in bufs:
+            if b:
+                b.buf.free()
+
+
+def primary_masks(spheres, eye, basis, width, height, row_begin=0, row_end=None, dirs=False):
+    """Lab library: primary_candidates (csrc/pt_footprint.h) per pixel of rows [row_begin, row_end), each lane's own word
+    (pt_debug_primary_masks): uint32 [pixels]; dirs=True: also the five directions each lane used, float32 [pixels][5][3].
+    The outputs lie between guard words and the sphere buffer is read back: RuntimeError if either changed."""
+    row_end = height if row_end is None else row_end
+    px = max(row_end - row_begin, 0) * width
+
+    def pt_debug_primary_masks(d_scene, n, eye_c, basis_c, d_masks, d_dirs):
+        return lib.pt_debug_primary_masks(d_scene, n, eye_c, basis_c, width, height, row_begin, row_end, d_masks, d_dirs)
+
+    masks, d = _primary_dump(spheres, eye, basis, pt_debug_primary_masks, [max(px, 1), 15 * px if dirs else 0])
+    masks = masks[:px]
+    return (masks, d.view(np.float32).reshape(px, 5, 3)) if dirs else masks
+
+
+def primary_lists(spheres, eye, basis, width, height, row_begin=0, row_end=None, threads=512):
+    """Lab library: build_primary_list (csrc/pt_primlist.h) per LANE of workgroups of `threads` lanes over rows [row_begin,
+    row_end) (pt_debug_primary_lists).  Returns (header, lists): header = the grid's 20 header words (word 0 = valid, 16 / 17 the
+    bits of r_small / r_big, 14 & 0xFFFF = spheres outside the grid, 18 = prim_base), lists = uint32 [lanes][6] = {valid, length,
+    e0.x, e0.y, e1.x, e1.y}, lanes = the tile rounded up to `threads`; None when the grid is invalid (nothing was launched: the
+    output must still hold its fill).  Guards and sphere buffer as primary_masks."""
+    row_end = height if row_end is None else row_end
+    px = max(row_end - row_begin, 0) * width
+    lanes = max((px + threads - 1) // threads, 1) * threads
+    header = (ctypes.c_uint32 * 20)()
+
+    def pt_debug_primary_lists(d_scene, n, eye_c, basis_c, d_lists):
+        return lib.pt_debug_primary_lists(d_scene, n, eye_c, basis_c, width, height, row_begin, row_end, threads, d_lists, header)
+
+    (lists,) = _primary_dump(spheres, eye, basis, pt_debug_primary_lists, [6 * lanes])
+    hdr = np.frombuffer(header, dtype=np.uint32).copy()
+    if not hdr[0]:
+        if (lists != _GUARD).any():
+            raise RuntimeError("pt_debug_primary_lists: an invalid grid, yet the output was written")
+        return hdr, None
+    return hdr, lists.reshape(lanes, 6)
 
 
 def upload_scene(spheres):

@@ -175,6 +175,53 @@ extern "C" int pt_debug_grid_image(const pt_sphere* d_spheres, int n_spheres, co
 }
 
 #if PT_BUILD_EXPERIMENTS
+// ---- the two primary-ray exclusion analyses on their own (include/ptcore_lab.h; the kernels: pt_kernel.hip's lab section) --------
+static bool primary_dump_args(PrimaryDumpArgs& a, const pt_sphere* d_spheres, int n, const float* eye, const float* basis, int width,
+                              int height, int row_begin, int row_end) {
+  if (!d_spheres || !eye || !basis || n < 1 || width < 1 || height < 1 || width > 16384 || height > 16384 || row_begin < 0 ||
+      row_end <= row_begin || row_end > height)
+    return false;
+  a.spheres = d_spheres;
+  a.n_spheres = n;
+  for (int k = 0; k < 3; k++) a.eye[k] = eye[k];
+  for (int k = 0; k < 12; k++) a.basis[k] = basis[k];
+  a.width = width;
+  a.height = height;
+  a.row_begin = row_begin;
+  a.tile_pixels = (uint32_t)(row_end - row_begin) * (uint32_t)width;
+  return true;
+}
+
+extern "C" int pt_debug_primary_masks(const pt_sphere* d_spheres, int n_spheres, const float eye[3], const float basis[12], int width,
+                                      int height, int row_begin, int row_end, uint32_t* d_masks, float* d_dirs) {
+  PrimaryDumpArgs a;
+  if (!d_masks || n_spheres > 64 || !primary_dump_args(a, d_spheres, n_spheres, eye, basis, width, height, row_begin, row_end))
+    return pt_fail(PT_EINVAL, "pt_debug_primary_masks: bad arguments (1 .. 64 spheres, rows inside the image)");
+  PT_HIPD(pt_launch_primary_masks_dump(a, d_masks, d_dirs));
+  PT_HIPD(hipDeviceSynchronize());
+  return PT_OK;
+}
+
+extern "C" int pt_debug_primary_lists(const pt_sphere* d_spheres, int n_spheres, const float eye[3], const float basis[12], int width,
+                                      int height, int row_begin, int row_end, int threads, uint32_t* d_lists, uint32_t header_out[20]) {
+  PrimaryDumpArgs a;
+  if (!d_lists || !header_out || (threads != PT_GRID_BLOCK_THREADS && threads != PT_GRID_WIDE_THREADS) ||
+      !primary_dump_args(a, d_spheres, n_spheres, eye, basis, width, height, row_begin, row_end))
+    return pt_fail(PT_EINVAL, "pt_debug_primary_lists: bad arguments (threads 512 or 1024, rows inside the image)");
+  uint32_t* d = nullptr;  // the grid exactly as pt_debug_grid_image builds it
+  PT_HIPD(hipMalloc((void**)&d, pt_kernel_accel_bytes()));
+  hipError_t e = hipMemset(d, 0, pt_kernel_accel_bytes());
+  if (e == hipSuccess) e = pt_launch_build_grid(d_spheres, n_spheres, d, eye, true, nullptr, threads);
+  if (e == hipSuccess) e = hipMemcpy(header_out, d, 20 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && header_out[0] != 0u) {  // (an invalid grid is reported in the header: nothing is launched, no list is written)
+    e = pt_launch_primary_lists_dump(a, d, threads, d_lists);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  (void)hipFree(d);
+  PT_HIPD(e);
+  return PT_OK;
+}
+
 // ---- the adaptive selection and finalize kernels on states the caller builds (include/ptcore_lab.h) ----------------------------
 // Host code only: the launchers are pt_adaptive.hip's own.  Every device array is an allocation of its own, filled with a sentinel
 // before the caller's data goes over its front, and followed by 64 guard words; a guard that changed is reported by name.

@@ -326,6 +326,20 @@ hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_ta
 #include "../../include/ptcore_lab.h"
 hipError_t pt_census_launched(const void* fn, uint32_t modes);  // pt_kernel.hip
 #define PT_LAUNCHED(fn, modes) pt_census_launched((const void*)(fn), (modes))
+// The two primary-ray exclusion analyses on their own (pt_kernel.hip, beside the kernels whose headers they need; the entry
+// points pt_debug_primary_masks / pt_debug_primary_lists are in pt_debug.hip).  masks: one word per tile pixel, dirs (may be
+// null): [pixels][5][3].  lists: six words per LANE of every workgroup (the tile rounded up to `threads`); accel: the grid
+// pt_launch_build_grid made for the same scene, eye and `threads`, and found valid.
+struct PrimaryDumpArgs {
+  const pt_sphere* spheres;
+  int n_spheres;
+  float eye[3];
+  float basis[12];
+  int width, height, row_begin;
+  uint32_t tile_pixels;
+};
+hipError_t pt_launch_primary_masks_dump(const PrimaryDumpArgs& a, uint32_t* masks, float* dirs);
+hipError_t pt_launch_primary_lists_dump(const PrimaryDumpArgs& a, const uint32_t* accel, int threads, uint32_t* lists);
 #else
 #define PT_LAUNCHED(fn, modes) hipGetLastError()
 #endif

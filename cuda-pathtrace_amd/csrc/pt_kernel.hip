@@ -1469,4 +1469,113 @@ extern "C" int pt_debug_launch_census_reset(void) {
   g_unknown_launches.store(0u, std::memory_order_relaxed);
   return PT_OK;
 }
+
+// ---- lab library: the two primary-ray exclusion analyses on their own (pt_debug_primary_masks / pt_debug_primary_lists) -------
+// The pictures say little about them (8-16 random rays per pixel do not notice a footprint radius three times too small), so
+// the tests take each lane's OWN result and hold it to a NumPy model bit for bit (tests/test_primary_exclusion_gpu.py).
+namespace pt {
+
+// A COPY of the pixel kernels' dir_at (pixel_kernel, pixel_kernel_split, pt_fast.hip: a lambda in each).  Moving the lambdas into
+// one functor is not guaranteed to leave the shipped kernels' instruction streams alone, so they stay as they are; what ties this
+// copy to them is the dump's `dirs` output, which the tests compare with the primary-ray formula bit for bit.
+struct PrimaryDirAt {
+  F3 B0, B1, B2, B3;
+  float inv_w, inv_h, fw, fh;
+  bool pow2_image;
+  __device__ __forceinline__ explicit PrimaryDirAt(const PrimaryDumpArgs& a)
+      : B0(mk3(a.basis[0], a.basis[1], a.basis[2])), B1(mk3(a.basis[3], a.basis[4], a.basis[5])),
+        B2(mk3(a.basis[6], a.basis[7], a.basis[8])), B3(mk3(a.basis[9], a.basis[10], a.basis[11])),
+        inv_w(1.0f / (float)a.width), inv_h(1.0f / (float)a.height), fw((float)a.width), fh((float)a.height),
+        pow2_image(((a.width & (a.width - 1)) == 0) && ((a.height & (a.height - 1)) == 0)) {}
+  __device__ __forceinline__ F3 operator()(float sx, float sy) const {
+    if (pow2_image) {
+      sx *= inv_h;
+      sy *= inv_w;
+    } else {
+      sx /= fh;
+      sy /= fw;
+    }
+    return lerp(lerp(B0, B1, sy), lerp(B2, B3, sy), 1.0f - sx);
+  }
+};
+
+// one lane per tile pixel, in the pixel kernels' order; the scene staged as the reference-configuration builds stage it
+__global__ void __launch_bounds__(PT_BLOCK_THREADS) primary_masks_dump_kernel(PrimaryDumpArgs a, uint32_t* __restrict__ masks,
+                                                                              float* __restrict__ dirs) {
+  extern __shared__ float4 lds_scene[];
+  const SceneLds sc = stage_scene<false>(a.spheres, a.n_spheres, lds_scene, false, mk3(a.eye[0], a.eye[1], a.eye[2]), 0);
+  const uint32_t tp = blockIdx.x * PT_BLOCK_THREADS + threadIdx.x;
+  if (tp >= a.tile_pixels) return;  // (after the staging barrier)
+  const int row = a.row_begin + (int)(tp / (uint32_t)a.width);
+  const int col = (int)(tp % (uint32_t)a.width);
+  const PrimaryDirAt dir_at(a);
+  masks[tp] = primary_candidates(sc, a.n_spheres, (float)row, (float)col, dir_at);  // the lane's own word, not the wave's union
+  if (dirs) {
+    float* out = dirs + (size_t)tp * 15;
+    for (int k = 0; k < 5; k++) {  // the centre, then the four corners in the analyses' order
+      const F3 d = k == 0 ? dir_at((float)row, (float)col)
+                          : dir_at((float)row + (((k - 1) & 1) ? 0.5f : -0.5f), (float)col + (((k - 1) & 2) ? 0.5f : -0.5f));
+      out[3 * k] = d.x;
+      out[3 * k + 1] = d.y;
+      out[3 * k + 2] = d.z;
+    }
+  }
+}
+
+// `THREADS` lanes per workgroup with the pooled kernel's LDS layout (the small tables' room, the grid image, a test pool per wave)
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) primary_lists_dump_kernel(PrimaryDumpArgs a, const uint32_t* __restrict__ accel,
+                                                                     uint32_t* __restrict__ lists) {
+  extern __shared__ float4 lds_scene[];
+  float4* image = lds_scene + kTablesF4;
+  const GridLds grid = stage_grid<true>(a.spheres, a.n_spheres, accel, image);
+  if (!grid.valid) return;  // (the host launches only on a valid grid)
+  void* pool = reinterpret_cast<char*>(image) + ((grid_lds_bytes(a.n_spheres, true, THREADS) + 15) & ~(size_t)15);
+  const uint32_t lane_id = blockIdx.x * THREADS + threadIdx.x;
+  const bool active = lane_id < a.tile_pixels;  // lanes past the tile stay for the cooperative parts, as in the pixel kernels
+  const int row = a.row_begin + (int)(lane_id / (uint32_t)a.width);
+  const int col = (int)(lane_id % (uint32_t)a.width);
+  const PrimaryDirAt dir_at(a);
+  int k = 0;
+  const uint32_t slot = grid.h.prim_base + (uint32_t)kPrimEntriesPerLane * threadIdx.x;
+  uint2* cells = const_cast<uint2*>(grid.cells);
+  const bool ok = build_primary_list(grid, a.spheres, a.n_spheres, mk3(a.eye[0], a.eye[1], a.eye[2]), (float)row, (float)col, active,
+                                     dir_at, pool_of_wave(pool).ring, cells, slot, k);
+  const uint2 e0 = cells[slot], e1 = cells[slot + 1u];  // read back from the table, where bounce 0 would find them
+  uint32_t* out = lists + (size_t)lane_id * 6;
+  out[0] = ok ? 1u : 0u;
+  out[1] = (uint32_t)k;
+  out[2] = e0.x;
+  out[3] = e0.y;
+  out[4] = e1.x;
+  out[5] = e1.y;
+}
+
+}  // namespace pt
+
+hipError_t pt_launch_primary_masks_dump(const PrimaryDumpArgs& a, uint32_t* masks, float* dirs) {
+  const size_t lds = ((size_t)a.n_spheres * 4 + pt::kTablesF4) * sizeof(float4);
+  if (a.n_spheres < 1 || a.width < 1 || !a.tile_pixels || lds > 64 * 1024) return hipErrorInvalidValue;
+  const unsigned blocks = (a.tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS;
+  hipLaunchKernelGGL(pt::primary_masks_dump_kernel, dim3(blocks), dim3(PT_BLOCK_THREADS), lds, 0, a, masks, dirs);
+  return hipGetLastError();
+}
+
+hipError_t pt_launch_primary_lists_dump(const PrimaryDumpArgs& a, const uint32_t* accel, int threads, uint32_t* lists) {
+  const bool wide = threads == PT_GRID_WIDE_THREADS;
+  if ((threads != PT_GRID_BLOCK_THREADS && !wide) || a.n_spheres < 1 || a.n_spheres > pt::kGridMaxSpheres || a.width < 1 || !a.tile_pixels)
+    return hipErrorInvalidValue;
+  const size_t lds = pt::kTablesF4 * sizeof(float4) + ((pt::grid_lds_bytes(a.n_spheres, true, threads) + 15) & ~(size_t)15) +
+                     (size_t)(threads / 64) * pt::kPoolWaveBytes;
+  const size_t lds_budget = wide ? (size_t)PT_LDS_WIDE_BUDGET_BYTES : (size_t)PT_LDS_BUDGET_BYTES;
+  if (lds > lds_budget) return hipErrorInvalidValue;
+  const auto fn = wide ? pt::primary_lists_dump_kernel<PT_GRID_WIDE_THREADS> : pt::primary_lists_dump_kernel<PT_GRID_BLOCK_THREADS>;
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget);
+    if (e != hipSuccess) return e;
+  }
+  const unsigned blocks = (a.tile_pixels + (unsigned)threads - 1) / (unsigned)threads;
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(threads), lds, 0, a, accel, lists);
+  return hipGetLastError();
+}
 #endif  // PT_BUILD_EXPERIMENTS

@@ -53,6 +53,22 @@ int pt_debug_grid_header(const pt_sphere* d_spheres, int n_spheres, uint32_t hea
  * for; entries the pooled table may have}.  image_out NULL: only the layout is returned. */
 int pt_debug_grid_image(const pt_sphere* d_spheres, int n_spheres, const float* eye, int threads, uint32_t* image_out,
                         size_t image_bytes, uint64_t layout_out[8]);
+/* The pixel-footprint analysis alone (csrc/pt_footprint.h, primary_candidates): one lane per pixel of rows [row_begin, row_end) in
+ * the pixel kernels' order (tile pixel tp: row = row_begin + tp / width, col = tp % width), the scene (1 .. 64 spheres) staged as
+ * the reference-configuration builds stage it.  d_masks[tp] = the lane's OWN word (bit j = sphere j is kept), not the wave's
+ * union; d_dirs (may be NULL) = the five directions the lane used, [pixels][5][3] floats: the centre, then the corners
+ * (row -+ 0.5, col -+ 0.5) with the row's sign changing fastest.  eye[3] and basis[12] are host arrays, d_* device.  Synchronous. */
+int pt_debug_primary_masks(const pt_sphere* d_spheres, int n_spheres, const float eye[3], const float basis[12], int width, int height,
+                           int row_begin, int row_end, uint32_t* d_masks, float* d_dirs);
+/* The per-pixel primary-ray lists alone (csrc/pt_primlist.h, build_primary_list).  Builds the grid exactly as
+ * pt_debug_grid_image does (eye as the camera hint, `threads` = 512 or 1024) and returns its 20 header words in header_out
+ * (host; word 0 = valid).  On a valid grid, workgroups of `threads` lanes with the pooled kernel's LDS layout each build their
+ * lanes' lists, lane L of the launch = tile pixel L; d_lists gets six words per LANE -- the tile rounded up to a multiple of
+ * `threads`, the lanes past the tile being the inactive ones --: {list valid, length, then the two table entries e0.x, e0.y,
+ * e1.x, e1.y read back from the lane's slots prim_base + 2 * lane-in-workgroup (csrc/pt_grid.h has the entry format)}.  An
+ * invalid grid (header_out[0] == 0) is no error: nothing is launched and d_lists is left alone.  Synchronous. */
+int pt_debug_primary_lists(const pt_sphere* d_spheres, int n_spheres, const float eye[3], const float basis[12], int width, int height,
+                           int row_begin, int row_end, int threads, uint32_t* d_lists, uint32_t header_out[20]);
 /* The automatic policy's cost model (csrc/pt_capi.hip, "which kernel for a small scene"): predicted kernel milliseconds of
  * variant 6, 8 or 9 on a tile of `waves_per_simd` one-lane waves per SIMD at `spp` samples and `bounces` bounces.  Host
  * arithmetic only (no device needed): tests/test_policy_model.py holds it against the measured sweeps under profiles/. */
