@@ -63,6 +63,8 @@ class RendererOpts(ctypes.Structure):
 VARIANT_FAST = 100
 VARIANT_MATERIALS = 101  # PT_VARIANT_MATERIALS: what kernel_info reports while a material table is set
 VARIANT_MATERIALS_LIGHTS = 102  # PT_VARIANT_MATERIALS_LIGHTS: ... while direct light sampling is on (Renderer.set_light_sampling)
+VARIANT_MATERIALS_SKY = 103  # PT_VARIANT_MATERIALS_SKY: ... while a sky is set (Renderer.set_sky)
+VARIANT_MATERIALS_LIGHTS_SKY = 104  # PT_VARIANT_MATERIALS_LIGHTS_SKY: ... a sky and direct light sampling
 LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
 # sphere materials (pt_material, include/ptcore.h; EXACTNESS.md A.22)
 MATERIAL_DIFFUSE, MATERIAL_MIRROR, MATERIAL_GLOSSY, MATERIAL_GLASS = 0, 1, 2, 3
@@ -143,6 +145,8 @@ ABI = {
     "pt_material_check": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pt_renderer_set_materials": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "pt_renderer_set_light_sampling": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "pt_sky_check": (ctypes.c_int, [_vp]),
+    "pt_renderer_set_sky": (ctypes.c_int, [_vp, _vp]),
     "pt_mgpu_opts_default": (None, [ctypes.POINTER(MgpuOpts)]),
     "pt_mgpu_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(RendererOpts), ctypes.POINTER(MgpuOpts), ctypes.POINTER(_vp)]),
@@ -779,6 +783,53 @@ def material_check(materials):
     check(lib.pt_material_check(t.ctypes.data if len(t) else None, len(t)))
 
 
+class PtSky(ctypes.Structure):
+    """pt_sky (include/ptcore.h)."""
+    _fields_ = [("zenith", ctypes.c_float * 3), ("horizon", ctypes.c_float * 3), ("ground", ctypes.c_float * 3),
+                ("sun_dir", ctypes.c_float * 3), ("sun_cos", ctypes.c_float), ("sun_radiance", ctypes.c_float * 3)]
+
+
+class Sky:
+    """A sky and, optionally, a sun (pt_sky, EXACTNESS.md A.24): radiance `zenith` straight up, `horizon` at the horizon, `ground`
+    for every direction below it (world up is +y); a sun of radiance `sun_radiance` wherever the angle to `sun_dir` (towards the
+    sun, any length) has a cosine of at least `sun_cos`.  Without sun_radiance (or all zero) there is no sun."""
+
+    def __init__(self, zenith, horizon, ground, sun_dir=None, sun_cos=None, sun_radiance=None):
+        vec = lambda v: tuple(float(x) for x in ((0.0, 0.0, 0.0) if v is None else v))  # noqa: E731
+        self.zenith, self.horizon, self.ground = vec(zenith), vec(horizon), vec(ground)
+        self.sun_dir, self.sun_radiance = vec(sun_dir), vec(sun_radiance)
+        self.sun_cos = 0.0 if sun_cos is None else float(sun_cos)
+        for name in ("zenith", "horizon", "ground", "sun_dir", "sun_radiance"):
+            if len(getattr(self, name)) != 3:
+                raise ValueError(f"Sky: {name} takes three components")
+
+    def as_struct(self):
+        return PtSky(self.zenith, self.horizon, self.ground, self.sun_dir, self.sun_cos, self.sun_radiance)
+
+    def as_dict(self):
+        """The description as tests/sky_model.py takes it."""
+        return {k: getattr(self, k) for k in ("zenith", "horizon", "ground", "sun_dir", "sun_cos", "sun_radiance")}
+
+    def __repr__(self):
+        return "Sky(%r, %r, %r, sun_dir=%r, sun_cos=%r, sun_radiance=%r)" % (self.zenith, self.horizon, self.ground, self.sun_dir, self.sun_cos,
+                                                                           self.sun_radiance)
+
+
+# a clear day: a blue-to-white gradient, a grey ground and a sun of angular radius 2.56 degrees (cos 0.999, 0.0063 sr) 64 degrees
+# above the horizon whose radiance is 500 to 1000 times the sky's
+CLEAR_SKY = Sky(zenith=(0.18, 0.36, 0.80), horizon=(0.80, 0.85, 0.90), ground=(0.25, 0.25, 0.25), sun_dir=(0.4, 0.8, 0.45), sun_cos=0.999,
+                sun_radiance=(400.0, 380.0, 340.0))
+
+
+def sky_check(sky):
+    """pt_sky_check: the host checks of Renderer.set_sky alone (no device); raises PtError naming the field."""
+    if sky is None:
+        check(lib.pt_sky_check(None))
+        return
+    st = sky.as_struct()
+    check(lib.pt_sky_check(ctypes.addressof(st)))
+
+
 class Renderer(_Session):
     """ctypes view of pt_renderer (the reference's class Renderer, include/Renderer.h)."""
     _destroy = "pt_renderer_destroy"
@@ -852,6 +903,16 @@ class Renderer(_Session):
         emitting sphere (kernel_info: VARIANT_MATERIALS_LIGHTS), with or without a material table.  False: exactly what the
         renderer was before."""
         check(lib.pt_renderer_set_light_sampling(self.handle, 1 if on else 0))
+
+    def set_sky(self, sky):
+        """A Sky (EXACTNESS.md A.24): from now on an escaping path takes the sky's radiance and every frame runs a SKY build of the
+        materials kernel (kernel_info: VARIANT_MATERIALS_SKY, or VARIANT_MATERIALS_LIGHTS_SKY with light sampling, which then
+        samples the sun as its last light), with or without a material table.  None clears it: exactly what the renderer was."""
+        if sky is None:
+            check(lib.pt_renderer_set_sky(self.handle, None))
+            return
+        st = sky.as_struct()
+        check(lib.pt_renderer_set_sky(self.handle, ctypes.addressof(st)))
 
     def set_frame(self, frame):
         check(lib.pt_renderer_set_frame(self.handle, frame))
@@ -1050,16 +1111,18 @@ class MultiRenderer(_Session):
         return buf.value.decode()
 
 
-def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, materials=None, light_sampling=False, **opts):
+def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, materials=None, light_sampling=False, sky=None, **opts):
     """Convenience for tests: allocate, render rows [row_begin,row_end) on the GPU, download.
     Returns (float32 [rows][width][14], kernel_ms).  materials: [(kind, param), ...], one per sphere (Renderer.set_materials);
-    light_sampling: Renderer.set_light_sampling."""
+    light_sampling: Renderer.set_light_sampling; sky: a Sky (Renderer.set_sky)."""
     if spheres is None:
         spheres = scene_cornell()
     if basis is None:
         basis = camera_basis(eye, width=width, height=height)
     if materials is not None:
         material_check(materials)  # before a renderer (a device) exists
+    if sky is not None:
+        sky_check(sky)
     r = Renderer(width, height, spp, **opts)
     d_scene, n = upload_scene(spheres)
     d_out = DeviceBuffer(max(r.tile_floats * 4, 4))
@@ -1068,6 +1131,8 @@ def render_frame(width, height, spp, spheres=None, basis=None, eye=DEFAULT_EYE, 
             r.set_materials(materials)
         if light_sampling:
             r.set_light_sampling(True)
+        if sky is not None:
+            r.set_sky(sky)
         ms = r.render(d_out.ptr, d_scene.ptr, n, basis, eye)
         img = d_out.download(np.float32, (r.rows, width, CHANNELS))
     finally:

@@ -73,10 +73,15 @@ struct pt_renderer {
   // or, without a table, on d_all_diffuse (PT_MATERIALS_MAX_SPHERES zeroed rows: kind DIFFUSE, param 0)
   bool light_sampling = false;
   void* d_all_diffuse = nullptr;
+  // sky and sun (pt_renderer_set_sky): every launch is a SKY build of the materials kernel, on d_materials or d_all_diffuse
+  bool has_sky = false;
+  PtSkyConsts sky = {};
 };
 
 // the kernels outside the variant table (pt_fast.hip, pt_materials.hip): no row to read, no chunking, no frame batches
-static bool materials_variant(int variant) { return variant == PT_VARIANT_MATERIALS || variant == PT_VARIANT_MATERIALS_LIGHTS; }
+static bool lights_variant(int variant) { return variant == PT_VARIANT_MATERIALS_LIGHTS || variant == PT_VARIANT_MATERIALS_LIGHTS_SKY; }
+static bool sky_variant(int variant) { return variant == PT_VARIANT_MATERIALS_SKY || variant == PT_VARIANT_MATERIALS_LIGHTS_SKY; }
+static bool materials_variant(int variant) { return variant == PT_VARIANT_MATERIALS || lights_variant(variant) || sky_variant(variant); }
 static bool outside_table(int variant) { return variant == PT_VARIANT_FAST || materials_variant(variant); }
 
 // the chunk count of the variant's chunk family (0: the variant belongs to none)
@@ -161,6 +166,7 @@ static int cheapest_variant(int rng_mode, double w, int spp, int bounces, bool w
 
 static int effective_variant(pt_renderer* r, int n_spheres) {
   if (r->opts.fast_math) return PT_VARIANT_FAST;
+  if (r->has_sky) return r->light_sampling ? PT_VARIANT_MATERIALS_LIGHTS_SKY : PT_VARIANT_MATERIALS_SKY;  // (pt_renderer_set_sky: as below)
   if (r->light_sampling) return PT_VARIANT_MATERIALS_LIGHTS;  // (never with fast_math or an explicit variant either)
   if (r->d_materials) return PT_VARIANT_MATERIALS;  // (never with fast_math or an explicit variant: pt_renderer_set_materials)
   if (!r->auto_variant) return r->opts.variant;
@@ -509,6 +515,9 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
   if (variant == PT_VARIANT_MATERIALS_LIGHTS && !r->d_materials && n_spheres > PT_MATERIALS_MAX_SPHERES)
     return pt_fail(PT_ELIMIT, "render: %d spheres exceed the %d spheres (PT_MATERIALS_MAX_SPHERES) the light-sampling kernel stages (pt_renderer_set_light_sampling)",
                    n_spheres, PT_MATERIALS_MAX_SPHERES);
+  if (sky_variant(variant) && !r->d_materials && n_spheres > PT_MATERIALS_MAX_SPHERES)
+    return pt_fail(PT_ELIMIT, "render: %d spheres exceed the %d spheres (PT_MATERIALS_MAX_SPHERES) the sky kernel stages (pt_renderer_set_sky)",
+                   n_spheres, PT_MATERIALS_MAX_SPHERES);
   if (!outside_table(variant) && n_spheres > pt_kernel_max_spheres(variant))
     return pt_fail(PT_ELIMIT, "render: %d spheres exceed the LDS staging limit of %d", n_spheres,
                    pt_kernel_max_spheres(variant));
@@ -551,9 +560,10 @@ static int fill_args(pt_renderer* r, float* d_out, const pt_sphere* d_spheres, i
 // OUTSIDE the event pair of pt_renderer_render so the returned kernel time is not distorted.
 static hipError_t launch(pt_renderer* r, const PixelKernelArgs& a, hipStream_t stream) {
   if (r->launch_variant == PT_VARIANT_FAST) return pt_launch_fast_kernel(a, r->opts.rng_mode, stream);
-  if (r->launch_variant == PT_VARIANT_MATERIALS) return pt_launch_materials_kernel(a, r->d_materials, r->opts.rng_mode, false, stream);
-  if (r->launch_variant == PT_VARIANT_MATERIALS_LIGHTS)
-    return pt_launch_materials_kernel(a, r->d_materials ? r->d_materials : r->d_all_diffuse, r->opts.rng_mode, true, stream);
+  if (r->launch_variant == PT_VARIANT_MATERIALS) return pt_launch_materials_kernel(a, r->d_materials, r->opts.rng_mode, false, nullptr, stream);
+  if (materials_variant(r->launch_variant))
+    return pt_launch_materials_kernel(a, r->d_materials ? r->d_materials : r->d_all_diffuse, r->opts.rng_mode, lights_variant(r->launch_variant),
+                                      sky_variant(r->launch_variant) ? &r->sky : nullptr, stream);
   return pt_launch_pixel_kernel(a, r->opts.rng_mode, r->launch_variant, stream);
 }
 
@@ -766,6 +776,7 @@ int pt_progressive_create(pt_renderer* r, pt_progressive** out) {
   variant_list(resume, &VariantInfo::resume);
   if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_progressive_create: a fast_math renderer has no progressive passes (resume builds: variants %s)", resume);
   if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
+  if (r->has_sky) return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer has a sky (pt_renderer_set_sky); the sky kernel has no progressive passes");
   if (r->light_sampling)
     return pt_fail(PT_EINVAL, "pt_progressive_create: the renderer samples its lights directly (pt_renderer_set_light_sampling); the light-sampling kernel has no progressive passes");
   if (!r->auto_variant && !pt_kernel_has_resume(r->opts.variant))
@@ -843,6 +854,7 @@ static int progressive_args(pt_progressive* p, int spp, float* d_out, const pt_s
                          p->spheres != d_spheres || p->n_spheres != n_spheres))
     return pt_fail(PT_EINVAL, "pt_progressive: camera or scene differs from the session's first pass: reset the session");
   if (r->d_materials) return pt_fail(PT_EINVAL, "pt_progressive: the renderer has a material table (pt_renderer_set_materials); the materials kernel has no progressive passes");
+  if (r->has_sky) return pt_fail(PT_EINVAL, "pt_progressive: the renderer has a sky (pt_renderer_set_sky); the sky kernel has no progressive passes");
   if (r->light_sampling)
     return pt_fail(PT_EINVAL, "pt_progressive: the renderer samples its lights directly (pt_renderer_set_light_sampling); the light-sampling kernel has no progressive passes");
   const int v = session_variant(r, n_spheres);
@@ -1155,6 +1167,21 @@ int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int
   return PT_OK;
 }
 
+// the table of a renderer without one: every sphere DIFFUSE (kind 0, param 0: zeroed rows)
+static int ensure_all_diffuse(pt_renderer* r, const char* who) {
+  if (r->d_all_diffuse) return PT_OK;
+  static const unsigned char zeros[PT_MATERIALS_MAX_SPHERES * 16] = {};
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, sizeof(zeros));
+  if (e == hipSuccess) e = hipMemcpy(d, zeros, sizeof(zeros), hipMemcpyHostToDevice);  // blocking, like set_materials' upload
+  if (e != hipSuccess) {
+    if (d) (void)hipFree(d);
+    return pt_fail(PT_EHIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  r->d_all_diffuse = d;
+  return PT_OK;
+}
+
 int pt_renderer_set_light_sampling(pt_renderer* r, int on) {
   if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: renderer is NULL");
   if (!on) {
@@ -1164,18 +1191,53 @@ int pt_renderer_set_light_sampling(pt_renderer* r, int on) {
   if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: a fast_math renderer has no light sampling");
   if (!r->auto_variant)
     return pt_fail(PT_EINVAL, "pt_renderer_set_light_sampling: the renderer has an explicit kernel variant (%d); the light-sampling kernel is none of the table's: leave variant at -1", r->opts.variant);
-  if (!r->d_all_diffuse) {  // the table of a renderer without one: every sphere DIFFUSE (kind 0, param 0: zeroed rows)
-    static const unsigned char zeros[PT_MATERIALS_MAX_SPHERES * 16] = {};
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, sizeof(zeros));
-    if (e == hipSuccess) e = hipMemcpy(d, zeros, sizeof(zeros), hipMemcpyHostToDevice);  // blocking, like set_materials' upload
-    if (e != hipSuccess) {
-      if (d) (void)hipFree(d);
-      return pt_fail(PT_EHIP, "pt_renderer_set_light_sampling: %s", hipGetErrorString(e));
-    }
-    r->d_all_diffuse = d;
-  }
+  const int rc = ensure_all_diffuse(r, "pt_renderer_set_light_sampling");
+  if (rc != PT_OK) return rc;
   r->light_sampling = true;
+  return PT_OK;
+}
+
+// ---- sky and sun (include/ptcore.h; EXACTNESS.md A.24) -------------------------------------------------------------------------
+int pt_sky_check(const pt_sky* sky) {
+  if (!sky) return pt_fail(PT_EINVAL, "pt_sky_check: sky is NULL");
+  const struct { const char* name; const float* v; } rad[4] = {{"zenith", sky->zenith}, {"horizon", sky->horizon}, {"ground", sky->ground},
+                                                                {"sun_radiance", sky->sun_radiance}};
+  for (const auto& f : rad)
+    for (int k = 0; k < 3; k++) {
+      if (!isfinite(f.v[k])) return pt_fail(PT_EINVAL, "pt_sky_check: %s[%d] is not finite", f.name, k);
+      if (f.v[k] < 0.0f) return pt_fail(PT_EINVAL, "pt_sky_check: %s[%d] %g is negative (a radiance)", f.name, k, (double)f.v[k]);
+    }
+  const bool sun = sky->sun_radiance[0] > 0.0f || sky->sun_radiance[1] > 0.0f || sky->sun_radiance[2] > 0.0f;
+  if (!sun) return PT_OK;
+  for (int k = 0; k < 3; k++)
+    if (!isfinite(sky->sun_dir[k])) return pt_fail(PT_EINVAL, "pt_sky_check: sun_dir[%d] is not finite", k);
+  // the length the host normalises by, in float32 as pt_materials_sky_consts forms it: it must be a finite, non-zero number
+  const float len2 = sky->sun_dir[0] * sky->sun_dir[0] + sky->sun_dir[1] * sky->sun_dir[1] + sky->sun_dir[2] * sky->sun_dir[2];
+  if (!(len2 > 0.0f) || !isfinite(len2) || !isfinite(1.0f / sqrtf(len2)))
+    return pt_fail(PT_EINVAL, "pt_sky_check: sun_dir (%g, %g, %g) has no direction (zero length, or a squared length float32 cannot hold)",
+                   (double)sky->sun_dir[0], (double)sky->sun_dir[1], (double)sky->sun_dir[2]);
+  if (!(sky->sun_cos >= 0.0f && sky->sun_cos < 1.0f))
+    return pt_fail(PT_EINVAL, "pt_sky_check: sun_cos %g (the cosine of the sun's angular radius: 0 <= sun_cos < 1)", (double)sky->sun_cos);
+  if (1.0f - sky->sun_cos < 9.5367431640625e-07f)
+    return pt_fail(PT_EINVAL, "pt_sky_check: sun_cos %.9g is too near 1 (1 - sun_cos must be at least 2^-20)", (double)sky->sun_cos);
+  return PT_OK;
+}
+
+int pt_renderer_set_sky(pt_renderer* r, const pt_sky* sky) {
+  if (!r) return pt_fail(PT_EINVAL, "pt_renderer_set_sky: renderer is NULL");
+  if (!sky) {
+    r->has_sky = false;  // the table and light sampling, if any, stay: the renderer is what it was before the sky
+    return PT_OK;
+  }
+  if (r->opts.fast_math) return pt_fail(PT_EINVAL, "pt_renderer_set_sky: a fast_math renderer has no sky");
+  if (!r->auto_variant)
+    return pt_fail(PT_EINVAL, "pt_renderer_set_sky: the renderer has an explicit kernel variant (%d); the sky kernel is none of the table's: leave variant at -1", r->opts.variant);
+  int rc = pt_sky_check(sky);
+  if (rc != PT_OK) return rc;
+  rc = ensure_all_diffuse(r, "pt_renderer_set_sky");
+  if (rc != PT_OK) return rc;
+  pt_materials_sky_consts(sky, &r->sky);  // by value into every launch: a frame in flight keeps the constants it was launched with
+  r->has_sky = true;
   return PT_OK;
 }
 
@@ -1212,7 +1274,7 @@ int pt_renderer_kernel_info(pt_renderer* r, int n_spheres, pt_kernel_info* info)
   hipFuncAttributes fa;
   const int variant = effective_variant(r, n_spheres);
   if (materials_variant(variant)) {
-    PT_HIP(hipFuncGetAttributes(&fa, pt_materials_kernel_symbol(r->opts.rng_mode, variant == PT_VARIANT_MATERIALS_LIGHTS)));
+    PT_HIP(hipFuncGetAttributes(&fa, pt_materials_kernel_symbol(r->opts.rng_mode, lights_variant(variant), sky_variant(variant))));
     info->block_threads = PT_BLOCK_THREADS;
     info->grid_blocks = (int)(((uint64_t)r->tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
     info->lds_bytes = (int)pt_materials_kernel_lds_bytes(n_spheres < 0 ? 0 : (n_spheres > PT_MATERIALS_MAX_SPHERES ? PT_MATERIALS_MAX_SPHERES : n_spheres));

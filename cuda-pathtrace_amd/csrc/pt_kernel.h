@@ -313,10 +313,21 @@ hipError_t pt_launch_fast_kernel(const PixelKernelArgs& a, int rng_mode, hipStre
 // sphere materials (pt_materials.hip): one kernel family outside the variant table and the launch census.  d_table: one 16-byte
 // row per sphere, formed from a pt_material by pt_materials_device_row
 // lights: the build with direct light sampling (pt_renderer_set_light_sampling, PT_VARIANT_MATERIALS_LIGHTS)
-const void* pt_materials_kernel_symbol(int rng_mode, bool lights);
+// sky: the build with a sky and a sun (pt_renderer_set_sky, PT_VARIANT_MATERIALS_SKY / PT_VARIANT_MATERIALS_LIGHTS_SKY; EXACTNESS.md A.24)
+struct PtSkyConsts {  // what pt_materials_sky_consts forms from a pt_sky; a kernel argument by value
+  float horizon[3], slope[3], ground[3];       // slope = zenith - horizon
+  float sun_dir[3], sun_o1[3], sun_o2[3];      // the unit direction towards the sun and getCosineWeightedNormal's frame around it
+  float sun_cos, sun_vers;                     // sun_vers = 1 - sun_cos
+  float sun_radiance[3];
+  int32_t has_sun;                             // any sun_radiance component > 0
+};
+const void* pt_materials_kernel_symbol(int rng_mode, bool lights, bool sky);
 size_t pt_materials_kernel_lds_bytes(int n_spheres);
 void pt_materials_device_row(const pt_material* m, void* row16);
-hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, hipStream_t stream);
+void pt_materials_sky_consts(const pt_sky* s, PtSkyConsts* out);
+// sky: NULL = the builds without one
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, const PtSkyConsts* sky,
+                                      hipStream_t stream);
 
 // The launch census (lab library only; include/ptcore_lab.h, pt_debug_launch_census): every launcher of a pixel kernel ends in
 // PT_LAUNCHED(fn, modes) -- the launch's status, and in the lab library a count under the function it handed to

@@ -27,6 +27,14 @@
 // with every lane of the bounce loop in step, a lane without a sample following its own next ray with its result dropped, and is
 // skipped when no lane of the wave has a sample.  The shadow ray is unbounded: "the nearest hit is sphere s" is what the search
 // returns.  122 / 127 VGPRs, no scratch: the family's launch bound holds (profiles/lights/README.md).
+//
+// SKY (pt_renderer_set_sky, PT_VARIANT_MATERIALS_SKY / PT_VARIANT_MATERIALS_LIGHTS_SKY; EXACTNESS.md A.24, tests/sky_model.py): the
+// third template parameter gives an escaping path the radiance of a sky -- a gradient over u.y, a ground colour, a sun disc --
+// everything of it under `if constexpr (SKY)`, and a build without it keeps its arguments and its instruction stream
+// (tools/sky_asm_diff.py).  The sky's constants are a kernel argument by value: wave-uniform, in scalar registers.  With LIGHTS the
+// sun is the last light of the list: light_sample's sequence from the polar angle on (cone_polar, cone_direction) around a
+// direction and a frame the host formed, one shadow ray with the wave converged, lit iff the search finds nothing, and a flag per
+// path that keeps the next escape from counting the disc again.  118 / 119 / 122 / 127 VGPRs, no scratch (profiles/sky/README.md).
 #include <cstring>
 
 #include "pt_intersect.h"
@@ -140,6 +148,31 @@ struct LightSample {
   bool outside;  // d2 > r2: the point is outside the light (false also for a NaN)
 };
 
+// the tail of a cone sample, shared by the sphere lights (A.23) and the sun (A.24): the polar angle's cosine and sine from u1 and
+// vers = 1 - cos(a_max) ...
+template <bool FAST>
+__device__ __forceinline__ void cone_polar(float u1, float vers, float& cos_a, float& sin_a, bool& bad) {
+  const float h = u1 * vers;
+  cos_a = 1.0f - h;
+  if constexpr (FAST) sin_a = sqrt_cr_f32_nb(h * (2.0f - h), bad); else sin_a = sqrtf(h * (2.0f - h));
+}
+// ... and the direction in getCosineWeightedNormal's frame (dir, o1, o2) at the azimuth of u0, with its cosine to nl and the
+// factor cosl * (2 * vers) = cosl * Omega / pi
+template <bool FAST>
+__device__ __forceinline__ void cone_direction(LightSample& out, F3 dir, F3 o1, F3 o2, float cos_a, float sin_a, float vers, float u0, F3 nl, bool& bad,
+                                               uint32_t absmask) {
+  const float rx = FAST ? u0 * (2.0f * 3.141592654f) : u0 * 2.0f * 3.141592654f;  // doubling is exact (bounce_geometry)
+  float sn, cs;
+  pt_sincos(rx, sn, cs, absmask);
+  const F3 a = o1 * (cs * sin_a);
+  const F3 b = o2 * (sn * sin_a);
+  const F3 c = dir * cos_a;
+  const F3 sum = (a + b) + c;
+  if constexpr (FAST) out.l = normalize_nb(sum, bad); else out.l = normalize(sum);
+  out.cosl = dot(out.l, nl);
+  out.factor = out.cosl * (2.0f * vers);
+}
+
 // one sample of the cone the light sphere g = {centre, r * r} subtends at x.  FAST: as in bounce_step
 template <bool FAST>
 __device__ __forceinline__ LightSample light_sample(F3 x, F3 nl, float4 g, float u0, float u1, bool& bad, uint32_t absmask) {
@@ -152,30 +185,60 @@ __device__ __forceinline__ LightSample light_sample(F3 x, F3 nl, float4 g, float
   const float q = g.w / d2;
   const float cmax = root(1.0f - q);
   const float vers = q / (1.0f + cmax);  // 1 - cmax without the cancellation a small lamp would suffer
-  const float h = u1 * vers;
-  const float cos_a = 1.0f - h;
-  const float sin_a = root(h * (2.0f - h));
+  float cos_a, sin_a;
+  cone_polar<FAST>(u1, vers, cos_a, sin_a, bad);
   // getCosineWeightedNormal's frame (:126-129) around sw
   const F3 dir = unit(sw);
   const F3 o1 = unit(ortho_vector(dir));
   const F3 o2 = unit(cross(dir, o1));
-  const float rx = FAST ? u0 * (2.0f * 3.141592654f) : u0 * 2.0f * 3.141592654f;  // doubling is exact (bounce_geometry)
-  float sn, cs;
-  pt_sincos(rx, sn, cs, absmask);
-  const F3 a = o1 * (cs * sin_a);
-  const F3 b = o2 * (sn * sin_a);
-  const F3 c = dir * cos_a;
-  out.l = unit((a + b) + c);
-  out.cosl = dot(out.l, nl);
-  out.factor = out.cosl * (2.0f * vers);
+  cone_direction<FAST>(out, dir, o1, o2, cos_a, sin_a, vers, u0, nl, bad, absmask);
   return out;
+}
+
+// the sun (EXACTNESS.md A.24): the cone is given, not derived -- the unit direction towards the sun, the frame (o1, o2) the host
+// formed around it and vers = 1 - sun_cos; from the polar angle on it is the sphere light's sequence
+template <bool FAST>
+__device__ __forceinline__ LightSample sun_sample(F3 nl, F3 dir, F3 o1, F3 o2, float vers, float u0, float u1, bool& bad, uint32_t absmask) {
+  LightSample out;
+  out.outside = true;  // the sun is nowhere
+  float cos_a, sin_a;
+  cone_polar<FAST>(u1, vers, cos_a, sin_a, bad);
+  cone_direction<FAST>(out, dir, o1, o2, cos_a, sin_a, vers, u0, nl, bad, absmask);
+  return out;
+}
+
+// ---- sky and sun (EXACTNESS.md A.24; tests/sky_model.py is the same definition) -------------------------------------------------
+// the radiance an escaping path takes along the unit direction u.  sunned: the previous hit sampled the sun (LIGHTS), so the
+// disc is accounted for and the path takes the gradient alone
+__device__ __forceinline__ F3 sky_radiance(const PtSkyConsts& sky, F3 u, bool sunned) {
+  const F3 grad = mk3(sky.horizon[0] + sky.slope[0] * u.y, sky.horizon[1] + sky.slope[1] * u.y, sky.horizon[2] + sky.slope[2] * u.y);
+  F3 rad = u.y >= 0.0f ? grad : mk3(sky.ground[0], sky.ground[1], sky.ground[2]);  // (a NaN takes the ground)
+  if (sky.has_sun) {  // wave-uniform
+    const bool inside = dot(u, mk3(sky.sun_dir[0], sky.sun_dir[1], sky.sun_dir[2])) >= sky.sun_cos;
+    const F3 with_sun = rad + mk3(sky.sun_radiance[0], sky.sun_radiance[1], sky.sun_radiance[2]);
+    if (inside & !sunned) rad = with_sun;
+  }
+  return rad;
 }
 
 #ifndef PT_MATERIALS_MIN_WAVES
 #define PT_MATERIALS_MIN_WAVES 4  // <= 128 VGPRs
 #endif
-template <int RNG, bool LIGHTS>  // (the LIGHTS builds hold the same bound: 122 / 127 VGPRs, no scratch)
-__global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixel_kernel_materials(PixelKernelArgs a, const Row* __restrict__ table) {
+#ifndef PT_MATERIALS_SKY_MIN_WAVES
+#define PT_MATERIALS_SKY_MIN_WAVES 4  // the SKY builds' own bound: they fit the family's without scratch (profiles/sky/README.md)
+#endif
+// SKY = true takes the sky's constants by value as its third argument (wave-uniform: they are read into scalar registers);
+// SKY = false takes the two arguments it always took -- an unused third one would move the hidden arguments that follow the
+// explicit ones, and with them an offset inside the instruction stream -- so the third argument is a pack of one or of none
+struct NoSky {};
+__device__ __forceinline__ NoSky sky_argument() { return NoSky{}; }
+__device__ __forceinline__ const PtSkyConsts& sky_argument(const PtSkyConsts& s) { return s; }
+
+template <int RNG, bool LIGHTS, bool SKY, typename... SKY_CONSTS>  // (the LIGHTS builds hold the same bound: 122 / 127 VGPRs, no scratch)
+__global__ void __launch_bounds__(PT_BLOCK_THREADS, SKY ? PT_MATERIALS_SKY_MIN_WAVES : PT_MATERIALS_MIN_WAVES)
+pixel_kernel_materials(PixelKernelArgs a, const Row* __restrict__ table, SKY_CONSTS... sky_consts) {
+  static_assert(sizeof...(SKY_CONSTS) == (SKY ? 1 : 0), "a SKY build takes one PtSkyConsts, the others nothing");
+  const auto& sky = sky_argument(sky_consts...);
   extern __shared__ float4 lds_scene[];
   // the table is staged beside the scene image: one slot per sphere after the small tables; stage_scene's barrier covers it
   Row* mtab = reinterpret_cast<Row*>(lds_scene + 4 * a.n_spheres + kTablesF4);
@@ -237,11 +300,19 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
     F3 color = mk3(0.0f, 0.0f, 0.0f), mask = mk3(1.0f, 1.0f, 1.0f);
     bool escaped = false;
     uint64_t marked = 0ull;  // LIGHTS: bit i = light sphere i was sampled at the previous hit: its emission there is accounted for
+    bool sunned = false;     // LIGHTS and SKY: the sun was sampled at the previous hit: an escape now takes the gradient alone
     for (int n = 0; n < a.max_bounces; n++) {  // :155
       float t = 0.0f;
       int idx = 0;
       if (!intersect_scene<6, false, false, false>(sc, a.n_spheres, o, d, t, idx)) {  // :157-161
         escaped = true;
+        if constexpr (SKY) {  // the path takes the sky's radiance; a primary ray is not of unit length
+          const F3 mr = mask * sky_radiance(sky, n == 0 ? normalize(d) : d, sunned);
+          if (n == 0)  // :171-172, applied to the sky as to an emitter seen directly
+            color = color + mk3(clampf(mr.x, 0.0f, 1.0f), clampf(mr.y, 0.0f, 1.0f), clampf(mr.z, 0.0f, 1.0f));
+          else
+            color = color + mr;
+        }
         break;
       }
       const float4 g = sc.geom_lane(idx);
@@ -270,7 +341,12 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
       mask = mask * st.w;  // GLASS: Re / P or (1 - Re) / (1 - P), after the colour
       if constexpr (LIGHTS) {
         marked = 0ull;
-        if (lights != 0ull && n < a.max_bounces - 1) {  // wave-uniform; the last bounce does not sample
+        bool sun_light = false;  // the sun is the LAST light of the list
+        if constexpr (SKY) {
+          sunned = false;
+          sun_light = sky.has_sun != 0;
+        }
+        if ((lights != 0ull || sun_light) && n < a.max_bounces - 1) {  // wave-uniform; the last bounce does not sample
           const bool diffuse = m.kind == PT_MATERIAL_DIFFUSE;
           uint4 lblk = make_uint4(0u, 0u, 0u, 0u);
           int j = 0;
@@ -297,6 +373,30 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
               color = color + (mask * mk3(le.x, le.y, le.z)) * ls.factor;
             }
           }
+          if constexpr (SKY) {
+            if (sun_light) {  // wave-uniform
+              float u0, u1;
+              light_draws<RNG>(rng, n, j, lblk, u0, u1);  // light j = the number of emitting spheres
+              if (__builtin_amdgcn_ballot_w64(diffuse) != 0ull) {
+                const F3 sdir = mk3(sky.sun_dir[0], sky.sun_dir[1], sky.sun_dir[2]);
+                const F3 s1 = mk3(sky.sun_o1[0], sky.sun_o1[1], sky.sun_o1[2]), s2 = mk3(sky.sun_o2[0], sky.sun_o2[1], sky.sun_o2[2]);
+                bool sbad = false;
+                LightSample ls = sun_sample<true>(st.normal, sdir, s1, s2, sky.sun_vers, u0, u1, sbad, sc.absmask);
+                if (__builtin_expect(diffuse & sbad, 0)) ls = sun_sample<false>(st.normal, sdir, s1, s2, sky.sun_vers, u0, u1, sbad, sc.absmask);
+                sunned = diffuse;  // lit, shadowed or below the horizon: accounted for
+                const bool want = diffuse & (ls.cosl > 0.0f);
+                if (__builtin_amdgcn_ballot_w64(want) != 0ull) {
+                  // the same search, the wave converged, as for a sphere light; lit iff it finds nothing
+                  const F3 sd = want ? ls.l : st.d;
+                  float shadow_t = 0.0f;
+                  int shadow_idx = 0;
+                  const bool shadow_hit = intersect_scene<6, false, false, false>(sc, a.n_spheres, st.o, sd, shadow_t, shadow_idx);
+                  if (want & !shadow_hit)
+                    color = color + (mask * mk3(sky.sun_radiance[0], sky.sun_radiance[1], sky.sun_radiance[2])) * ls.factor;
+                }
+              }
+            }
+          }
         }
       }
       if (n == 0) {        // :187-195, from nl, the sphere's colour and t
@@ -309,7 +409,8 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
       d = st.d;
     }
     L.color = L.color + color;  // :159 / :198
-    if (!escaped) welford_update(var[0], luminance(color), sc.rcpn);  // :200
+    // :200 -- and the decision of A.24: under a sky the escaped paths carry light, so EVERY sample counts
+    if (SKY || !escaped) welford_update(var[0], luminance(color), sc.rcpn);
   }
 
   float px[14];
@@ -354,14 +455,23 @@ __global__ void __launch_bounds__(PT_BLOCK_THREADS, PT_MATERIALS_MIN_WAVES) pixe
 }  // namespace pt
 
 typedef void (*materials_kernel_fn)(PixelKernelArgs, const pt::materials::Row*);
+typedef void (*materials_sky_kernel_fn)(PixelKernelArgs, const pt::materials::Row*, PtSkyConsts);
 
 static materials_kernel_fn select_materials(int rng_mode, bool lights) {
   using namespace pt::materials;
-  if (lights) return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, true> : pixel_kernel_materials<PT_RNG_XORWOW, true>;
-  return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, false> : pixel_kernel_materials<PT_RNG_XORWOW, false>;
+  if (lights) return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, true, false> : pixel_kernel_materials<PT_RNG_XORWOW, true, false>;
+  return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, false, false> : pixel_kernel_materials<PT_RNG_XORWOW, false, false>;
 }
 
-const void* pt_materials_kernel_symbol(int rng_mode, bool lights) { return (const void*)select_materials(rng_mode, lights); }
+static materials_sky_kernel_fn select_materials_sky(int rng_mode, bool lights) {
+  using namespace pt::materials;
+  if (lights) return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, true, true, PtSkyConsts> : pixel_kernel_materials<PT_RNG_XORWOW, true, true, PtSkyConsts>;
+  return rng_mode == PT_RNG_PHILOX ? pixel_kernel_materials<PT_RNG_PHILOX, false, true, PtSkyConsts> : pixel_kernel_materials<PT_RNG_XORWOW, false, true, PtSkyConsts>;
+}
+
+const void* pt_materials_kernel_symbol(int rng_mode, bool lights, bool sky) {
+  return sky ? (const void*)select_materials_sky(rng_mode, lights) : (const void*)select_materials(rng_mode, lights);
+}
 
 static uint32_t materials_scene_f4(int n_spheres) { return (uint32_t)n_spheres * 5u + (uint32_t)pt::kTablesF4; }  // scene image, small tables, table
 
@@ -381,10 +491,47 @@ void pt_materials_device_row(const pt_material* m, void* row16) {
   memcpy(row16, &r, sizeof(r));
 }
 
-hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, hipStream_t stream) {
+// the sky's constants as the kernel reads them (EXACTNESS.md A.24): slope = zenith - horizon; with a sun the unit direction
+// v * (1 / sqrt(dot(v, v))), getCosineWeightedNormal's frame around it and vers = 1 - sun_cos -- float32, one rounding per operation
+void pt_materials_sky_consts(const pt_sky* s, PtSkyConsts* out) {
+  PtSkyConsts c;
+  memset(&c, 0, sizeof(c));
+  for (int k = 0; k < 3; k++) {
+    c.horizon[k] = s->horizon[k];
+    c.slope[k] = s->zenith[k] - s->horizon[k];
+    c.ground[k] = s->ground[k];
+    c.sun_radiance[k] = s->sun_radiance[k];
+  }
+  c.has_sun = (s->sun_radiance[0] > 0.0f) | (s->sun_radiance[1] > 0.0f) | (s->sun_radiance[2] > 0.0f);
+  if (c.has_sun) {
+    auto unit = [](const float* v, float* o) {
+      const float inv = 1.0f / sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      for (int k = 0; k < 3; k++) o[k] = v[k] * inv;
+    };
+    unit(s->sun_dir, c.sun_dir);
+    const float* d = c.sun_dir;
+    const float zero = 0.0f;
+    const float ortho[3] = {fabsf(d[0]) > fabsf(d[2]) ? -d[1] : zero, fabsf(d[0]) > fabsf(d[2]) ? d[0] : -d[2], fabsf(d[0]) > fabsf(d[2]) ? zero : d[1]};
+    unit(ortho, c.sun_o1);
+    const float* p = c.sun_o1;
+    const float cr[3] = {d[1] * p[2] - d[2] * p[1], d[2] * p[0] - d[0] * p[2], d[0] * p[1] - d[1] * p[0]};
+    unit(cr, c.sun_o2);
+    c.sun_cos = s->sun_cos;
+    c.sun_vers = 1.0f - s->sun_cos;
+  }
+  *out = c;
+}
+
+hipError_t pt_launch_materials_kernel(const PixelKernelArgs& a, const void* d_table, int rng_mode, bool lights, const PtSkyConsts* sky,
+                                      hipStream_t stream) {
   PixelKernelArgs b = a;
   b.scene_lds_f4 = materials_scene_f4(a.n_spheres);
   const unsigned grid = (unsigned)(((uint64_t)a.tile_pixels + PT_BLOCK_THREADS - 1) / PT_BLOCK_THREADS);
+  if (sky) {
+    hipLaunchKernelGGL(select_materials_sky(rng_mode, lights), dim3(grid), dim3(PT_BLOCK_THREADS), pt_materials_kernel_lds_bytes(a.n_spheres), stream,
+                       b, (const pt::materials::Row*)d_table, *sky);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(select_materials(rng_mode, lights), dim3(grid), dim3(PT_BLOCK_THREADS), pt_materials_kernel_lds_bytes(a.n_spheres), stream, b,
                      (const pt::materials::Row*)d_table);
   return hipGetLastError();  // (outside the launch census: no PT_LAUNCHED)

@@ -45,6 +45,9 @@ class Renderer {
   // Extension (the reference adds emission only where a bounce lands on an emitter): every diffuse hit but the last bounce's
   // also samples each emitting sphere directly (pt_renderer_set_light_sampling), with or without a material table.
   void SetLightSampling(bool on) { gpuErrchk(pt_renderer_set_light_sampling(impl, on ? 1 : 0)); }
+  // Extension (the reference returns nothing for a ray that leaves the scene, :157-161): such a ray takes the radiance of a sky
+  // (Sky.h, pt_renderer_set_sky), and with SetLightSampling the sun is sampled like a lamp.  NULL: the renderer as it was.
+  void SetSky(const pt_sky* sky) { gpuErrchk(pt_renderer_set_sky(impl, sky)); }
 
   // Renderer.h:55-76: synchronous, returns kernel-only milliseconds.
   float Render(OutputBuffer d_buffer, const Scene& d_scene, const Camera& camera) {

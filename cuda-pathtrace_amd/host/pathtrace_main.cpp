@@ -33,7 +33,10 @@
 // --materials FILE | smallpt (Material.h, pt_renderer_set_materials: a material per sphere -- mirror, glossy, glass -- for the
 // single frame and the headless loop; every stage behind Render() only sees frames.  Not with --progressive, --batch or --gpus),
 // --direct-light (pt_renderer_set_light_sampling: every diffuse hit also samples the emitting spheres; alone or with --materials,
-// in the single frame and the headless loop, every stage behind Render() as before.  Not with --progressive, --batch or --gpus).
+// in the single frame and the headless loop, every stage behind Render() as before.  Not with --progressive, --batch or --gpus),
+// --sky FILE | clear (Sky.h, pt_renderer_set_sky: a ray that leaves the scene takes a sky's radiance, and with --direct-light the
+// sun is sampled like a lamp; alone or with --materials and --direct-light, in the single frame and the headless loop, every stage
+// behind Render() as before.  Not with --progressive, --batch or --gpus).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -53,6 +56,7 @@
 #include "FeatureFilter.h"
 #include "FrameCompare.h"
 #include "Material.h"
+#include "Sky.h"
 #include "MultiRenderer.h"
 #include "OutputBuffer.h"
 #include "ProgressiveRenderer.h"
@@ -114,6 +118,9 @@ static void usage() {
                "                                'smallpt': sphere 6 a mirror, sphere 7 glass of index 1.5; unlisted spheres are diffuse\n"
                "  --direct-light                sample the emitting spheres at every diffuse hit (next-event estimation); alone or with\n"
                "                                --materials; not with --progressive, --batch or --gpus\n"
+               "  --sky arg                     file of 'zenith r g b', 'horizon r g b', 'ground r g b', 'sun dx dy dz cos r g b' lines, or\n"
+               "                                'clear': a clear day; rays that leave the scene take the sky's light, and --direct-light\n"
+               "                                samples the sun; not with --progressive, --batch or --gpus\n"
                "  --tonemap arg                 clamp | reinhard | aces: also write the tone-mapped picture <output>_tm.ppm\n"
                "  --exposure arg                with --tonemap: auto (default, metered on the device) or a number > 0\n"
                "  --tonemap-key arg             with --tonemap: luminance the metered mean is mapped to (default 0.18)\n"
@@ -136,7 +143,7 @@ int main(int argc, const char** argv) {
   std::string outputName = "output/out";
   std::string rng = "xorwow";
   int maxBounces = 5, nSpheres = 0, frames = 1, gpus = 1;
-  std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile, materialsArg;
+  std::string posesFile, previewFile, denoiseWeights, denoisePrecision, velocitiesFile, materialsArg, skyArg;
   bool denoisePrecisionGiven = false;
   bool directLight = false;  // --direct-light: Renderer::SetLightSampling
   bool batch = false;        // --poses: all frames in one call (one launch per 32 frames)
@@ -228,6 +235,7 @@ int main(int argc, const char** argv) {
     else if (a == "--velocities") velocitiesFile = value("--velocities");
     else if (a == "--materials") materialsArg = value("--materials");
     else if (a == "--direct-light") directLight = true;
+    else if (a == "--sky") skyArg = value("--sky");
     else if (a == "--batch") batch = true;
     else if (a == "--preview") previewFile = value("--preview");
     else if (a == "--denoise-weights") denoiseWeights = value("--denoise-weights");
@@ -438,6 +446,21 @@ int main(int argc, const char** argv) {
       return 1;
     }
   }
+  // --sky: the description on the host, checked by the library's own host checks (before any device is touched)
+  Sky sky = ClearSky();
+  if (!skyArg.empty()) {
+    const char* other = progressiveGiven ? "--progressive" : batch ? "--batch" : multi ? "--gpus" : NULL;
+    if (other) {
+      std::cerr << "ERROR: --sky cannot be combined with " << other
+                << ": the sky kernel renders single frames on one device (no progressive passes, no frame batches)" << std::endl;
+      return 1;
+    }
+    std::string why;
+    if (skyArg != "clear" && !ParseSky(skyArg, sky, why)) {
+      std::cerr << "ERROR: --sky: " << why << std::endl;
+      return 1;
+    }
+  }
   pt_tonemap_opts tonemapOpts;
   pt_tonemap_opts_default(&tonemapOpts);
   if (tonemapOption && !tonemapGiven) {  // (before any device is touched)
@@ -579,6 +602,7 @@ int main(int argc, const char** argv) {
     single = new Renderer(width, height, samplesPerPixel, threadsPerBlock, opts);
     if (!materials.empty()) single->SetMaterials(materials);
     if (directLight) single->SetLightSampling(true);
+    if (!skyArg.empty()) single->SetSky(&sky);
   }
   // -d: the network for this frame size on the first device (after a multi-GPU frame's gather the frame lives there)
   DenoiseNet* net =

@@ -259,6 +259,38 @@ int pt_renderer_set_materials(pt_renderer* r, const pt_material* host_table, int
 #define PT_VARIANT_MATERIALS_LIGHTS 102 /* a pseudo-variant like PT_VARIANT_MATERIALS */
 int pt_renderer_set_light_sampling(pt_renderer* r, int on);
 
+/* ---- sky and sun (opt-in; csrc/pt_materials.hip, EXACTNESS.md A.24) --------------------------- */
+/* Departs from src/pathtrace.cu:157-161, where a ray that leaves the scene returns nothing.  With a sky set, an escaping path
+ * takes the radiance of its direction u (world up is +y): horizon + (zenith - horizon) * u.y where u.y >= 0, ground elsewhere,
+ * plus sun_radiance where dot(u, sun_dir) >= sun_cos.  A primary ray's sky is clamped to [0, 1] per component like an emitter
+ * seen directly (:171-172); the first-hit features of such a sample stay zero; every sample, escaped or not, enters the colour
+ * variance.  With pt_renderer_set_light_sampling on, the sun is the last light of A.23's list: one direction inside its cone
+ * and one shadow ray per DIFFUSE hit but the last bounce's, lit iff the ray leaves the scene, and the escape that follows takes
+ * the gradient without the disc.  EXACT code: the frame equals tests/sky_model.py bit for bit. */
+typedef struct pt_sky {
+  float zenith[3];       /* radiance straight up */
+  float horizon[3];      /* radiance at the horizon */
+  float ground[3];       /* radiance of every direction with u.y < 0 */
+  float sun_dir[3];      /* direction TOWARDS the sun, any length: normalised on the host in float32 */
+  float sun_cos;         /* cosine of the sun's angular radius */
+  float sun_radiance[3]; /* radiance of the disc; all zero: no sun, and sun_dir / sun_cos are not read */
+} pt_sky;
+#define PT_VARIANT_MATERIALS_SKY 103        /* pseudo-variants like PT_VARIANT_MATERIALS: a sky is set, ... */
+#define PT_VARIANT_MATERIALS_LIGHTS_SKY 104 /* ... and direct light sampling is on */
+/* The host checks of pt_renderer_set_sky alone (no device, no renderer): PT_EINVAL naming the field for a NULL pointer; a
+ * radiance component (zenith, horizon, ground, sun_radiance) that is not finite or is negative; with a sun (a sun_radiance
+ * component > 0) a sun_dir that is not finite or of zero length, a sun_cos outside [0, 1) or with 1 - sun_cos < 2^-20. */
+int pt_sky_check(const pt_sky* sky);
+/* Copies the description; NULL clears it and the renderer is exactly what it was.  While a sky is set EVERY render / enqueue
+ * runs a SKY build of the materials kernel -- with the renderer's material table, or, without one, with every sphere DIFFUSE
+ * (a scene above PT_MATERIALS_MAX_SPHERES is then PT_ELIMIT and nothing is launched) -- and pt_renderer_kernel_info reports
+ * PT_VARIANT_MATERIALS_SKY, or PT_VARIANT_MATERIALS_LIGHTS_SKY with light sampling on.  The order of pt_renderer_set_materials,
+ * pt_renderer_set_light_sampling and this call does not matter.  Refused (PT_EINVAL): whatever pt_sky_check refuses, a NULL
+ * renderer, a fast_math renderer, a renderer with an explicit kernel variant; while a sky is set, pt_progressive_create and a
+ * session's passes are refused, and pt_renderer_enqueue_frames is the loop of single enqueues (refused with light sampling
+ * on, as without a sky).  pt_mgpu has no sky. */
+int pt_renderer_set_sky(pt_renderer* r, const pt_sky* sky);
+
 /* ---- one frame over several GPUs of one node ------------------------------------------------- */
 /* The reference selects ONE device per process (cudaSetDevice(cudaDevice), src/main.cu:86) and its
  * Renderer covers the whole image with one launch (Renderer.h:29-33,69).  pt_mgpu_* is the same
